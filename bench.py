@@ -15,6 +15,12 @@ both sides; the reported time is the MAX over ranks; ``value`` is the total over
 (weak scaling: per-GPU batch fixed; ``--global-batch G`` = strong scaling with the reference's
 global-batch semantics, ceil(G/N) per rank, train.py:82).
 
+A plain run does only what the headline figure needs: set up, warm up, time K steps, print one JSON
+line (``ms_per_step`` = milliseconds per timed step). ``--dump-outputs DIR`` also writes the last
+timed step's loss, logits, updated parameters and gradients as ``DIR/<name>.npy`` (inputs and initial
+weights are seeded, so two builds can be compared array for array). ``--full`` is where any stage
+beyond the headline figure belongs; this benchmark has none today.
+
 --model resnet50 (default, headline) | vit_b16 | gpt2_medium (other north-star configs)
         | lenet (the reference's own LeNet/MNIST workload, fp32, Adadelta)
 --impl ours       : this framework (DDP reducer, HIP BN/LN/GELU/CE/optimizer kernels, bf16 params +
@@ -56,6 +62,10 @@ WORKLOADS = {
     "lenet": ("images/sec (whole node) LeNet-MNIST DDP (reference workload)", "images/sec", 128, "adadelta"),
 }
 
+# --dump-outputs: at most this many float32 per array (16 MiB; loss + logits + params + grads < 64 MB)
+DUMP_MAX_ELEMS = 4 << 20
+DUMP_SEED = 20240
+
 
 def parse(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -91,7 +101,34 @@ def parse(argv=None):
     ap.add_argument("--deterministic", type=int, default=0, help="MIOpen deterministic solvers (slow)")
     ap.add_argument("--backend", default=None, help="process-group backend (default: nccl = RCCL on GPU)")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the last timed step produced as DIR/<name>.npy "
+                         "(float32): loss, logits, params (after the update), grads; an array above "
+                         f"{DUMP_MAX_ELEMS} elements is a fixed seeded sample of that many")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement or check beyond the headline figure. A plain run sets up, warms "
+                         "up, times --steps steps and prints the result line; this benchmark has no further stage, so "
+                         "today the flag only records itself in the result's config")
     return ap.parse_args(argv)
+
+
+def dump_outputs(path, arrays):
+    """Write ``arrays`` (name -> tensor) as ``path/<name>.npy`` in float32. An array above DUMP_MAX_ELEMS
+    elements is sampled at fixed positions (seeded, with replacement, the same for every run and build).
+    Returns name -> {"shape", "sampled"} for the result line."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    info = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        sampled = flat.numel() > DUMP_MAX_ELEMS
+        if sampled:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            flat = flat[torch.randint(0, flat.numel(), (DUMP_MAX_ELEMS,), generator=g).to(flat.device)]
+        a = flat.float().cpu().numpy() if sampled else t.detach().float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        info[name] = {"shape": list(t.shape), "sampled": sampled}
+    return info
 
 
 def build(args, ctx):
@@ -225,6 +262,8 @@ def run(args, ctx):
             return cross_entropy(out, y, label_smoothing=ls)
         return torch.nn.functional.cross_entropy(out.float(), y, label_smoothing=ls)
 
+    kept = {} if args.dump_outputs else None
+
     def step(x, y):
         opt.zero_grad(set_to_none=True)
         xs, ys = x.chunk(args.grad_accum), y.chunk(args.grad_accum)
@@ -237,6 +276,8 @@ def run(args, ctx):
                     out = ddp(xm)
                 loss = loss_of(out, ym) / len(xs)
                 loss.backward()
+            if kept is not None:  # --dump-outputs: the last micro-batch's logits outlive the step
+                kept["logits"] = out.detach()
             total = loss.detach() if total is None else total + loss.detach()
         if args.impl == "reference" and world > 1:
             average_gradients(model)
@@ -297,6 +338,18 @@ def run(args, ctx):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0].item())
         exposed = float(t[1].item()) if t[1].item() >= 0 else None
+    dumped = None
+    if args.dump_outputs and ctx.rank == 0:
+        # what a caller of the step holds after the last timed one: its loss and logits, the updated
+        # parameters, and the (reduced) gradients the update consumed
+        params = [p for p in model.parameters() if p.requires_grad]
+        dumped = dump_outputs(args.dump_outputs, {
+            "loss": loss.reshape(1),
+            "logits": kept["logits"],
+            "params": torch.cat([p.detach().float().reshape(-1) for p in params]),
+            "grads": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().float().reshape(-1)
+                                for p in params]),
+        })
     ms = elapsed / args.steps * 1e3
     per_step = B * (T if is_lm else 1)
     value = per_step * world * args.steps / elapsed
@@ -320,7 +373,8 @@ def run(args, ctx):
                    "bucket_ready_lead_ms": None if leads is None else [round(v, 3) for v in leads],
                    "pg_size": pg_size, "pg_backend": dist.get_backend() if dist.is_initialized() else None,
                    "rank_devices": rank_devices,
-                   "deterministic": bool(det), "final_loss": round(float(loss.float().item()), 4)},
+                   "deterministic": bool(det), "final_loss": round(float(loss.float().item()), 4),
+                   "full": bool(args.full), "dumped": dumped},
     }
     return result
 

@@ -12,10 +12,34 @@ os.environ.setdefault("PDT_BWD_ALG_MIN_M", "0")
 # MIOpen reads its solver switches once per process: exclude the capture-unsafe solvers before
 # any test runs a convolution so the hipGraph tests see the same solver set as bench --graph 1
 from pytorch_distributed_training_example_amd.engine.graph import make_miopen_capture_safe  # noqa: E402
-from pytorch_distributed_training_example_amd.engine.miopen_cache import use_repo_miopen_cache  # noqa: E402
+from pytorch_distributed_training_example_amd.engine.miopen_cache import DEFAULT_DIR, use_repo_miopen_cache  # noqa: E402
+
+
+def _suite_miopen_cache():
+    """The suite's own copy of the committed find-db (git-ignored, next to it): MIOpen appends every
+    shape the tests search to its user db, which must not rewrite the committed files. A committed db
+    file is copied when the copy is missing or older; what the tests add stays for the next run."""
+    if os.environ.get("PDT_MIOPEN_CACHE"):
+        return None
+    import shutil
+    dst = os.path.join(DEFAULT_DIR, ".suite")
+    try:
+        for sub in ("db", os.path.join("capture_safe", "db")):
+            src_dir = os.path.join(DEFAULT_DIR, sub)
+            if not os.path.isdir(src_dir):
+                continue
+            os.makedirs(os.path.join(dst, sub), exist_ok=True)
+            for name in os.listdir(src_dir):
+                s, d = os.path.join(src_dir, name), os.path.join(dst, sub, name)
+                if os.path.isfile(s) and (not os.path.exists(d) or os.path.getmtime(s) > os.path.getmtime(d)):
+                    shutil.copy2(s, d)
+    except OSError:
+        return None
+    return dst
+
 
 make_miopen_capture_safe()
-use_repo_miopen_cache()
+use_repo_miopen_cache(_suite_miopen_cache())
 
 
 @pytest.fixture(autouse=True)

@@ -69,6 +69,51 @@ def test_bench_global_batch_strong_scaling():
     assert r["config"]["global_batch"] == 6 and r["n_gpus"] == 2
 
 
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs DIR: the last timed step's loss, logits, updated parameters and gradients as
+    float32 .npy (at most 64 MB in all); same arguments -> same inputs, so on CPU (deterministic
+    kernels) two runs write identical arrays. --full is accepted and recorded."""
+    import numpy as np
+    a, b = tmp_path / "a", tmp_path / "b"
+    ra = _run(1, 0, extra=("--model", "lenet", "--dump-outputs", str(a), "--full"))
+    rb = _run(1, 0, extra=("--model", "lenet", "--dump-outputs", str(b)))
+    assert ra["config"]["full"] is True and rb["config"]["full"] is False
+    assert ra["steps"] == 2 and ra["ms_per_step"] > 0
+    assert sorted(p.name for p in a.iterdir()) == ["grads.npy", "logits.npy", "loss.npy", "params.npy"]
+    assert sum(p.stat().st_size for p in a.iterdir()) <= 64 * 10 ** 6
+    for p in a.iterdir():
+        x, y = np.load(p), np.load(b / p.name)
+        assert x.dtype == np.float32 and x.shape == y.shape and np.isfinite(x).all()
+        if ra["config"]["rank_devices"] == [-1]:  # CPU: bit-identical
+            assert np.array_equal(x, y), p.name
+        else:  # on a GPU the reduction order may differ between runs: fp32 LeNet, two steps
+            np.testing.assert_allclose(x, y, rtol=1e-4, atol=1e-6, err_msg=p.name)
+    assert np.load(a / "logits.npy").shape == (2, 10)
+    assert np.load(a / "params.npy").shape == (61706,)
+    assert float(np.load(a / "loss.npy")[0]) == pytest.approx(ra["config"]["final_loss"], abs=1e-4)
+    assert np.abs(np.load(a / "grads.npy")).max() > 0
+
+
+def test_bench_dump_samples_large_arrays_at_fixed_positions(tmp_path):
+    """An array above DUMP_MAX_ELEMS elements (ResNet-50's 25.6M parameters) is written as a sample of
+    that many, at positions that depend on nothing but the array's size; bf16 comes out as float32."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n = bench.DUMP_MAX_ELEMS + 12345
+    pos = torch.arange(n, dtype=torch.float32)  # value = position (exact in float32 below 2^24)
+    info = bench.dump_outputs(str(tmp_path), {"big": pos.reshape(1, n), "again": pos + 0.0,
+                                             "small": torch.ones(3, 5, dtype=torch.bfloat16)})
+    big, again, small = (np.load(tmp_path / f"{k}.npy") for k in ("big", "again", "small"))
+    assert info["big"] == {"shape": [1, n], "sampled": True} and info["small"] == {"shape": [3, 5], "sampled": False}
+    assert big.dtype == small.dtype == np.float32
+    assert big.shape == (bench.DUMP_MAX_ELEMS,) and small.shape == (3, 5)
+    assert np.array_equal(big, again) and big.min() >= 0 and big.max() < n
+    assert len(np.unique(big)) > bench.DUMP_MAX_ELEMS // 2  # spread over the array, not one region
+    assert 4 * (3 * bench.DUMP_MAX_ELEMS) + (1 << 20) <= 64 * 10 ** 6  # loss + logits + params + grads
+
+
 def test_bench_fails_on_non_finite_loss():
     """A run whose loss ends NaN is not a measurement: bench.py exits 3 (round 6: a graphed run looked
     faster while training to NaN, profiles/r6/graph_colsum_bwd.txt)."""
