@@ -75,6 +75,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="alias: off=fp32, bf16=bf16 params+fp32 master, fp8=bf16+e4m3 transformer GEMMs")
     p.add_argument("--hipgraph", action="store_true",
                    help="replay each train step as one hipGraph (static shapes; MIOpen capture-safe solvers)")
+    p.add_argument("--sync-bn", action="store_true",
+                   help="BatchNorm statistics over all ranks (convert_sync_batchnorm before the DDP wrap); "
+                        "not with --hipgraph on more than one rank")
     p.add_argument("--profile", default=None, metavar="DIR",
                    help="torch.profiler trace of a few steps of epoch 1 into DIR (rank 0), roctx ranges on")
     return p
@@ -155,6 +158,13 @@ def run(rank: int, world: int, args) -> dict:
     if args.channels_last:
         model = model.to(memory_format=torch.channels_last)
     model = apply_precision(model, args.precision)
+    if args.sync_bn:
+        from .parallel import SyncBatchNorm, convert_sync_batchnorm
+        model = convert_sync_batchnorm(model)
+        nsync = sum(isinstance(m, SyncBatchNorm) for m in model.modules())
+        if rank == 0:
+            print(f"--sync-bn: {nsync} BatchNorm2d converted to SyncBatchNorm" if nsync else
+                  f"--sync-bn: model {args.model} has no BatchNorm2d, nothing to convert", flush=True)
 
     if args.reducer == "ddp" and world >= 1 and launcher.context().distributed:
         wrapped = DistributedDataParallel(model, bucket_cap_mb=args.bucket_cap_mb)
@@ -272,10 +282,24 @@ def _entry(rank: int, world: int, args) -> None:
     run(rank, world, args)
 
 
+SYNC_BN_HIPGRAPH_MSG = ("--sync-bn cannot be combined with --hipgraph on more than one rank: the SyncBatchNorm "
+                        "statistics exchange is a collective that hipGraph capture does not support yet")
+
+
+def _planned_world(args, use_gpu: bool) -> int:
+    if "RANK" in os.environ and "WORLD_SIZE" in os.environ:  # torchrun
+        return int(os.environ["WORLD_SIZE"])
+    if args.world_size is not None:
+        return args.world_size
+    return torch.cuda.device_count() if use_gpu else 1
+
+
 def main(argv: Optional[list] = None) -> int:
     args = build_parser().parse_args(argv)
     if args.amp is not None:
         args.precision = {"off": "fp32", "bf16": "bf16", "fp8": "fp8"}[args.amp]
+    if args.sync_bn and args.hipgraph and _planned_world(args, not args.no_cuda and torch.cuda.is_available()) > 1:
+        raise SystemExit(SYNC_BN_HIPGRAPH_MSG)
     if args.hipgraph:
         # MIOpen reads its solver switches once per process: set before any convolution
         from .engine.graph import make_miopen_capture_safe

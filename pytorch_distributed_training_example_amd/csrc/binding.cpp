@@ -66,6 +66,20 @@ int pdt_bn_fwd_eval(const uint16_t* x, const uint16_t* res, const float* gamma, 
 int pdt_bn_bwd_train(const uint16_t* dy, const uint16_t* x, const uint8_t* mask, const float* gamma,
                      const float* mean, const float* invstd, int64_t M, int C, int relu, int has_res, uint16_t* dx,
                      uint16_t* dres, float* dgamma, float* dbeta, float* ws, unsigned* counters, hipStream_t s);
+int pdt_bn_sync_fwd_stats(const uint16_t* x, int64_t M, int C, float* stats, float* count, float* ws,
+                          unsigned* counters, hipStream_t s);
+int pdt_bn_sync_fwd_merge(const float* gathered, int W, int C, const float* gamma, const float* beta,
+                          float* running_mean, float* running_var, float momentum, float eps, float* mean,
+                          float* invstd, float* ab, int64_t* ntot, hipStream_t s);
+int pdt_bn_apply_coef(const uint16_t* x, const uint16_t* res, const float* ab, int64_t M, int C, int relu,
+                      uint16_t* y, uint8_t* mask, hipStream_t s);
+int pdt_bn_sync_bwd_sums(const uint16_t* dy, const uint16_t* x, const uint8_t* mask, const float* mean, int64_t M,
+                         int C, int relu, float* sums, float* ws, unsigned* counters, hipStream_t s);
+int pdt_bn_sync_bwd_merge(const float* gathered, int W, int rank, int C, const float* gamma, const float* invstd,
+                          const int64_t* ntot, float* coef, float* dgamma, float* dbeta, hipStream_t s);
+int pdt_bn_bwd_apply_coef(const uint16_t* dy, const uint16_t* x, const uint8_t* mask, const float* mean,
+                          const float* coef, int64_t M, int C, int relu, int has_res, uint16_t* dx, uint16_t* dres,
+                          hipStream_t s);
 int pdt_ce_fwd(const void* logits, int dtype, const int64_t* target, int64_t N, int64_t V, float smoothing,
                int64_t ignore_index, float* loss, float* lse, hipStream_t s);
 int pdt_ce_bwd(const void* logits, int dtype, const int64_t* target, const float* lse, const float* dloss,
@@ -643,6 +657,170 @@ std::vector<Tensor> bn_bwd_train(Tensor dy, Tensor x, c10::optional<Tensor> mask
                             ws.data_ptr<float>(), bn_counters(x), stream());
   TORCH_CHECK(rc == 0, "pdt_bn_bwd_train failed");
   return {dx, dres, dg, db};
+}
+
+// ---- SyncBatchNorm (ops/sync_batchnorm.py): the train forward / backward split around the exchange.
+void check_f32_cuda(const Tensor& t, int64_t numel, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == numel,
+              "pdt sync bn: ", name, " must be a contiguous fp32 GPU tensor of ", numel, " elements");
+}
+
+const uint8_t* relu_mask_ptr(const c10::optional<Tensor>& mask, bool relu, int64_t bytes) {
+  if (!relu) return nullptr;
+  TORCH_CHECK(mask.has_value() && mask->defined() && mask->is_cuda() && mask->scalar_type() == at::kByte &&
+              mask->numel() == bytes, "pdt sync bn: relu needs the uint8 mask [M C / 8]");
+  return mask->data_ptr<uint8_t>();
+}
+
+// This rank's raw statistics [2, C] = (mean_r, M2_r = sum (x - mean_r)^2). row (optional, fp32 [2C + 1]): written
+// in place as (mean_r, M2_r, M) — this rank's row of the exchange buffer — and returned.
+Tensor bn_sync_fwd_stats(Tensor x, c10::optional<Tensor> row) {
+  check_nhwc_bf16(x, "x");
+  const int64_t C = x.size(1);
+  TORCH_CHECK(C % 64 == 0 && C <= 64 * 4096 && x.numel() > 0, "pdt sync bn: C must be a multiple of 64, M >= 1");
+  const int64_t M = x.numel() / C;
+  auto fopt = x.options().dtype(at::kFloat);
+  const bool in_row = row.has_value() && row->defined();
+  if (in_row) {
+    check_f32_cuda(*row, 2 * C + 1, "row");
+    TORCH_CHECK(M < (1 << 24), "pdt sync bn: the row count travels as fp32 (M < 2^24)");
+  }
+  auto stats = in_row ? *row : at::empty({2, C}, fopt);
+  auto ws = at::empty({bn_ws_floats(M, C)}, fopt);
+  const int rc = pdt_bn_sync_fwd_stats(reinterpret_cast<const uint16_t*>(x.data_ptr()), M, (int)C,
+                                       stats.data_ptr<float>(), in_row ? stats.data_ptr<float>() + 2 * C : nullptr,
+                                       ws.data_ptr<float>(), bn_counters(x), stream());
+  TORCH_CHECK(rc == 0, "pdt_bn_sync_fwd_stats failed: ", rc);
+  return stats;
+}
+
+// gathered [W, 2C + 1] (rank r: mean_r, M2_r, n_r) -> {mean, invstd, ab [2, C], ntot int64 [1]}; updates the
+// running statistics.
+std::vector<Tensor> bn_sync_fwd_merge(Tensor gathered, c10::optional<Tensor> weight, c10::optional<Tensor> bias,
+                                      c10::optional<Tensor> running_mean, c10::optional<Tensor> running_var,
+                                      double momentum, double eps) {
+  TORCH_CHECK(gathered.dim() == 2 && gathered.size(0) >= 1 && gathered.size(1) % 2 == 1,
+              "pdt sync bn: gathered must be [W, 2C + 1]");
+  const int64_t W = gathered.size(0), C = (gathered.size(1) - 1) / 2;
+  TORCH_CHECK(C >= 64 && C % 64 == 0, "pdt sync bn: C must be a multiple of 64");
+  check_f32_cuda(gathered, W * (2 * C + 1), "gathered");
+  auto opt_c = [&](const c10::optional<Tensor>& t, const char* name) -> float* {
+    if (!t.has_value() || !t->defined()) return nullptr;
+    check_f32_cuda(*t, C, name);
+    return t->data_ptr<float>();
+  };
+  auto mean = at::empty({C}, gathered.options()), invstd = at::empty({C}, gathered.options());
+  auto ab = at::empty({2, C}, gathered.options());
+  auto ntot = at::empty({1}, gathered.options().dtype(at::kLong));
+  const int rc = pdt_bn_sync_fwd_merge(gathered.data_ptr<float>(), (int)W, (int)C, opt_c(weight, "weight"),
+                                       opt_c(bias, "bias"), opt_c(running_mean, "running_mean"),
+                                       opt_c(running_var, "running_var"), (float)momentum, (float)eps,
+                                       mean.data_ptr<float>(), invstd.data_ptr<float>(), ab.data_ptr<float>(),
+                                       ntot.data_ptr<int64_t>(), stream());
+  TORCH_CHECK(rc == 0, "pdt_bn_sync_fwd_merge failed: ", rc);
+  return {mean, invstd, ab, ntot};
+}
+
+// y = relu?(ab[0] x + ab[1] + res?) -> {y, mask (with relu)}.
+std::vector<Tensor> bn_apply_coef(Tensor x, c10::optional<Tensor> res, Tensor ab, bool relu) {
+  check_nhwc_bf16(x, "x");
+  const int64_t C = x.size(1);
+  TORCH_CHECK(C % 64 == 0 && x.numel() > 0, "pdt sync bn: C must be a multiple of 64, M >= 1");
+  const int64_t M = x.numel() / C;
+  check_f32_cuda(ab, 2 * C, "ab");
+  const uint16_t* rp = nullptr;
+  if (res.has_value() && res->defined()) {
+    check_nhwc_bf16(*res, "residual");
+    TORCH_CHECK(res->sizes() == x.sizes() && res->strides() == x.strides(), "pdt sync bn: residual layout mismatch");
+    rp = reinterpret_cast<const uint16_t*>(res->data_ptr());
+  }
+  auto y = at::empty_like(x);
+  Tensor mask;
+  if (relu) mask = at::empty({M * C / 8}, x.options().dtype(at::kByte));
+  const int rc = pdt_bn_apply_coef(reinterpret_cast<const uint16_t*>(x.data_ptr()), rp, ab.data_ptr<float>(), M, (int)C,
+                                   relu, reinterpret_cast<uint16_t*>(y.data_ptr()),
+                                   relu ? mask.data_ptr<uint8_t>() : nullptr, stream());
+  TORCH_CHECK(rc == 0, "pdt_bn_apply_coef failed: ", rc);
+  return {y, mask};
+}
+
+// This rank's raw backward sums [2, C] = (sum dz, sum dz (x - mean)), dz = dy * mask with relu.
+// row (optional, fp32 [2C]): written in place (this rank's row of the exchange buffer) and returned.
+Tensor bn_sync_bwd_sums(Tensor dy, Tensor x, c10::optional<Tensor> mask, Tensor mean, bool relu,
+                        c10::optional<Tensor> row) {
+  check_nhwc_bf16(x, "x");
+  check_nhwc_bf16(dy, "dy");
+  TORCH_CHECK(dy.sizes() == x.sizes() && dy.strides() == x.strides(), "pdt sync bn: dy layout mismatch");
+  const int64_t C = x.size(1);
+  TORCH_CHECK(C % 64 == 0 && x.numel() > 0, "pdt sync bn: C must be a multiple of 64, M >= 1");
+  const int64_t M = x.numel() / C;
+  check_f32_cuda(mean, C, "mean");
+  auto fopt = x.options().dtype(at::kFloat);
+  const bool in_row = row.has_value() && row->defined();
+  if (in_row) check_f32_cuda(*row, 2 * C, "row");
+  auto sums = in_row ? *row : at::empty({2, C}, fopt);
+  auto ws = at::empty({bn_ws_floats(M, C)}, fopt);
+  const int rc = pdt_bn_sync_bwd_sums(reinterpret_cast<const uint16_t*>(dy.data_ptr()),
+                                      reinterpret_cast<const uint16_t*>(x.data_ptr()),
+                                      relu_mask_ptr(mask, relu, M * C / 8), mean.data_ptr<float>(), M, (int)C, relu,
+                                      sums.data_ptr<float>(), ws.data_ptr<float>(), bn_counters(x), stream());
+  TORCH_CHECK(rc == 0, "pdt_bn_sync_bwd_sums failed: ", rc);
+  return sums;
+}
+
+// gathered [W, 2C] (rank r: sum dz, sum dz (x - mean)) -> {coef [3, C] = A, B, D from all rows over ntot,
+// dgamma, dbeta from row `rank` only (undefined without need_dgamma)}.
+std::vector<Tensor> bn_sync_bwd_merge(Tensor gathered, int64_t rank, c10::optional<Tensor> weight, Tensor invstd,
+                                      Tensor ntot, bool need_dgamma) {
+  TORCH_CHECK(gathered.dim() == 2 && gathered.size(0) >= 1 && gathered.size(1) % 2 == 0,
+              "pdt sync bn: gathered must be [W, 2C]");
+  const int64_t W = gathered.size(0), C = gathered.size(1) / 2;
+  TORCH_CHECK(C >= 64 && C % 64 == 0, "pdt sync bn: C must be a multiple of 64");
+  TORCH_CHECK(rank >= 0 && rank < W, "pdt sync bn: rank ", rank, " outside [0, ", W, ")");
+  check_f32_cuda(gathered, W * 2 * C, "gathered");
+  check_f32_cuda(invstd, C, "invstd");
+  TORCH_CHECK(ntot.is_cuda() && ntot.scalar_type() == at::kLong && ntot.numel() == 1, "pdt sync bn: ntot int64 [1]");
+  const float* gp = nullptr;
+  if (weight.has_value() && weight->defined()) {
+    check_f32_cuda(*weight, C, "weight");
+    gp = weight->data_ptr<float>();
+  }
+  auto coef = at::empty({3, C}, gathered.options());
+  Tensor dg, db;
+  if (need_dgamma) {
+    dg = at::empty({C}, gathered.options());
+    db = at::empty({C}, gathered.options());
+  }
+  const int rc = pdt_bn_sync_bwd_merge(gathered.data_ptr<float>(), (int)W, (int)rank, (int)C, gp,
+                                       invstd.data_ptr<float>(), ntot.data_ptr<int64_t>(), coef.data_ptr<float>(),
+                                       need_dgamma ? dg.data_ptr<float>() : nullptr,
+                                       need_dgamma ? db.data_ptr<float>() : nullptr, stream());
+  TORCH_CHECK(rc == 0, "pdt_bn_sync_bwd_merge failed: ", rc);
+  return {coef, dg, db};
+}
+
+// dx = A dz + B (x - mean) + D from coef [3, C] -> {dx, dres = dz (with has_res)}.
+std::vector<Tensor> bn_bwd_apply_coef(Tensor dy, Tensor x, c10::optional<Tensor> mask, Tensor mean, Tensor coef,
+                                      bool relu, bool has_res) {
+  check_nhwc_bf16(x, "x");
+  check_nhwc_bf16(dy, "dy");
+  TORCH_CHECK(dy.sizes() == x.sizes() && dy.strides() == x.strides(), "pdt sync bn: dy layout mismatch");
+  const int64_t C = x.size(1);
+  TORCH_CHECK(C % 64 == 0 && x.numel() > 0, "pdt sync bn: C must be a multiple of 64, M >= 1");
+  const int64_t M = x.numel() / C;
+  check_f32_cuda(mean, C, "mean");
+  check_f32_cuda(coef, 3 * C, "coef");
+  auto dx = at::empty_like(x);
+  Tensor dres;
+  if (has_res) dres = at::empty_like(x);
+  const int rc = pdt_bn_bwd_apply_coef(reinterpret_cast<const uint16_t*>(dy.data_ptr()),
+                                       reinterpret_cast<const uint16_t*>(x.data_ptr()),
+                                       relu_mask_ptr(mask, relu, M * C / 8), mean.data_ptr<float>(),
+                                       coef.data_ptr<float>(), M, (int)C, relu, has_res,
+                                       reinterpret_cast<uint16_t*>(dx.data_ptr()),
+                                       has_res ? reinterpret_cast<uint16_t*>(dres.data_ptr()) : nullptr, stream());
+  TORCH_CHECK(rc == 0, "pdt_bn_bwd_apply_coef failed: ", rc);
+  return {dx, dres};
 }
 
 // ResNet stem backward: max-pool gradient (the BN's dz, never returned) with the stem BatchNorm's
@@ -2424,6 +2602,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv3x3_wgrad_tune", [](int target_wgs, int co_tile) { pdt_conv3x3_wgrad_tune(target_wgs, co_tile); });
   m.def("bn_bwd_train", &bn_bwd_train);
   m.def("bn_bwd_coef", &bn_bwd_coef);
+  m.def("bn_sync_fwd_stats", &bn_sync_fwd_stats, py::arg("x"), py::arg("row") = py::none());
+  m.def("bn_sync_fwd_merge", &bn_sync_fwd_merge);
+  m.def("bn_apply_coef", &bn_apply_coef);
+  m.def("bn_sync_bwd_sums", &bn_sync_bwd_sums, py::arg("dy"), py::arg("x"), py::arg("mask"), py::arg("mean"),
+        py::arg("relu"), py::arg("row") = py::none());
+  m.def("bn_sync_bwd_merge", &bn_sync_bwd_merge);
+  m.def("bn_bwd_apply_coef", &bn_bwd_apply_coef);
   m.def("conv1x1_bwd_fused", &conv1x1_bwd_fused, py::arg("dy"), py::arg("z"), py::arg("mz"), py::arg("mean"),
         py::arg("coef"), py::arg("w"), py::arg("xa"), py::arg("bn_x") = py::none(), py::arg("bn_mask") = py::none(),
         py::arg("bn_mean") = py::none(), py::arg("xcoef") = py::none(), py::arg("wt") = py::none());

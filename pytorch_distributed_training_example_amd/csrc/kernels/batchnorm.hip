@@ -1504,3 +1504,244 @@ int pdt_maxpool3s2_bwd_bn_coef(const uint16_t* dy, const uint8_t* code, uint16_t
 }
 
 }  // extern "C"
+
+// ---- SyncBatchNorm: the train forward / backward above, split at the point where the statistics of
+// several ranks meet (ops/sync_batchnorm.py). Each rank reduces its own rows to RAW per-channel values
+// (mean_r, M2_r = sum (x - mean_r)^2; sum dz, sum dz (x - mean)), the ranks exchange them, and a
+// one-launch merge combines the gathered rows in rank order — the same bits on every rank — into the
+// coefficients the existing apply kernels take. The reduce is bn_reduce3_kernel writing one slab per
+// block (its split-finalize mode); no float atomics anywhere.
+namespace {
+
+// Forward raw values of one channel from the shifted sums S1 = sum (x - k), S2 = sum (x - k)^2
+// (k = x[0, c], bn_finalize<0>'s arithmetic): mean_r = k + S1 / M, M2_r = S2 - S1^2 / M.
+__device__ __forceinline__ void bn_sync_raw_fwd(int ch, float S1, float S2, const uint16_t* __restrict__ x,
+                                                int64_t M, int C, float* __restrict__ out) {
+  const float kk = bf2f(x[ch]);
+  const double inv_m = 1.0 / (double)M;
+  const double d1 = (double)S1 * inv_m;
+  const double m2 = (double)S2 - (double)S1 * d1;
+  out[ch] = (float)((double)kk + d1);
+  out[C + ch] = (float)(m2 < 0.0 ? 0.0 : m2);
+}
+
+// bn_fin_kernel's slab sum — the same thread layout and summation order, so S1 / S2 are the bits the
+// local finalize sees — ending in the raw values: out [2, C] = (mean_r, M2_r) forward (FWD), or the
+// plain sums (sum dz, sum dz (x - mean)) backward. count (nullable): the row count M as a float (exact
+// below 2^24 rows), which travels with the forward statistics.
+template <bool FWD>
+__global__ __launch_bounds__(1024) void bn_sync_fin_kernel(const float* __restrict__ part, int nrow, int CC,
+                                                           const uint16_t* __restrict__ x, int64_t M, int C,
+                                                           float* __restrict__ out, float* __restrict__ count) {
+  __shared__ float sm[8 * 128];
+  const int tid = threadIdx.x;
+  const int ch0 = blockIdx.x * 64;
+  const int chunk = ch0 / CC, off = ch0 % CC;
+  const int W = 2 * CC;
+  const int col = tid & 127, j = tid >> 7;
+  const int v = (col >> 6) * CC + off + (col & 63);
+  const float* base = part + (int64_t)chunk * nrow * W + v;
+  float a = 0.f;
+  for (int b0 = j; b0 < nrow; b0 += 8 * 16) {
+    float t[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int b = b0 + 8 * u;
+      t[u] = base[(int64_t)(b < nrow ? b : j) * W];
+    }
+#pragma unroll
+    for (int u = 0; u < 16; ++u) a += (b0 + 8 * u < nrow) ? t[u] : 0.f;
+  }
+  sm[j * 128 + col] = a;
+  __syncthreads();
+  if (tid < 128) {
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) s += sm[q * 128 + tid];
+    sm[tid] = s;
+  }
+  __syncthreads();
+  if (count && blockIdx.x == 0 && tid == 0) *count = (float)M;
+  if (tid < 64) {
+    const int ch = ch0 + tid;
+    if (FWD) {
+      bn_sync_raw_fwd(ch, sm[tid], sm[64 + tid], x, M, C, out);
+    } else {
+      out[ch] = sm[tid];
+      out[C + ch] = sm[64 + tid];
+    }
+  }
+}
+
+// Forward merge of the gathered [W, 2C + 1] rows (rank r: mean_r [C], M2_r [C], n_r) in rank order, in
+// double, with Chan's formula: N = sum n_r, mean = sum n_r mean_r / N, M2 = sum M2_r + sum n_r (mean_r -
+// mean)^2 — never E[x^2] - E[x]^2. bn_set_fwd then rounds exactly as the local path does (fa.M = N).
+__global__ __launch_bounds__(256) void bn_sync_merge_fwd_kernel(const float* __restrict__ g, int W, int C, FinArgs fa,
+                                                                int64_t* __restrict__ ntot) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const int64_t stride = 2 * (int64_t)C + 1;
+  double N = 0.0, sm = 0.0;
+  for (int r = 0; r < W; ++r) {
+    const double n = (double)g[r * stride + 2 * C];
+    N += n;
+    sm += n * (double)g[r * stride + c];
+  }
+  const double mean = sm / N;
+  double m2 = 0.0, between = 0.0;
+  for (int r = 0; r < W; ++r) {
+    const double n = (double)g[r * stride + 2 * C];
+    const double d = (double)g[r * stride + c] - mean;
+    m2 += (double)g[r * stride + C + c];
+    between += n * d * d;
+  }
+  fa.M = (int64_t)N;
+  bn_set_fwd(c, mean, (m2 + between) / N, fa);
+  if (c == 0) *ntot = (int64_t)N;
+}
+
+// Backward merge of the gathered [W, 2C] sums (rank r: sum dz [C], sum dz (x - mean) [C]): the dx
+// coefficients from the sums of ALL ranks (added in rank order) over the total row count, dgamma / dbeta
+// from this rank's row alone (the data-parallel reducer averages them afterwards). bn_finalize<1>'s arithmetic.
+__global__ __launch_bounds__(256) void bn_sync_merge_bwd_kernel(const float* __restrict__ g, int W, int rank, int C,
+                                                                const int64_t* __restrict__ ntot, FinArgs fa) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  double s1 = 0.0, s2 = 0.0;
+  for (int r = 0; r < W; ++r) {
+    s1 += (double)g[(int64_t)r * 2 * C + c];
+    s2 += (double)g[(int64_t)r * 2 * C + C + c];
+  }
+  const float S1 = (float)s1, S2 = (float)s2;
+  const float is = fa.invstd[c];
+  const float gm = fa.gamma ? fa.gamma[c] : 1.f;
+  if (fa.dgamma) fa.dgamma[c] = g[(int64_t)rank * 2 * C + C + c] * is;
+  if (fa.dbeta) fa.dbeta[c] = g[(int64_t)rank * 2 * C + c];
+  const float dg = S2 * is;
+  const float inv_m = 1.f / (float)*ntot;
+  fa.A[c] = gm * is;
+  fa.B[c] = -gm * is * is * dg * inv_m;
+  fa.D[c] = -gm * is * S1 * inv_m;
+}
+
+// The reduce pass of MODE over this rank's rows (one slab per block), then the raw finalize into out [2, C].
+template <int MODE>
+void launch_reduce_raw(const uint16_t* x, const uint16_t* dy, const uint8_t* mask, const float* mean, int64_t M, int C,
+                       float* ws, unsigned* counters, float* out, float* count, hipStream_t s) {
+  const int U = MODE == 0 ? g_tune.u_fwd : g_tune.u_bwd;
+  const ReduceGeo g = reduce_geo3(M, C, U);
+  float* part = ws;
+  float* gpart = ws + (int64_t)g.nrow * 2 * C;
+  const int cc = chunk3(C);
+  const FinArgs fa{};  // unused, like the counters: the kernel returns after its slab store
+#define PDT_R3(LPR, UU)                                                                                      \
+  hipLaunchKernelGGL((bn_reduce3_kernel<MODE, LPR, UU>), dim3(g.nrow, g.nchunks), dim3(kThreads), 0, s, x, dy, \
+                     mask, mean, M, C, g.rows_per_block, g.nrow, part, gpart, counters, fa, 1)
+#define PDT_R3U(LPR)              \
+  if (U >= 8) PDT_R3(LPR, 8);     \
+  else if (U >= 4) PDT_R3(LPR, 4); \
+  else PDT_R3(LPR, 2)
+  if (cc == 512) { PDT_R3U(64); }
+  else if (cc == 256) { PDT_R3U(32); }
+  else if (cc == 128) { PDT_R3U(16); }
+  else { PDT_R3U(8); }
+#undef PDT_R3U
+#undef PDT_R3
+  hipLaunchKernelGGL(bn_sync_fin_kernel<MODE == 0>, dim3(C / 64), dim3(1024), 0, s, part, g.nrow, cc, x, M, C, out,
+                     count);
+}
+
+}  // namespace
+
+extern "C" {
+
+// This rank's raw forward statistics: stats [2, C] = (mean_r, M2_r) over its M rows; count (nullable): M as
+// a float (M < 2^24). ws: pdt_bn_workspace_floats(M, C) floats; counters as for pdt_bn_fwd_train.
+int pdt_bn_sync_fwd_stats(const uint16_t* x, int64_t M, int C, float* stats, float* count, float* ws,
+                          unsigned* counters, hipStream_t s) {
+  if (C % kCC != 0 || M < 1 || (count && M >= (1 << 24))) return -1;
+  launch_reduce_raw<0>(x, nullptr, nullptr, nullptr, M, C, ws, counters, stats, count, s);
+  return 0;
+}
+
+// Merge of the gathered forward rows [W, 2C + 1] -> mean, invstd, ab [2, C] (y = a x + b), the running
+// statistics (unbiased with the total row count, which also goes to ntot [1] for the backward merge).
+int pdt_bn_sync_fwd_merge(const float* gathered, int W, int C, const float* gamma, const float* beta,
+                          float* running_mean, float* running_var, float momentum, float eps, float* mean,
+                          float* invstd, float* ab, int64_t* ntot, hipStream_t s) {
+  if (C % kCC != 0 || W < 1) return -1;
+  FinArgs fa{};
+  fa.gamma = gamma; fa.beta = beta; fa.mean_out = mean; fa.invstd_out = invstd; fa.a_out = ab; fa.b_out = ab + C;
+  fa.running_mean = running_mean; fa.running_var = running_var; fa.momentum = momentum; fa.eps = eps;
+  hipLaunchKernelGGL(bn_sync_merge_fwd_kernel, dim3((C + 255) / 256), dim3(256), 0, s, gathered, W, C, fa, ntot);
+  return 0;
+}
+
+// y = relu?(a x + b + res?) from the caller's coefficients ab [2, C]; mask (M C / 8 bytes) with relu.
+int pdt_bn_apply_coef(const uint16_t* x, const uint16_t* res, const float* ab, int64_t M, int C, int relu,
+                      uint16_t* y, uint8_t* mask, hipStream_t s) {
+  if (C % kCC != 0 || M < 1) return -1;
+  if (relu && !mask) return -2;
+  const float* a = ab;
+  const float* b = ab + C;
+  const int64_t nvec = M * C / 8;
+  const int fixed = (2048 % C) == 0;
+  const int grid = apply_grid(nvec, res ? kApplyRes : kApplyPlain);
+  const SubOut so{};
+#define PDT_APPLY(RL, RS, MK)                                                                                 \
+  hipLaunchKernelGGL((bn_apply_kernel<RL, RS, MK, 1>), dim3(grid), dim3(256), 0, s, x, res, a, b, y, mask, \
+                     nvec, C, fixed, nullptr, nullptr, so)
+  if (relu && res) PDT_APPLY(true, true, true);
+  else if (relu) PDT_APPLY(true, false, true);
+  else if (res) PDT_APPLY(false, true, false);
+  else PDT_APPLY(false, false, false);
+#undef PDT_APPLY
+  return 0;
+}
+
+// This rank's raw backward sums: sums [2, C] = (sum dz, sum dz (x - mean)), dz = dy * mask with relu,
+// mean the merged (global) mean. ws: pdt_bn_workspace_floats(M, C) floats.
+int pdt_bn_sync_bwd_sums(const uint16_t* dy, const uint16_t* x, const uint8_t* mask, const float* mean, int64_t M,
+                         int C, int relu, float* sums, float* ws, unsigned* counters, hipStream_t s) {
+  if (C % kCC != 0 || M < 1) return -1;
+  if (relu && !mask) return -2;
+  if (relu) launch_reduce_raw<2>(x, dy, mask, mean, M, C, ws, counters, sums, nullptr, s);
+  else launch_reduce_raw<1>(x, dy, mask, mean, M, C, ws, counters, sums, nullptr, s);
+  return 0;
+}
+
+// Merge of the gathered backward rows [W, 2C] -> coef [3, C] = A, B, D and this rank's dgamma / dbeta.
+int pdt_bn_sync_bwd_merge(const float* gathered, int W, int rank, int C, const float* gamma, const float* invstd,
+                          const int64_t* ntot, float* coef, float* dgamma, float* dbeta, hipStream_t s) {
+  if (C % kCC != 0 || W < 1 || rank < 0 || rank >= W || !coef) return -1;
+  FinArgs fa{};
+  fa.gamma = gamma; fa.invstd = invstd; fa.dgamma = dgamma; fa.dbeta = dbeta;
+  fa.A = coef; fa.B = coef + C; fa.D = coef + 2 * C;
+  hipLaunchKernelGGL(bn_sync_merge_bwd_kernel, dim3((C + 255) / 256), dim3(256), 0, s, gathered, W, rank, C, ntot, fa);
+  return 0;
+}
+
+// dx = A dz + B (x - mean) + D from the caller's coef [3, C] (and dres = dz where a residual was added).
+int pdt_bn_bwd_apply_coef(const uint16_t* dy, const uint16_t* x, const uint8_t* mask, const float* mean,
+                          const float* coef, int64_t M, int C, int relu, int has_res, uint16_t* dx, uint16_t* dres,
+                          hipStream_t s) {
+  if (C % kCC != 0 || M < 1) return -1;
+  if ((relu && !mask) || (has_res && !dres)) return -2;
+  const float* A = coef;
+  const float* B = coef + C;
+  const float* D = coef + 2 * C;
+  const int64_t nvec = M * C / 8;
+  const int fixed = (2048 % C) == 0;
+  const int grid = apply_grid(nvec, kApplyBwd);
+#define PDT_BAPPLY(RL, RS)                                                                                      \
+  hipLaunchKernelGGL((bn_bwd_apply_kernel<RL, RS, 1>), dim3(grid), dim3(256), 0, s, dy, x, mask, mean, A, B, D, \
+                     dx, dres, nvec, C, fixed)
+  if (relu && has_res) PDT_BAPPLY(true, true);
+  else if (relu) PDT_BAPPLY(true, false);
+  else if (has_res) PDT_BAPPLY(false, true);
+  else PDT_BAPPLY(false, false);
+#undef PDT_BAPPLY
+  return 0;
+}
+
+}  // extern "C"

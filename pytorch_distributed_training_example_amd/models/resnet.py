@@ -20,6 +20,7 @@ import torch
 from torch import nn
 
 from ..ops.batchnorm import BatchNorm2d, BNGradLink, ResidualGradLink
+from ..ops.sync_batchnorm import SyncBatchNorm
 from ..config import SW
 from ..ops._native import disabled as native_disabled
 from ..ops.conv import Conv1x1, SplitConv2d, linked_conv, prepare_weights, stem_block
@@ -69,7 +70,7 @@ def _bn_trains(bn: nn.Module) -> bool:
 
 def bn_act(bn: nn.Module, x, residual=None, relu: bool = False):
     """relu?(bn(x) + residual?) — one fused kernel for our BN, three ops for torch's."""
-    if isinstance(bn, BatchNorm2d):
+    if isinstance(bn, (BatchNorm2d, SyncBatchNorm)):
         return bn(x, residual=residual, relu=relu)
     y = bn(x)
     if residual is not None:
