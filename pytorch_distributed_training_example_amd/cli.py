@@ -54,7 +54,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--clip-grad", type=float, default=0.0)
     p.add_argument("--reducer", default="ddp", help="ddp (ours) | torch_ddp | reference (per-param)")
     p.add_argument("--bucket-cap-mb", type=float, default=25.0)
-    p.add_argument("--sharding", default="split", help="split (reference SplitDataset) | sampler (DistributedSampler)")
+    p.add_argument("--sharding", default="split", help="split (reference SplitDataset; shards may differ by one sample, ranks with fewer steps join() "
+                        "the others: see README 'Uneven inputs') | sampler (DistributedSampler, equal shards)")
     p.add_argument("--loader", default="resident", help="resident (whole shard in HBM) | reference (DataLoader)")
     p.add_argument("--synthetic", default="auto", help="auto | yes | no (MNIST source)")
     p.add_argument("--data-dir", default="./data")

@@ -132,16 +132,74 @@ class TrainStep:
         return total / n
 
 
+UNEVEN_MSG = ("ranks would run different numbers of training steps this epoch (per rank: {counts}), and {why} "
+              "cannot train through uneven step counts: a rank would be left alone in a collective. Use "
+              "--sharding sampler (DistributedSampler pads every shard to the same length) or a sample count "
+              "divisible by world size x per-rank batch size")
+
+
+def agree_step_counts(step: TrainStep, n_steps: int, device) -> Optional[list]:
+    """Every rank's planned step count for this epoch (one small all-reduce of a zero-filled one-slot-per-rank
+    tensor), or None where uneven counts are not this loop's business: one rank, or a model that is neither
+    our DDP wrapper nor reduced by ``reducer='reference'``."""
+    from ..parallel.ddp import DistributedDataParallel
+    if not (dist.is_available() and dist.is_initialized()):
+        return None
+    ours = isinstance(step.model, DistributedDataParallel)
+    group = step.model.process_group if ours else None
+    world = dist.get_world_size(group)
+    if world == 1 or not (ours or step.cfg.reducer == "reference"):
+        return None
+    dev = torch.device(device) if dist.get_backend(group) != "gloo" else torch.device("cpu")
+    t = torch.zeros(world, dtype=torch.int64, device=dev)
+    t[dist.get_rank(group)] = n_steps
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return [int(c) for c in t.tolist()]
+
+
+def uneven_refusal(step: TrainStep, counts: list) -> Optional[str]:
+    """The error message if this configuration cannot run ``counts`` (unequal) steps per rank, else None."""
+    from ..ops.sync_batchnorm import SyncBatchNorm
+    why = None
+    if step._graphs is not None:
+        why = "hipGraph step capture (--hipgraph / TrainStep.enable_graph)"
+    elif step.cfg.reducer == "reference":
+        why = "--reducer reference (average_gradients)"
+    elif any(isinstance(m, SyncBatchNorm) for m in step.raw_model.modules()):
+        why = "--sync-bn (SyncBatchNorm)"
+    return None if why is None else UNEVEN_MSG.format(counts=counts, why=why)
+
+
 def train_epoch(step: TrainStep, loader, device, epoch: int, log_interval: int = 15, dry_run: bool = False,
                 rank: Optional[int] = None, metrics=None, max_steps: Optional[int] = None,
                 input_dtype: Optional[torch.dtype] = None, channels_last: bool = False,
                 on_step: Optional[Callable[[int, int], None]] = None) -> dict:
     """Reference-compatible train loop (log line format of train.py:52-55).
 
-    ``on_step(epoch, batch_idx)`` runs after every optimizer step (fault injection, profiling)."""
+    ``on_step(epoch, batch_idx)`` runs after every optimizer step (fault injection, profiling).
+
+    With our DDP wrapper on more than one rank, the ranks first agree on how many steps each will run. Equal
+    counts: the loop runs as it is. Unequal counts (``SplitDataset`` shards differ by up to one sample): the
+    loop runs inside ``DistributedDataParallel.join()``; configurations that cannot be joined raise
+    ``UNEVEN_MSG`` on every rank before the first step."""
     rank = launcher.get_rank() if rank is None else rank
     step.model.train()
     nb = len(loader)
+    n_steps = min(nb, 1) if dry_run else (nb if max_steps is None else min(nb, max_steps))
+    counts = agree_step_counts(step, n_steps, device)
+    join_ctx = contextlib.nullcontext()
+    if counts is not None and len(set(counts)) > 1:
+        msg = uneven_refusal(step, counts)
+        if msg is not None:
+            raise RuntimeError(msg)
+        join_ctx = step.model.join()
+    with join_ctx:
+        return _train_loop(step, loader, device, epoch, log_interval, dry_run, rank, metrics, max_steps,
+                           input_dtype, channels_last, on_step, nb)
+
+
+def _train_loop(step, loader, device, epoch, log_interval, dry_run, rank, metrics, max_steps, input_dtype,
+                channels_last, on_step, nb) -> dict:
     t0 = time.perf_counter()
     seen = 0
     for batch_idx, (data, target) in enumerate(loader):

@@ -22,7 +22,9 @@ state_dict, rank-0 parameter/buffer broadcast) built for MI355X:
   * after the first iteration buckets are rebuilt in the order gradients actually
     became ready (rank 0's order is broadcast so all ranks agree);
   * optional ``reduce_dtype`` (e.g. reduce bf16 gradients in fp32) and comm hooks
-    (bf16/fp16 compression, per-rank debugging).
+    (bf16/fp16 compression, per-rank debugging);
+  * ``join()``: ranks may run different numbers of iterations; a rank that ran out of data shadows the
+    collectives of the ranks still training (torch's uneven-inputs semantics).
 """
 from __future__ import annotations
 
@@ -38,6 +40,7 @@ import torch.nn as nn
 
 from ..ops._native import cuda_available
 from ..ops import multi_tensor
+from ..ops.sync_batchnorm import SyncBatchNorm
 from .debug import ReducerDebug
 from .buckets import (AUTO_TAIL_BYTES, DEFAULT_BUCKET_CAP_MB, DEFAULT_FIRST_BUCKET_BYTES, BucketSpec,
                       compute_bucket_assignment, plan_auto)
@@ -123,6 +126,19 @@ class _Bucket:
         self.future = None
 
 
+class _JoinState:
+    """What one ``join()`` context carries (``DistributedDataParallel._join``)."""
+
+    def __init__(self, divide_by_initial_world_size: bool, throw_on_early_termination: bool):
+        self.divide_by_initial_world_size = divide_by_initial_world_size
+        self.throw = throw_on_early_termination
+        self.last: Optional[torch.Tensor] = None        # the last non-zero notify result (device)
+        # divide_by_initial_world_size=False: device scalars from the notify result, applied to every
+        # reduced bucket with the multi-tensor scale (never read on the host)
+        self.rescale: Optional[torch.Tensor] = None     # world / active: after an average over world
+        self.inv_active: Optional[torch.Tensor] = None  # 1 / active: after a plain SUM
+
+
 def _default_avg_op(pg) -> tuple[Any, bool]:
     """(op, needs_divide). RCCL averages in-collective; gloo has no AVG.
 
@@ -201,6 +217,7 @@ class DistributedDataParallel(nn.Module):
         self._callback_queued = False
         self._next_bucket = 0
         self._num_iterations = 0
+        self._join: Optional[_JoinState] = None  # set inside a join() context only
         # exposed-communication timing (enable_comm_timing): per backward, events on the compute
         # stream at the start of _finalize_backward and after the last bucket's wait
         self._comm_timing = False
@@ -237,16 +254,17 @@ class DistributedDataParallel(nn.Module):
                               for i, p in enumerate(self._params)]
 
     # ------------------------------------------------------------------ setup
-    def _sync_module_states(self) -> None:
-        """Broadcast rank 0's parameters and buffers (coalesced by dtype).
+    def _sync_module_states(self, src: int = 0) -> None:
+        """Broadcast rank ``src``'s (default: rank 0's) parameters and buffers (coalesced by dtype).
 
         The reference relies on every rank using the same seed (train.py:80-81) and never
         broadcasts; a broadcast makes replicas identical regardless of init RNG.
         """
         tensors = [p.data for p in self.module.parameters()] + list(self._buffers_to_sync)
-        self._broadcast_coalesced(tensors)
+        self._broadcast_coalesced(tensors, src=src)
 
-    def _broadcast_coalesced(self, tensors: List[torch.Tensor], bucket_bytes: int = 256 << 20) -> None:
+    def _broadcast_coalesced(self, tensors: List[torch.Tensor], bucket_bytes: int = 256 << 20, src: int = 0) -> None:
+        """``src``: the sending rank within the process group (rank 0 unless a join() context names another)."""
         by_key: Dict[Any, List[torch.Tensor]] = {}
         for t in tensors:
             if t.numel() == 0:
@@ -261,8 +279,8 @@ class DistributedDataParallel(nn.Module):
                     size += t.numel() * t.element_size()
                 if chunk and (t is None or size >= bucket_bytes):
                     flat = torch.cat([c.reshape(-1) for c in chunk])
-                    dist.broadcast(flat, src=dist.get_global_rank(self.process_group, 0)
-                                   if self.process_group not in (None, dist.group.WORLD) else 0,
+                    dist.broadcast(flat, src=dist.get_global_rank(self.process_group, src)
+                                   if self.process_group not in (None, dist.group.WORLD) else src,
                                    group=self.process_group)
                     off = 0
                     for c in chunk:
@@ -387,6 +405,8 @@ class DistributedDataParallel(nn.Module):
         self._launch_ready_buckets()
         works = [(b.index, b.future if b.future is not None else b.work) for b in self._buckets] \
             if self._debug is not None else None
+        # join(divide_by_initial_world_size=False): divide by the ranks still active instead of the world
+        rescale = self._join.rescale if self._join is not None else None
         for bucket in self._buckets:
             if bucket.future is not None:
                 out = bucket.future.wait()
@@ -394,10 +414,17 @@ class DistributedDataParallel(nn.Module):
                     out = out[0]
                 if out is not None and out.data_ptr() != bucket.buffer.data_ptr():
                     bucket.buffer.copy_(out.view(-1)[: bucket.buffer.numel()])
+                if rescale is not None:  # the hook averaged over the world
+                    multi_tensor.scale_([bucket.buffer], rescale)
             elif bucket.work is not None:
                 bucket.work.wait()  # stream-ordered: compute stream waits on the RCCL stream
                 if self._needs_div:
-                    bucket.comm_buffer.div_(self.world_size)
+                    if rescale is not None:
+                        multi_tensor.scale_([bucket.comm_buffer], self._join.inv_active)
+                    else:
+                        bucket.comm_buffer.div_(self.world_size)
+                elif rescale is not None:  # ReduceOp.AVG divided by the world
+                    multi_tensor.scale_([bucket.comm_buffer], rescale)
                 if bucket.comm_buffer is not bucket.buffer:
                     multi_tensor.copy_([bucket.comm_buffer], [bucket.buffer])
             if not self.gradient_as_bucket_view:
@@ -437,11 +464,128 @@ class DistributedDataParallel(nn.Module):
 
     # ------------------------------------------------------------------ API
     def forward(self, *inputs, **kwargs):
+        src = 0 if self._join is None else self._join_pre_forward()
         if torch.is_grad_enabled() and self.require_backward_grad_sync:
             self._maybe_rebuild()
         if self.broadcast_buffers and self.world_size > 1 and self._buffers_to_sync:
-            self._broadcast_coalesced(list(self._buffers_to_sync))
+            self._broadcast_coalesced(list(self._buffers_to_sync), src=src)
         return self.module(*inputs, **kwargs)
+
+    # ------------------------------------------------------------------ uneven inputs (join)
+    def _join_notify(self, active: bool, sync: bool) -> torch.Tensor:
+        """All-reduce (SUM) the notify tensor: ``world + 1`` fp32 elements, element r = 1 if rank r is active,
+        the last = 1 if this iteration's backward synchronises gradients. A joined rank sends zeros. Adding
+        zeros is exact (the one-row-per-rank exchange of ops/sync_batchnorm.py), so from the one result every
+        rank knows the active count, the highest active rank and whether anyone syncs."""
+        js, w = self._join, self.world_size
+        row = [0.0] * (w + 1)
+        if active:
+            row[dist.get_rank(self.process_group)] = 1.0
+            row[w] = 1.0 if sync else 0.0
+        dev = self._buckets[0].buffer.device if self._buckets else torch.device("cpu")
+        t = torch.tensor(row, dtype=torch.float32, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.process_group)
+        if active and not js.divide_by_initial_world_size:
+            n = t[:w].sum().reshape(1)  # >= 1: this rank is in it
+            js.inv_active = torch.reciprocal(n)
+            js.rescale = float(w) / n
+        return t
+
+    def _join_pre_forward(self) -> int:
+        """An active rank's forward inside join(): notify; returns the rank whose buffers are broadcast (the
+        highest active rank: a joined rank 0's running statistics are stale). The result is read on the host
+        only where a value from it is needed here."""
+        js, w = self._join, self.world_size
+        t = self._join_notify(True, torch.is_grad_enabled() and self.require_backward_grad_sync)
+        js.last = t
+        need_src = self.broadcast_buffers and bool(self._buffers_to_sync)
+        if not (js.throw or need_src):
+            return 0
+        v = t.tolist()
+        if js.throw and sum(x > 0 for x in v[:w]) < w:
+            raise RuntimeError("Detected at least one rank that exhausted inputs. Throwing across all ranks.")
+        return max(r for r in range(w) if v[r] > 0)
+
+    def _join_shadow(self) -> None:
+        """A joined rank: until no rank is active, issue the collectives of one active iteration (same order,
+        sizes and dtypes) through the real code paths, contributing zero gradients."""
+        js, w = self._join, self.world_size
+        while True:
+            t = self._join_notify(False, False)
+            v = t.tolist()
+            active = sum(x > 0 for x in v[:w])
+            if active == 0:
+                return
+            if js.throw:
+                raise RuntimeError(f"Rank {dist.get_rank(self.process_group)} exhausted all inputs.")
+            js.last = t
+            if not js.divide_by_initial_world_size:  # the same scaling as the active ranks (debug checksums)
+                n = t[:w].sum().reshape(1)
+                js.inv_active = torch.reciprocal(n)
+                js.rescale = float(w) / n
+            sync = v[w] > 0
+            if sync:
+                self._maybe_rebuild()
+            if self.broadcast_buffers and self._buffers_to_sync:
+                self._broadcast_coalesced(list(self._buffers_to_sync), src=max(r for r in range(w) if v[r] > 0))
+            if sync:
+                for b in self._buckets:
+                    b.buffer.zero_()
+                    b.arrived = [True] * len(b.params)
+                    b.pending = 0
+                    b.zero_slots, b.copy_src, b.copy_dst, b.copy_params = [], [], [], []
+                self._launch_ready_buckets()
+                self._finalize_backward()
+
+    def _join_final_sync(self) -> None:
+        """Every rank has seen the last non-zero notify vector; the highest rank in it took every step:
+        broadcast its parameters and buffers."""
+        js, w = self._join, self.world_size
+        if js.last is None:  # no rank ran a step
+            return
+        v = js.last.tolist()
+        self._sync_module_states(src=max(r for r in range(w) if v[r] > 0))
+
+    @contextlib.contextmanager
+    def join(self, divide_by_initial_world_size: bool = True, enable: bool = True,
+             throw_on_early_termination: bool = False):
+        """Train through uneven inputs (``torch.nn.parallel.DistributedDataParallel.join``): inside the
+        context each rank may run a different number of iterations, zero included.
+
+        Every forward of an active rank first all-reduces a ``world + 1`` element notify tensor. A rank that
+        leaves the body normally shadows the others: per remaining iteration it joins the notify, the bucket
+        rebuild broadcast, the buffer broadcast (from the highest active rank) and, with zero gradients,
+        every bucket's reduction (comm hooks, ``reduce_dtype`` and debug mode included), until no rank is
+        active. Then the last joiner's parameters and buffers are broadcast, so every replica ends with the
+        model that took every step. Optimizer state on ranks that joined early stays one or more steps
+        behind, as in torch; synchronise it yourself if training continues on those ranks.
+
+        ``divide_by_initial_world_size``: True averages over the initial world size (a joined rank counts
+        as a zero gradient); False divides by the number of ranks still active.
+        ``throw_on_early_termination``: raise ``RuntimeError`` on every rank as soon as one rank has joined.
+        ``enable=False``, one rank or no process group: a no-op without any collective.
+
+        Refused (``RuntimeError`` at entry): a module containing ``SyncBatchNorm`` (its forward collectives
+        cannot be shadowed) and entering during a stream capture. A rank that leaves the body through an
+        exception does not shadow; the exception propagates."""
+        if not enable or self.process_group is None or self.world_size == 1:
+            yield
+            return
+        if self._join is not None:
+            raise RuntimeError("join() is already active on this DistributedDataParallel")
+        if any(isinstance(m, SyncBatchNorm) for m in self.module.modules()):
+            raise RuntimeError("join() does not support a module containing SyncBatchNorm: its forward "
+                               "statistics exchange is a collective a joined rank cannot shadow")
+        if cuda_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("join() cannot be entered while a stream capture is in progress: a joined rank "
+                               "shadows collectives from the host")
+        self._join = _JoinState(bool(divide_by_initial_world_size), bool(throw_on_early_termination))
+        try:
+            yield
+            self._join_shadow()
+            self._join_final_sync()
+        finally:
+            self._join = None
 
     @contextlib.contextmanager
     def no_sync(self):
