@@ -46,10 +46,12 @@ PDT_BWD_ALG                 2            bottleneck conv3 + bn3 backward (the sh
                                          bn3's apply pass: z = a W^T substituted into bn3's backward (ops/conv.py
                                          _bwd_alg, csrc/kernels/bn_alg.hip): one wgrad pass + one data-gradient GEMM;
                                          2: also bn3's backward reduction without reading z (sum-only producer)
-PDT_Z3_VIRTUAL              0            (with PDT_BWD_ALG=2) a bottleneck conv3 output (bn3 input) is never written —
-                                         statistics-only GEMM, bn3's apply as the GEMM again (APPLY epilogue): 1 every
-                                         block; 2 only where that APPLY GEMM runs anyway (conv3 input channels <=
-                                         PDT_BN_APPLY_GEMM_K: the skipped store is then pure gain)
+PDT_Z3_VIRTUAL              2            (with PDT_BWD_ALG=2) a bottleneck conv3 output (bn3 input) is never written —
+                                         statistics-only GEMM (conv1x1.hip NOST: no store instruction at all), bn3's
+                                         apply as the GEMM again (APPLY epilogue): 1 every block; 2 only where that
+                                         APPLY GEMM runs anyway (conv3 input channels <= PDT_BN_APPLY_GEMM_K); 0 off.
+                                         Round 7, with PDT_BN_APPLY_GEMM_K=128: +1.7..2.0 % over off, results bit for
+                                         bit the same (profiles/r7/ab_z3_virtual_default.txt, dump_compare.txt)
 PDT_ALG_GLO                 1            the ALG data gradient carries G = W^T diag(B) W as a bf16 hi + lo pair (a twice
                                          in K). 0 (hi only, K = C4 + CW + 32) ran +1.0 % but is NOT kept: the dropped
                                          lo half is a fixed matrix, so its error a (G - G_hi) is correlated with bn2's
@@ -69,14 +71,22 @@ PDT_BN2_DEFER               0            1: with PDT_BWD_FUSED, bn2's apply + Re
                                          operand transform then runs in both GEMM passes): off
 PDT_SUB_OUT                 1            a ResNet stage's last BatchNorm apply also writes the stride-2 subsample the next
                                          stage's strided 1x1 shortcut reads (its gather pass does not run)
-PDT_BN_APPLY_GEMM_K         0            a BatchNorm(+residual)+ReLU apply after a 1x1 conv with <= this many input
+PDT_BN_APPLY_GEMM_K         128          a BatchNorm(+residual)+ReLU apply after a 1x1 conv with <= this many input
                                          channels runs as that conv's GEMM again with the apply epilogue (reads
                                          the conv input, C/4 channels, instead of its output; 0 = off). Round 4
                                          (256-channel GEMM tiles): 128 (layers 1-2) +0.7 % over off, 64 +0.2 % over
                                          128 (profiles/r4/ab_bn_apply_gemm.md). Round 6, with the ALG backward: 64
                                          is 0.4 % SLOWER than off (16,202-16,226 vs 16,265-16,287 img/s, same box,
-                                         profiles/r6/ab_apply_gemm_r6.txt): the layer-1 APPLY GEMM runs at ~4 TB/s
-                                         (906-1217 us) against the 5.4 TB/s apply pass
+                                         profiles/r6/ab_apply_gemm_r6.txt): the layer-1 APPLY GEMM ran at ~4 TB/s
+                                         (906-1217 us) against the 5.4 TB/s apply pass. Round 7: the APPLY GEMM is
+                                         persistent (8-wave tile staged in four parts, two workgroups per CU,
+                                         coefficients in LDS): 886 -> 736-765 us in layer 1 (5.1-5.3 TB/s), 505 -> 424
+                                         in layer 2 (profiles/r7/conv1x1_probe_b1024.txt); with PDT_Z3_VIRTUAL=2,
+                                         128 (layers 1-2) beats 64 (layer 1) beats off in every run of the whole-step
+                                         A/B (profiles/r7/ab_z3_virtual_default.txt). A stage's last block takes it too:
+                                         its stride-2 subsample (PDT_SUB_OUT) then comes from the gather kernel right
+                                         behind the GEMM, +0.4 % over keeping that block on the standalone apply. A
+                                         downsample block's shortcut conv always writes its output
 PDT_LINEAR_EPILOGUE         auto         Linear forward GEMMs (+bias, MLP fc1+bias+GELU) on our MFMA kernel (gemm.hip)
                                          per shape by measurement (tuning/linear_gfx950.json, else timed once);
                                          1 / 0: forced on / off
@@ -153,13 +163,13 @@ class _Switches:
         self.alg_glo = on("PDT_ALG_GLO", "1")
         # bottleneck conv3 on the ALG backward: z (bn3's input) never written — statistics-only GEMM, bn3 applied by
         # the GEMM again (APPLY epilogue); recomputed only on a fallback (ops/conv.py materialize_virtual)
-        self.z3_virtual = int(e("PDT_Z3_VIRTUAL", "0"))
+        self.z3_virtual = int(e("PDT_Z3_VIRTUAL", "2"))
         # the ALG backward also for the conv3 shapes the fused kernel takes (ResNet-50 layer 1: 256x64)
         self.bwd_alg_first = on("PDT_BWD_ALG_FIRST", "1")
         # the ALG backward for the downsample shortcut conv + BN (input channels <= this; 0 = off)
         self.ds_alg = int(e("PDT_DS_ALG", "512"))
         self.bn2_defer = on("PDT_BN2_DEFER", "0")
-        self.bn_apply_gemm_k = int(e("PDT_BN_APPLY_GEMM_K", "0"))
+        self.bn_apply_gemm_k = int(e("PDT_BN_APPLY_GEMM_K", "128"))
         self.strided_bstats = on("PDT_STRIDED_BSTATS")
         self.gap_native = on("PDT_GAP_NATIVE")
         self.sub_out = on("PDT_SUB_OUT")

@@ -175,6 +175,7 @@ int pdt_conv1x1_gemm(const uint16_t* a, const uint16_t* b, uint16_t* y, const ui
                      hipStream_t s, int nostore);
 void pdt_conv1x1_probe(int probe);
 int pdt_conv1x1_persist(int mode);
+int pdt_conv1x1_last_persistent();
 int pdt_conv3x3_opt(int v);
 int pdt_conv3x3s1_stats_tile_rows(int N, int H, int W, int Ci, int Co);
 int pdt_conv3x3s1_bnbwd_tile_rows(int N, int H, int W, int Ci, int Co);
@@ -2547,6 +2548,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv1x1_probe", [](int probe) { pdt_conv1x1_probe(probe); });
   m.def("conv1x1_persist", [](int mode) { return pdt_conv1x1_persist(mode); },
         "1x1 GEMM persistence mode (0 off, 1 measured kinds, 2 all, -1 env default); returns the previous mode");
+  m.def("conv1x1_last_persistent", []() { return pdt_conv1x1_last_persistent(); },
+        "which kernel the last 1x1 GEMM call launched: 0 one tile per workgroup, else the persistent kernel's waves "
+        "per workgroup (+256 statistics-only, +512 APPLY)");
   m.def("conv3x3_opt", [](int v) { return pdt_conv3x3_opt(v); },
         "3x3 conv variant bits (csrc/kernels/conv3x3.hip conv3x3_opt; -1 env default); returns the previous value");
   m.def("weight_prep", &weight_prep);

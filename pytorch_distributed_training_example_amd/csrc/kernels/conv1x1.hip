@@ -38,7 +38,12 @@
 //                 BatchNorm's output relu(a z + b + r) and its ReLU bits instead of z, with r the residual
 //                 (or ra r + rb, a deferred shortcut BatchNorm). A ResNet bottleneck's bn3 apply pass then
 //                 reads conv3's input (C/4 channels) instead of z (C channels): 0.75 of a tensor less
-//                 traffic per block; z is still stored by the first run for the backward.
+//                 traffic per block. Where the backward never reads z either (the ALG backward, bn_alg.hip)
+//                 the first run is the statistics-only variant below and z is never written at all.
+//
+//   NOST (STATS forward only): the statistics-only GEMM. The tile is staged in LDS and reduced exactly as
+//                 in the storing STATS kernel (same rounded values, same order: the partials are bit-identical
+//                 to the storing kernel's), but no instruction touches Y: no row stores, no sink stores.
 //
 //   BSTATS (data grad only): the output Y is the gradient dy at a BatchNorm's output, and that
 //                 BatchNorm's backward reduction is taken here instead of in a separate pass over
@@ -137,20 +142,23 @@ struct ApArgs {
   const uint16_t* a2;
   int k1, k2, rep2;
   // nostore (STATS forward): the statistics only, Y is not written (ops/conv.py: a bottleneck conv3 whose output
-  // is consumed only by its BatchNorm's statistics and its recomputed APPLY GEMM, and never by the backward)
+  // is consumed only by its BatchNorm's statistics and its recomputed APPLY GEMM, and never by the backward).
+  // Host-side only: it selects the NOST instantiations, the kernels never read it.
   int nostore;
 };
 
 int g_probe = 0;
 
 // NT: streaming (non-temporal) output stores. ATR: acoef = [2][K] fp32 (a, then b), see the header.
-template <class Cf, bool ACC, bool STATS, bool NT, bool BSTATS, bool ATR = false, bool APPLY = false, bool STR = false>
+template <class Cf, bool ACC, bool STATS, bool NT, bool BSTATS, bool ATR = false, bool APPLY = false, bool STR = false,
+          bool NOST = false>
 __global__ __launch_bounds__(Cf::kThreads, Cf::kMinWaves) void conv1x1_kernel(
     const uint16_t* __restrict__ A, const uint16_t* __restrict__ B, uint16_t* Y, const uint16_t* Cin,
     const uint8_t* __restrict__ Cmask, float* __restrict__ part, int M, int K, int N, BnSrc bs, CGeom cg,
     const float* __restrict__ acoef, ApArgs ap) {
   static_assert(!(APPLY && (ACC || STATS || BSTATS)), "APPLY is a forward epilogue of its own");
   static_assert(!STR || ACC, "STR: a strided accumulate source");
+  static_assert(!NOST || (STATS && !ACC && !BSTATS && !APPLY && !NT), "NOST: the statistics-only forward");
   constexpr int BM = Cf::BM, BN = Cf::BN;
   constexpr int WROWS = BM / Cf::WM, WCOLS = BN / Cf::WN;
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -423,12 +431,14 @@ __global__ __launch_bounds__(Cf::kThreads, Cf::kMinWaves) void conv1x1_kernel(
     if constexpr (APPLY) {
       if (!(probe & 32)) ap.mask[off >> 3] = (uint8_t)amb;
     }
-    if ((probe & 1) || ap.nostore) continue;
-    if constexpr (NT) {
-      const u32x4 t = {v.x, v.y, v.z, v.w};
-      __builtin_nontemporal_store(t, reinterpret_cast<u32x4*>(Y + off));
-    } else {
-      *reinterpret_cast<uint4*>(Y + off) = v;
+    if constexpr (!NOST) {
+      if (probe & 1) continue;
+      if constexpr (NT) {
+        const u32x4 t = {v.x, v.y, v.z, v.w};
+        __builtin_nontemporal_store(t, reinterpret_cast<u32x4*>(Y + off));
+      } else {
+        *reinterpret_cast<uint4*>(Y + off) = v;
+      }
     }
   }
   }
@@ -458,11 +468,15 @@ __global__ __launch_bounds__(Cf::kThreads, Cf::kMinWaves) void conv1x1_kernel(
 // D2 (at step 0), D3 (step 1), ... Waiting for D_s leaves younger: D_{s+1} when it exists, plus the
 // previous epilogue's row stores while s < 2. Every row store is issued by every thread (rows past M
 // go to a sink) so the count is exact; the statistics stores come last and only make a wait stricter.
-template <class Cf>
+// HV: the tile is staged in HV parts, one after the other through one area of BM / HV rows (0: whole when it fits
+// next to slots 0 / 1, else in halves). The APPLY epilogue of the 8-wave tile uses 4: 73 KB instead of 116 KB, so
+// two workgroups share a CU and one's residual loads and output stores run under the other's main loop.
+template <class Cf, int HV = 0>
 struct PL {
   static constexpr int kStgOff = 2 * Cf::kSlot;              // slots 0 / 1 take tile t+1's D0 / D1
   static constexpr int kFull = Cf::BM * Cf::kEpiStride;
-  static constexpr int kHalves = kStgOff + kFull <= 152 * 1024 ? 1 : 2;
+  static constexpr int kHalves = HV > 0 ? HV : (kStgOff + kFull <= 152 * 1024 ? 1 : 2);
+  static_assert(Cf::WM % kHalves == 0, "a part is whole wave rows");
   static constexpr int kStg = kFull / kHalves;
   static constexpr int kRed0 = Cf::kWaves * (Cf::BN / 8) * 16 * 4, kRed1 = Cf::kWaves * 2 * Cf::BN * 4;
   static constexpr int kRed = kRed0 > kRed1 ? kRed0 : kRed1;
@@ -486,14 +500,20 @@ __device__ __forceinline__ void wait_vmn() {  // s_waitcnt vmcnt(N), expcnt / lg
   __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
 }
 
-template <class Cf, bool ACC, bool STATS, bool BSTATS, bool ATR, bool APPLY, bool STR>
-__global__ __launch_bounds__(Cf::kThreads, PL<Cf>::kMinWaves) void conv1x1p_kernel(
+// APPLY keeps its per-channel coefficients (a, b, ra, rb of the tile's BN columns) in an LDS table past kLds,
+// refilled only when the workgroup's column block changes, and reads them per row, four channels at a time (LDS
+// traffic is no limit here: the kernel is HBM-bound at ~16 us per tile per CU): held in registers
+// for the whole epilogue (32 floats per lane next to the packed accumulators and the residual batch) they
+// spilled at 128 registers per lane.
+template <class Cf, bool ACC, bool STATS, bool BSTATS, bool ATR, bool APPLY, bool STR, bool NOST = false, int HV = 0>
+__global__ __launch_bounds__(Cf::kThreads, (PL<Cf, HV>::kMinWaves)) void conv1x1p_kernel(
     const uint16_t* __restrict__ A, const uint16_t* __restrict__ B, uint16_t* Y, const uint16_t* Cin,
     const uint8_t* __restrict__ Cmask, float* __restrict__ part, int M, int K, int N, BnSrc bs, CGeom cg,
     const float* __restrict__ acoef, ApArgs ap) {
   static_assert(!(APPLY && (ACC || STATS || BSTATS)), "APPLY is a forward epilogue of its own");
   static_assert(!STR || ACC, "STR: a strided accumulate source");
-  using L = PL<Cf>;
+  static_assert(!NOST || (STATS && !ACC && !BSTATS && !APPLY), "NOST: the statistics-only forward");
+  using L = PL<Cf, HV>;
   constexpr int BM = Cf::BM, BN = Cf::BN, kG = Cf::kG, kHalves = L::kHalves;
   constexpr int WROWS = BM / Cf::WM, WCOLS = BN / Cf::WN;
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -530,6 +550,7 @@ __global__ __launch_bounds__(Cf::kThreads, PL<Cf>::kMinWaves) void conv1x1p_kern
   };
 
   float* const ctab = reinterpret_cast<float*>(lds + L::kLds);
+  float* const atab = ctab + (ATR ? 2 * K : 0);  // APPLY's [4][BN] table (a, b, ra, rb), past ATR's
   if constexpr (ATR) {
     for (int i = tid; i < 2 * K; i += Cf::kThreads) ctab[i] = acoef[i];
     __syncthreads();  // (no DMA issued yet: a plain barrier)
@@ -539,8 +560,10 @@ __global__ __launch_bounds__(Cf::kThreads, PL<Cf>::kMinWaves) void conv1x1p_kern
   constexpr int kRowStep = Cf::kThreads / kChunks, kIt = BM / kRowStep;
   constexpr int kItH = kIt / kHalves;
   // rows per batch of loads (registers: 128 per lane at 16 waves, 256 below)
-  constexpr int kB = (ACC && BSTATS) ? (Cf::kWaves >= 16 ? 2 : (kItH >= 8 ? kItH / 2 : kItH)) : kItH;
-  constexpr int kStores = kIt * (APPLY ? 2 : 1);  // row stores per thread per tile (exact)
+  constexpr int kB = (ACC && BSTATS) ? (Cf::kWaves >= 16 ? 2 : (kItH >= 8 ? kItH / 2 : kItH))
+                     : (APPLY && kItH > 2) ? 2 : kItH;
+  // row stores per thread per tile (exact); the statistics-only kernel has none
+  constexpr int kStores = NOST ? 0 : kIt * (APPLY ? 2 : 1);
   static_assert(kRowStep * kIt == BM && kIt % kHalves == 0 && kItH % kB == 0, "epilogue rows");
   const int r0 = tid / kChunks, c = tid % kChunks;
   const uint8_t* const cm_base = Cmask ? Cmask : g_mask_ones;
@@ -553,6 +576,7 @@ __global__ __launch_bounds__(Cf::kThreads, PL<Cf>::kMinWaves) void conv1x1p_kern
   const int64_t bx_scale = bs.x ? 1 : 0;
 
   int mt = tile / ntn, n0 = (tile % ntn) * BN, m0 = mt * BM;
+  int tab_n0 = -1;  // APPLY: the column block whose coefficients atab holds
 #pragma unroll
   for (int i = 0; i < Cf::kALd; ++i) aoff[i] = aoff_of(m0, i);
 #pragma unroll
@@ -643,14 +667,17 @@ __global__ __launch_bounds__(Cf::kThreads, PL<Cf>::kMinWaves) void conv1x1p_kern
     RowStats8 rst;
     float kst = 0.f;
     float bs1[8], bs2[8], bmu[8];
-    float pa[8], pb[8], pra[8], prb[8];
     if constexpr (APPLY) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        pa[k] = ap.ab[cur_n0 + c * 8 + k];
-        pb[k] = ap.ab[N + cur_n0 + c * 8 + k];
-        pra[k] = ap.rab ? ap.rab[cur_n0 + c * 8 + k] : 1.f;
-        prb[k] = ap.rab ? ap.rab[N + cur_n0 + c * 8 + k] : 0.f;
+      // (workgroup-uniform; the last reads of the old table were before the previous tile's last barrier, the
+      // first reads of the new one come after this tile's first staging barrier)
+      if (cur_n0 != tab_n0) {
+        if (tid < BN) {
+          atab[tid] = ap.ab[cur_n0 + tid];
+          atab[BN + tid] = ap.ab[N + cur_n0 + tid];
+          atab[2 * BN + tid] = ap.rab ? ap.rab[cur_n0 + tid] : 1.f;
+          atab[3 * BN + tid] = ap.rab ? ap.rab[N + cur_n0 + tid] : 0.f;
+        }
+        tab_n0 = cur_n0;
       }
     }
     if constexpr (BSTATS) {
@@ -737,25 +764,31 @@ __global__ __launch_bounds__(Cf::kThreads, PL<Cf>::kMinWaves) void conv1x1p_kern
             v.w = (uint32_t)f2bf(a8[6]) | ((uint32_t)f2bf(a8[7]) << 16);
           }
           unsigned amb = 0;
-          if constexpr (APPLY) {
-            float z[8], rr[8];
+          if constexpr (APPLY) {  // (the same fp32 operations as the one-tile kernel's, four channels at a time)
             const uint32_t w[4] = {v.x, v.y, v.z, v.w}, rw[4] = {cv[it].x, cv[it].y, cv[it].z, cv[it].w};
+            uint32_t o[4];
+            asm volatile("" ::: "memory");  // the coefficients are re-read per row, never carried across rows
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-              z[2 * k] = __uint_as_float(w[k] << 16); z[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-              rr[2 * k] = __uint_as_float(rw[k] << 16); rr[2 * k + 1] = __uint_as_float(rw[k] & 0xffff0000u);
-            }
+            for (int q = 0; q < 2; ++q) {
+              float fa[4], fb[4], fra[4], frb[4], z[4];
+              *reinterpret_cast<float4*>(fa) = *reinterpret_cast<const float4*>(atab + c * 8 + 4 * q);
+              *reinterpret_cast<float4*>(fb) = *reinterpret_cast<const float4*>(atab + BN + c * 8 + 4 * q);
+              *reinterpret_cast<float4*>(fra) = *reinterpret_cast<const float4*>(atab + 2 * BN + c * 8 + 4 * q);
+              *reinterpret_cast<float4*>(frb) = *reinterpret_cast<const float4*>(atab + 3 * BN + c * 8 + 4 * q);
 #pragma unroll
-            for (int k = 0; k < 8; ++k) {
-              float t = z[k] * pa[k] + pb[k];
-              t += ap.rab ? rr[k] * pra[k] + prb[k] : rr[k];
-              amb |= (t > 0.f ? 1u : 0u) << k;
-              z[k] = t > 0.f ? t : 0.f;
+              for (int k = 0; k < 4; ++k) {
+                const uint32_t wz = w[2 * q + (k >> 1)], wr = rw[2 * q + (k >> 1)];
+                const float zf = __uint_as_float(k & 1 ? wz & 0xffff0000u : wz << 16);
+                const float rf = __uint_as_float(k & 1 ? wr & 0xffff0000u : wr << 16);
+                float t = zf * fa[k] + fb[k];
+                t += ap.rab ? rf * fra[k] + frb[k] : rf;
+                amb |= (t > 0.f ? 1u : 0u) << (4 * q + k);
+                z[k] = t > 0.f ? t : 0.f;
+              }
+              o[2 * q] = (uint32_t)f2bf(z[0]) | ((uint32_t)f2bf(z[1]) << 16);
+              o[2 * q + 1] = (uint32_t)f2bf(z[2]) | ((uint32_t)f2bf(z[3]) << 16);
             }
-            v.x = (uint32_t)f2bf(z[0]) | ((uint32_t)f2bf(z[1]) << 16);
-            v.y = (uint32_t)f2bf(z[2]) | ((uint32_t)f2bf(z[3]) << 16);
-            v.z = (uint32_t)f2bf(z[4]) | ((uint32_t)f2bf(z[5]) << 16);
-            v.w = (uint32_t)f2bf(z[6]) | ((uint32_t)f2bf(z[7]) << 16);
+            v = make_uint4(o[0], o[1], o[2], o[3]);
           }
           if constexpr (BSTATS) {
             bn_bwd_accum8(v, xbv[it], bmkv[it], bmu, bs1, bs2);
@@ -764,9 +797,12 @@ __global__ __launch_bounds__(Cf::kThreads, PL<Cf>::kMinWaves) void conv1x1p_kern
           if constexpr (STATS) {
             if (ok) rs8_add(rst, v);
           }
-          // every thread stores every row (past M: the sink) so the vmcnt counts above are exact
-          uint4* yp = ok && !ap.nostore ? reinterpret_cast<uint4*>(Y + off) : g_gemm_sink + tid;
-          *yp = v;
+          // every thread stores every row (past M: the sink) so the vmcnt counts above are exact; the
+          // statistics-only kernel stores nothing (kStores = 0)
+          if constexpr (!NOST) {
+            uint4* yp = ok ? reinterpret_cast<uint4*>(Y + off) : g_gemm_sink + tid;
+            *yp = v;
+          }
           if constexpr (APPLY) {
             uint8_t* mp = ok ? ap.mask + (off >> 3) : g_mask_sink + tid;
             *mp = (uint8_t)amb;
@@ -797,8 +833,10 @@ __global__ __launch_bounds__(Cf::kThreads, PL<Cf>::kMinWaves) void conv1x1p_kern
 // 256-channel tile of the plain / statistics forward and of the data gradient without an accumulate source
 // (ResNet-50, 1024 images, tools/conv1x1_persist_bench.py, profiles/r5/conv1x1_persist_bench_b1024.txt:
 // forward + statistics 64->256 @56 526 -> 430 us, data gradient + BN reduction 64->256 @56 774 -> 725,
-// @28 458 -> 401, @14 290 -> 267); the ATR, APPLY and accumulate epilogues hold more registers and spill
-// at 128 per lane, and the 8- / 4-wave persistent tiles were slower: there the one-tile kernel stays;
+// @28 458 -> 401, @14 290 -> 267), and the APPLY epilogue on the 8-wave tile staged in four parts (two workgroups
+// per CU, coefficients in LDS: profiles/r7/conv1x1_probe_b1024.txt); the ATR and accumulate epilogues hold more
+// registers and spill at 128 per lane, and the other 8- / 4-wave persistent tiles were slower: there the one-tile
+// kernel stays;
 // 2: every kind and tile persistent (A/B). -1: PDT_CONV1X1_PERSIST, read once.
 int g_persist = -1;
 
@@ -811,39 +849,49 @@ inline int persist_mode() {
   return g_persist;
 }
 
-template <class Cf, bool ACC, bool STATS, bool BSTATS, bool ATR, bool APPLY, bool STR>
+// Which persistent kernel ran last (pdt_conv1x1_last_persistent: tests assert the path, not only the result):
+// 0 = the last GEMM launch was a one-tile kernel, else waves per workgroup | 256 statistics-only | 512 APPLY
+int g_last_persistent = 0;
+
+template <class Cf, bool ACC, bool STATS, bool BSTATS, bool ATR, bool APPLY, bool STR, bool NOST = false, int HV = 0>
 int launch_p(const uint16_t* a, const uint16_t* b, uint16_t* y, const uint16_t* c, const uint8_t* cm, float* part, int M,
              int K, int N, const BnSrc& bs, const CGeom& cg, hipStream_t s, const float* acoef, const ApArgs& ap) {
-  using L = PL<Cf>;
+  using L = PL<Cf, HV>;
   static bool attr = false;
-  constexpr int kMaxLds = L::kLds + (ATR ? 2 * 512 * 4 : 0);
+  constexpr int kTab = APPLY ? 4 * Cf::BN * 4 : 0;  // APPLY's coefficient table
+  constexpr int kMaxLds = L::kLds + (ATR ? 2 * 512 * 4 : 0) + kTab;
+  static_assert(kMaxLds <= 160 * 1024, "LDS");
   if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1x1p_kernel<Cf, ACC, STATS, BSTATS, ATR, APPLY, STR>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess)
+    if (hipFuncSetAttribute(
+            reinterpret_cast<const void*>(&conv1x1p_kernel<Cf, ACC, STATS, BSTATS, ATR, APPLY, STR, NOST, HV>),
+            hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess)
       return -3;
     attr = true;
   }
-  const int lds = L::kLds + (ATR ? 2 * K * 4 : 0);
+  const int lds = L::kLds + (ATR ? 2 * K * 4 : 0) + kTab;
   const int64_t total = (int64_t)(M + Cf::BM - 1) / Cf::BM * (N / Cf::BN);
   const int occ = (160 * 1024) / lds > 0 ? (160 * 1024) / lds : 1;
   int64_t grid = 256 * (int64_t)occ;
   if (grid > total) grid = total;
-  hipLaunchKernelGGL((conv1x1p_kernel<Cf, ACC, STATS, BSTATS, ATR, APPLY, STR>), dim3((unsigned)grid),
+  hipLaunchKernelGGL((conv1x1p_kernel<Cf, ACC, STATS, BSTATS, ATR, APPLY, STR, NOST, HV>), dim3((unsigned)grid),
                      dim3(Cf::kThreads), lds, s, a, b, y, c, cm, part, M, K, N, bs, cg, acoef, ap);
+  g_last_persistent = Cf::kWaves | (NOST ? 256 : 0) | (APPLY ? 512 : 0);
   return 0;
 }
 
 constexpr int kMaxATRK = 512;  // ATR coefficient table: [2][K] floats past kLds
 
-template <class Cf, bool ACC, bool STATS, bool NT, bool BSTATS, bool ATR = false, bool APPLY = false, bool STR = false>
+template <class Cf, bool ACC, bool STATS, bool NT, bool BSTATS, bool ATR = false, bool APPLY = false, bool STR = false,
+          bool NOST = false>
 int launch_nt(const uint16_t* a, const uint16_t* b, uint16_t* y, const uint16_t* c, const uint8_t* cm, float* part,
               int M, int K, int N, const BnSrc& bs, const CGeom& cg, hipStream_t s, const float* acoef = nullptr,
               const ApArgs& ap = ApArgs{}) {
   static bool attr = false;
   constexpr int kMaxLds = Cf::kLds + (ATR ? 2 * kMaxATRK * 4 : 0);
   if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1x1_kernel<Cf, ACC, STATS, NT, BSTATS, ATR, APPLY, STR>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess)
+    if (hipFuncSetAttribute(
+            reinterpret_cast<const void*>(&conv1x1_kernel<Cf, ACC, STATS, NT, BSTATS, ATR, APPLY, STR, NOST>),
+            hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess)
       return -3;
     attr = true;
   }
@@ -854,14 +902,19 @@ int launch_nt(const uint16_t* a, const uint16_t* b, uint16_t* y, const uint16_t*
   apx.probe = g_probe;
   // persistent: from two tiles per workgroup up (probes run on the one-tile kernel)
   if constexpr (!NT) {
-    constexpr bool kMeasured = Cf::kWaves >= 16 && !ACC && !ATR && !APPLY;  // see g_persist
+    // APPLY on the 8-wave tile: staged in four parts, two workgroups per CU (see PL)
+    // (not with ATR: its operand transform and APPLY together spill at 128 registers per lane)
+    constexpr int kHV = (APPLY && !ATR && Cf::kWaves == 8 && Cf::WM == 4) ? 4 : 0;
+    constexpr bool kMeasured = (Cf::kWaves >= 16 && !ACC && !ATR && !APPLY) || (APPLY && !ATR && kHV == 4);  // see g_persist
     const int pm = persist_mode();
     if ((pm == 2 || (pm == 1 && kMeasured)) && g_probe == 0 && !ap.a2 &&
-        grid >= 2 * 256 * (int64_t)((160 * 1024) / PL<Cf>::kLds))
-      return launch_p<Cf, ACC, STATS, BSTATS, ATR, APPLY, STR>(a, b, y, c, cm, part, M, K, N, bs, cg, s, acoef, apx);
+        grid >= 2 * 256 * (int64_t)((160 * 1024) / PL<Cf, kHV>::kLds))
+      return launch_p<Cf, ACC, STATS, BSTATS, ATR, APPLY, STR, NOST, kHV>(a, b, y, c, cm, part, M, K, N, bs, cg, s, acoef,
+                                                                          apx);
   }
-  hipLaunchKernelGGL((conv1x1_kernel<Cf, ACC, STATS, NT, BSTATS, ATR, APPLY, STR>), dim3((unsigned)grid),
+  hipLaunchKernelGGL((conv1x1_kernel<Cf, ACC, STATS, NT, BSTATS, ATR, APPLY, STR, NOST>), dim3((unsigned)grid),
                      dim3(Cf::kThreads), lds, s, a, b, y, c, cm, part, M, K, N, bs, cg, acoef, apx);
+  g_last_persistent = 0;
   return 0;
 }
 
@@ -871,6 +924,10 @@ int launch(const uint16_t* a, const uint16_t* b, uint16_t* y, const uint16_t* c,
   if constexpr (ACC)
     if (cg.s) return launch_nt<Cf, ACC, STATS, false, BSTATS, false, false, true>(a, b, y, c, cm, part, M, K, N, bs, cg, s,
                                                                                   nullptr, ap);
+  if constexpr (STATS && !ACC && !BSTATS)  // the statistics-only forward: same tile and kernel kind as the storing one
+    if (ap.nostore)
+      return launch_nt<Cf, false, true, false, false, false, false, false, true>(a, b, y, c, cm, part, M, K, N, bs, cg, s,
+                                                                                 nullptr, ap);
   // (non-temporal output stores, NT = true, measured no gain: default-policy stores keep the
   // output in L2 for the consuming BatchNorm)
   return launch_nt<Cf, ACC, STATS, false, BSTATS>(a, b, y, c, cm, part, M, K, N, bs, cg, s, nullptr, ap);
@@ -926,6 +983,10 @@ int pdt_conv1x1_persist(int mode) {
   g_persist = mode < 0 ? -1 : (mode > 2 ? 2 : mode);
   return old;
 }
+
+// Which kernel the last pdt_conv1x1_gemm* call launched: 0 = one tile per workgroup, else the persistent kernel's
+// waves per workgroup (4 / 8 / 16), + 256 for the statistics-only variant, + 512 for APPLY (see g_last_persistent).
+int pdt_conv1x1_last_persistent() { return g_last_persistent; }
 
 // y[M,N] = a[M,K] * b[N,K]^T (+ c[M,N], masked by the bit-mask cm when given: bit j of byte
 // (m*N + n) / 8 — the BatchNorm ReLU mask layout); part: stats of y per 256-row tile (see above),
@@ -1014,7 +1075,14 @@ int pdt_conv1x1_gemm_apply(const uint16_t* a, const uint16_t* b, uint16_t* y, co
   const CGeom cg{0, 1, 1, 1, 1};
   const ApArgs ap{ab, rab, mask};
   // (APPLY on the 8-wave tile at every size: 892 vs 943 us at 64->256 @56, 505 vs 540 @28, 307 vs 333 @14 on
-  // the 16-wave one, profiles/r5/conv1x1_tiles_bench_b1024.txt)
+  // the 16-wave one, profiles/r5/conv1x1_tiles_bench_b1024.txt. PDT_APPLY_TILE=1, A/B: the 16-wave tile where the
+  // plain forward takes it — persistent only with PDT_CONV1X1_PERSIST=2)
+  static const int apply_tile = [] {
+    const char* e = getenv("PDT_APPLY_TILE");
+    return (e && e[0]) ? (int)strtol(e, nullptr, 10) : 0;
+  }();
+  if (apply_tile == 1 && N % 256 == 0 && !acoef && (int64_t)((M + 255) / 256) * (N / 256) >= 2048 && !(g_probe & 64))
+    return launch_nt<GXWide, false, false, false, false, false, true>(a, b, y, res, nullptr, nullptr, M, K, N, bs, cg, s, acoef, ap);
   if (N % 128 == 0 && !(g_probe & 8)) {
     if (acoef) return launch_nt<GWide, false, false, false, false, true, true>(a, b, y, res, nullptr, nullptr, M, K, N, bs, cg, s, acoef, ap);
     return launch_nt<GWide, false, false, false, false, false, true>(a, b, y, res, nullptr, nullptr, M, K, N, bs, cg, s, acoef, ap);

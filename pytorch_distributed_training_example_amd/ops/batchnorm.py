@@ -222,6 +222,8 @@ class _BNTrainFn(torch.autograd.Function):
                                                           momentum, eps, False, apply=False)
             a2, w2 = gemm.operands()
             y, mask = C.conv1x1_gemm_apply(a2, w2, residual, ab, res_ab, gemm.acoef)
+            if sub:  # the APPLY epilogue writes no subsample: the gather kernel right behind it (subsample.hip)
+                sub.append(C.subsample_gather(y, sub[0]))
         elif part is not None:  # statistics from the producing conv's epilogue: no reduce pass over x
             r = C.bn_fwd_train_tiles(x, part, residual, weight, bias, running_mean, running_var, momentum, eps, relu,
                                      res_ab=res_ab, sub=sub[0] if sub else 0) if sub else ()

@@ -1115,8 +1115,10 @@ class Conv1x1(nn.Conv2d):
             # a bottleneck conv3 on the ALG backward (PDT_BWD_ALG=2): its output z is needed only for the consuming
             # BatchNorm's statistics (this GEMM's epilogue) and its apply, which runs as this GEMM again (APPLY
             # epilogue) — so z is never written (PDT_Z3_VIRTUAL; materialize_virtual recomputes it on a fallback)
+            # (not a conv with a res_link — a downsample block's shortcut conv on the ALG backward: its BatchNorm is
+            # statistics-only, never the APPLY GEMM, and would recompute z at once)
             virt = (holder is not None and bwd_link is not None and bwd_link.needs_masked and SW.bwd_alg >= 2
-                    and x.dtype == torch.bfloat16
+                    and x.dtype == torch.bfloat16 and res_link is None
                     and (SW.z3_virtual == 1 or (SW.z3_virtual == 2 and 0 < self.in_channels <= SW.bn_apply_gemm_k)))
             y = _Conv1x1Fn.apply(x, self.weight, res_link, holder,
                                  grad_stats_source_of(x) if self.training and torch.is_grad_enabled() else None,

@@ -51,6 +51,9 @@ def main():
         bmean = torch.randn(ci, device="cuda")
         cases = [
             (f"fwd+stats {ci}->{co} @{h}", lambda: C.conv1x1_gemm(x, w, y, False, True), (M * ci + M * co) * 2),
+            # the statistics-only forward (y never written): plain timing, column 0 is the number that counts
+            (f"fwd stats-only {ci}->{co} @{h}", lambda: C.conv1x1_gemm(x, w, y, False, True, no_store=True),
+             M * ci * 2),
             (f"apply {ci}->{co} @{h}", lambda: C.conv1x1_gemm_apply(x, w, res, ab), (M * ci + 2 * M * co + M * co // 8) * 2),
             (f"dgrad+acc+bst {co}->{ci} @{h}",
              lambda: C.conv1x1_gemm(gy, wt, dres, True, False, None, None, bx, None, bmean),
