@@ -79,6 +79,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--sync-bn", action="store_true",
                    help="BatchNorm statistics over all ranks (convert_sync_batchnorm before the DDP wrap); "
                         "not with --hipgraph on more than one rank")
+    p.add_argument("--dropout", type=float, default=0.0, metavar="P",
+                   help="dropout probability for the models that have dropout sites (gpt2_*, vit_*): embedding, "
+                        "attention and residual dropout from counter-generated masks, seeded from --seed and the rank")
     p.add_argument("--profile", default=None, metavar="DIR",
                    help="torch.profiler trace of a few steps of epoch 1 into DIR (rank 0), roctx ranges on")
     return p
@@ -153,8 +156,13 @@ def run(rank: int, world: int, args) -> dict:
             # logits by one fused kernel: identical values, no separate softmax round trip
             loss_kind = "prob_nll"
         model = get_model("lenet", output="logits")
+    elif args.dropout > 0:
+        model = get_model(args.model, dropout=args.dropout)
     else:
         model = get_model(args.model)
+    # dropout masks: one seed for the job, the rank enters the Philox key (ops/dropout.py)
+    from .ops.dropout import manual_seed as dropout_seed
+    dropout_seed(args.seed, rank)
     model = model.to(device)
     if args.channels_last:
         model = model.to(memory_format=torch.channels_last)
@@ -204,7 +212,8 @@ def run(rank: int, world: int, args) -> dict:
         from .data import SyntheticBatches
         steps = args.steps_per_epoch or 10
         if args.model.startswith("gpt"):
-            train_loader = SyntheticBatches((per_rank, args.seq_len), 50257, steps, device, seed=args.seed + rank,
+            vocab = min(50257, model.cfg.vocab_size)  # gpt2_tiny's vocabulary is smaller than GPT-2's
+            train_loader = SyntheticBatches((per_rank, args.seq_len), vocab, steps, device, seed=args.seed + rank,
                                             int_inputs=True)
         else:
             train_loader = SyntheticBatches((per_rank, 3, args.image_size, args.image_size), 1000, steps, device,
@@ -283,6 +292,15 @@ def _entry(rank: int, world: int, args) -> None:
     run(rank, world, args)
 
 
+def has_dropout_sites(model_name: str) -> bool:
+    return model_name.startswith(("gpt2", "vit"))
+
+
+def dropout_unsupported_msg(model_name: str) -> str:
+    return (f"--dropout: model {model_name} has no dropout sites (only the transformer models gpt2_* and vit_* "
+            "take --dropout); drop the flag or choose one of them")
+
+
 SYNC_BN_HIPGRAPH_MSG = ("--sync-bn cannot be combined with --hipgraph on more than one rank: the SyncBatchNorm "
                         "statistics exchange is a collective that hipGraph capture does not support yet")
 
@@ -301,6 +319,10 @@ def main(argv: Optional[list] = None) -> int:
         args.precision = {"off": "fp32", "bf16": "bf16", "fp8": "fp8"}[args.amp]
     if args.sync_bn and args.hipgraph and _planned_world(args, not args.no_cuda and torch.cuda.is_available()) > 1:
         raise SystemExit(SYNC_BN_HIPGRAPH_MSG)
+    if not 0.0 <= args.dropout < 1.0:
+        raise SystemExit(f"--dropout must be in [0, 1), got {args.dropout}")
+    if args.dropout > 0 and not has_dropout_sites(args.model):
+        raise SystemExit(dropout_unsupported_msg(args.model))
     if args.hipgraph:
         # MIOpen reads its solver switches once per process: set before any convolution
         from .engine.graph import make_miopen_capture_safe

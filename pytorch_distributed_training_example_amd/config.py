@@ -98,6 +98,9 @@ PDT_FP8_LN                  1            fp8: the add+LayerNorm in front of qkv 
                                          transpose for that GEMM (layernorm.hip ln_fwd_fp8_kernel): no bf16 y
 PDT_WGRAD_STREAM_M          0            conv weight gradients with <= this many output pixels run on a side
                                          stream, concurrent with their data gradient (0 = in-stream)
+PDT_DROPOUT_FUSED           1            GPT-2 / ViT dropout from counter-generated masks inside our kernels
+                                         (ops/dropout.py); 0: the same sites from F.dropout and SDPA's dropout
+                                         (what a user would otherwise write; A/B and escape hatch)
 """
 from __future__ import annotations
 
@@ -110,7 +113,8 @@ class _Switches:
                  "conv_bn_stats", "bn_bwd_stats", "res_masked", "stem_bwd_fused", "stem_bn_wgrad", "stem_bn_stats", "stem_pool_wgrad", "wgrad_splitk", "slice_sum",
                  "subsample_native", "linear_splitk", "fused_addln", "embedding_native", "linear_epilogue",
                  "bwd_fused", "bwd_fused_shapes", "bwd_alg", "alg_glo", "bwd_alg_min_m", "z3_virtual", "bwd_alg_first", "ds_alg", "bn2_defer", "bn_apply_gemm_k", "strided_bstats", "gap_native", "sub_out",
-                 "fp8_fused_gelu", "fp8_weight_multi", "fp8_cast_colsum", "fp8_ln", "wgrad_stream_m")
+                 "fp8_fused_gelu", "fp8_weight_multi", "fp8_cast_colsum", "fp8_ln", "wgrad_stream_m",
+                 "dropout_fused")
 
     def __init__(self):
         self.reload()
@@ -180,6 +184,7 @@ class _Switches:
         # conv weight gradients of at most this many output pixels run on a side stream, concurrent
         # with their data gradient (0 = off): small-batch grids leave CUs idle (ops/conv.py _WgradFork)
         self.wgrad_stream_m = int(e("PDT_WGRAD_STREAM_M", "0"))
+        self.dropout_fused = on("PDT_DROPOUT_FUSED")
         return self
 
 

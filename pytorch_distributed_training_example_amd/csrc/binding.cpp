@@ -100,6 +100,26 @@ int pdt_attn_bwd(const uint16_t* dout, const int64_t* dos, const uint16_t* q, co
                  const int64_t* ks, const uint16_t* v, const int64_t* vs, const uint16_t* o, const int64_t* os,
                  const float* lse, float* delta, uint16_t* dq, uint16_t* dk, uint16_t* dv, const int64_t* gs, int B,
                  int H, int T, int Dh, int causal, float scale, hipStream_t s);
+int pdt_dropout_begin(int64_t* state, int64_t* ticket, hipStream_t s);
+int pdt_dropout(const void* x, void* y, int dtype, int64_t n, const int64_t* ticket, int stream, int thr,
+                hipStream_t s);
+int pdt_dropout_mask_flat(uint8_t* out, int64_t n, const int64_t* ticket, int stream, int thr, hipStream_t s);
+int pdt_dropout_mask_attn(uint8_t* out, int64_t BH, int T, const int64_t* ticket, int stream, int thr,
+                          hipStream_t s);
+int pdt_ln_fwd_drop(const void* x, const void* res, int dtype, const float* w, const float* b, void* y,
+                    void* sum_out, float* mean, float* rstd, int64_t N, int D, float eps, const int64_t* ticket,
+                    int dstream, int thr, hipStream_t s);
+int pdt_ln_bwd_drop(const void* dy, const void* x, const void* dres, int dtype, const float* w, const float* mean,
+                    const float* rstd, void* dx, void* dh, float* dw, float* db, int64_t N, int D, float* ws,
+                    const int64_t* ticket, int dstream, int thr, hipStream_t s);
+int pdt_attn_fwd_drop(const uint16_t* q, const int64_t* qs, const uint16_t* k, const int64_t* ks, const uint16_t* v,
+                      const int64_t* vs, uint16_t* o, const int64_t* os, float* lse, int B, int H, int T, int Dh,
+                      int causal, float scale, const int64_t* ticket, int dstream, int thr, hipStream_t s);
+int pdt_attn_bwd_drop(const uint16_t* dout, const int64_t* dos, const uint16_t* q, const int64_t* qs,
+                      const uint16_t* k, const int64_t* ks, const uint16_t* v, const int64_t* vs, const uint16_t* o,
+                      const int64_t* os, const float* lse, float* delta, uint16_t* dq, uint16_t* dk, uint16_t* dv,
+                      const int64_t* gs, int B, int H, int T, int Dh, int causal, float scale, const int64_t* ticket,
+                      int dstream, int thr, hipStream_t s);
 int64_t pdt_gelu_workspace_floats(int64_t N, int D);
 int pdt_bias_gelu_fwd(const void* x, int dtype, const void* bias, void* y, int64_t N, int D, int tanh_form,
                       hipStream_t s, int bias_bf16);
@@ -1946,6 +1966,97 @@ std::vector<Tensor> ln_bwd(Tensor dy, Tensor x, Tensor w, Tensor mean, Tensor rs
   return {dx, dw, db};
 }
 
+// ----------------------------------------------------------------------------- dropout (philox.h)
+const int64_t* ticket_ptr(const Tensor& ticket, const Tensor& like) {
+  TORCH_CHECK(ticket.is_cuda() && ticket.scalar_type() == at::kLong && ticket.numel() == 2 && ticket.is_contiguous() &&
+              ticket.device() == like.device(), "dropout: ticket must be an int64 [2] tensor on the data's device");
+  return ticket.data_ptr<int64_t>();
+}
+int check_thr(int64_t thr) {
+  TORCH_CHECK(thr >= 1 && thr <= 255, "dropout: threshold ", thr, " outside 1..255");
+  return (int)thr;
+}
+
+// state = (key, step) -> a fresh ticket (key, step); step += 1. One launch, no host read: captured in a
+// hipGraph, every replay advances.
+Tensor dropout_begin(Tensor state) {
+  TORCH_CHECK(state.is_cuda() && state.scalar_type() == at::kLong && state.numel() == 2 && state.is_contiguous(),
+              "dropout: state must be an int64 [2] GPU tensor (key, step)");
+  auto ticket = at::empty({2}, state.options());
+  pdt_dropout_begin(state.data_ptr<int64_t>(), ticket.data_ptr<int64_t>(), stream());
+  return ticket;
+}
+
+// y = round_T(x * m * scale), flat mask layout; the backward is the same call on dy.
+Tensor dropout_fwd(Tensor x, Tensor ticket, int64_t dstream, int64_t thr) {
+  check_cuda(x, "x");
+  TORCH_CHECK(x.is_contiguous() && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "dropout: x must be contiguous and 16-byte aligned");
+  auto y = at::empty_like(x);
+  int rc = pdt_dropout(x.data_ptr(), y.data_ptr(), dcode(x), x.numel(), ticket_ptr(ticket, x), (int)dstream,
+                       check_thr(thr), stream());
+  TORCH_CHECK(rc == 0, "pdt_dropout failed: ", rc);
+  return y;
+}
+
+// The bool keep mask the kernels apply: kind "flat" (any shape, element order) or "attn" ([B, H, T, T]).
+Tensor dropout_mask(Tensor ticket, int64_t dstream, std::vector<int64_t> shape, int64_t thr, std::string kind) {
+  TORCH_CHECK(thr >= 0 && thr <= 255, "dropout: threshold ", thr, " outside 0..255");
+  auto out = at::empty(shape, ticket.options().dtype(at::kBool));
+  const int64_t* tp = ticket_ptr(ticket, out);
+  int rc;
+  if (kind == "flat") {
+    rc = pdt_dropout_mask_flat(reinterpret_cast<uint8_t*>(out.data_ptr()), out.numel(), tp, (int)dstream, (int)thr,
+                               stream());
+  } else {
+    TORCH_CHECK(kind == "attn" && shape.size() == 4 && shape[2] == shape[3], "dropout_mask: attn wants [B, H, T, T]");
+    rc = pdt_dropout_mask_attn(reinterpret_cast<uint8_t*>(out.data_ptr()), shape[0] * shape[1], (int)shape[2], tp,
+                               (int)dstream, (int)thr, stream());
+  }
+  TORCH_CHECK(rc == 0, "pdt_dropout_mask failed: ", rc);
+  return out;
+}
+
+// s = x + dropout(res), y = LN(s): {y, mean, rstd, s}
+std::vector<Tensor> ln_fwd_drop(Tensor x, Tensor w, Tensor b, double eps, Tensor res, Tensor ticket, int64_t dstream,
+                                int64_t thr) {
+  check_cuda(x, "x");
+  TORCH_CHECK(x.is_contiguous(), "ln: x must be contiguous");
+  const int64_t D = x.size(-1), N = x.numel() / D;
+  TORCH_CHECK(w.scalar_type() == at::kFloat && b.scalar_type() == at::kFloat, "ln: weight/bias must be fp32");
+  TORCH_CHECK(res.is_contiguous() && res.sizes() == x.sizes() && res.scalar_type() == x.scalar_type(),
+              "ln: residual must match x (contiguous, same shape/dtype)");
+  auto y = at::empty_like(x), sum = at::empty_like(x);
+  auto fopt = x.options().dtype(at::kFloat);
+  auto mean = at::empty({N}, fopt), rstd = at::empty({N}, fopt);
+  int rc = pdt_ln_fwd_drop(x.data_ptr(), res.data_ptr(), dcode(x), w.data_ptr<float>(), b.data_ptr<float>(),
+                           y.data_ptr(), sum.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(), N, (int)D,
+                           (float)eps, ticket_ptr(ticket, x), (int)dstream, check_thr(thr), stream());
+  TORCH_CHECK(rc == 0, "pdt_ln_fwd_drop: unsupported D=", D);
+  return {y, mean, rstd, sum};
+}
+
+// {dx, dh, dw, db}: dx as ln_bwd, dh = the dropout backward of dx (the dropped branch's gradient)
+std::vector<Tensor> ln_bwd_drop(Tensor dy, Tensor x, Tensor w, Tensor mean, Tensor rstd, c10::optional<Tensor> dres,
+                                Tensor ticket, int64_t dstream, int64_t thr) {
+  TORCH_CHECK(dy.is_contiguous() && x.is_contiguous(), "ln bwd: contiguous inputs required");
+  const int64_t D = x.size(-1), N = x.numel() / D;
+  const bool hr = dres.has_value() && dres->defined();
+  if (hr)
+    TORCH_CHECK(dres->is_contiguous() && dres->sizes() == x.sizes() && dres->scalar_type() == x.scalar_type(),
+                "ln bwd: dres must match x (contiguous, same shape/dtype)");
+  auto dx = at::empty_like(x), dh = at::empty_like(x);
+  auto fopt = x.options().dtype(at::kFloat);
+  auto dw = at::empty({D}, fopt), db = at::empty({D}, fopt);
+  auto ws = at::empty({std::max<int64_t>(pdt_ln_workspace_floats(N, (int)D), 1)}, fopt);
+  int rc = pdt_ln_bwd_drop(dy.data_ptr(), x.data_ptr(), hr ? dres->data_ptr() : nullptr, dcode(x),
+                           w.data_ptr<float>(), mean.data_ptr<float>(), rstd.data_ptr<float>(), dx.data_ptr(),
+                           dh.data_ptr(), dw.data_ptr<float>(), db.data_ptr<float>(), N, (int)D, ws.data_ptr<float>(),
+                           ticket_ptr(ticket, x), (int)dstream, check_thr(thr), stream());
+  TORCH_CHECK(rc == 0, "pdt_ln_bwd_drop: unsupported D=", D);
+  return {dx, dh, dw, db};
+}
+
 // ----------------------------------------------------------------------------- bias + gelu
 Tensor bias_gelu_fwd(Tensor x, c10::optional<Tensor> bias, bool tanh_form) {
   TORCH_CHECK(x.is_contiguous(), "gelu: x must be contiguous");
@@ -2026,6 +2137,46 @@ void attn_bwd_out(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor ls
                         reinterpret_cast<uint16_t*>(dk.data_ptr()), reinterpret_cast<uint16_t*>(dv.data_ptr()), gs.v, B,
                         H, T, Dh, causal, (float)scale, stream());
   TORCH_CHECK(rc == 0, "pdt_attn_bwd: unsupported head dim ", Dh);
+}
+
+// Attention dropout: the same calls with the mask of P regenerated from the ticket (attention.hip DROP).
+void attn_fwd_drop_out(Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal, double scale, Tensor ticket,
+                       int64_t dstream, int64_t thr) {
+  auto qs = bht_strides(q, "q"), ks = bht_strides(k, "k"), vs = bht_strides(v, "v"), os = bht_strides(o, "o");
+  TORCH_CHECK(q.sizes() == k.sizes() && q.sizes() == v.sizes() && q.sizes() == o.sizes(), "attn: shape mismatch");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() && lse.numel() == q.size(0) * q.size(1) * q.size(2),
+              "attn: lse must be fp32 [B,H,T]");
+  const int B = q.size(0), H = q.size(1), T = q.size(2), Dh = q.size(3);
+  int rc = pdt_attn_fwd_drop(reinterpret_cast<const uint16_t*>(q.data_ptr()), qs.v,
+                             reinterpret_cast<const uint16_t*>(k.data_ptr()), ks.v,
+                             reinterpret_cast<const uint16_t*>(v.data_ptr()), vs.v,
+                             reinterpret_cast<uint16_t*>(o.data_ptr()), os.v, lse.data_ptr<float>(), B, H, T, Dh, causal,
+                             (float)scale, ticket_ptr(ticket, q), (int)dstream, check_thr(thr), stream());
+  TORCH_CHECK(rc == 0, "pdt_attn_fwd_drop: unsupported head dim ", Dh);
+}
+
+void attn_bwd_drop_out(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor dq, Tensor dk, Tensor dv,
+                       bool causal, double scale, Tensor ticket, int64_t dstream, int64_t thr) {
+  auto dos = bht_strides(dout, "dout"), qs = bht_strides(q, "q"), ks = bht_strides(k, "k"), vs = bht_strides(v, "v"),
+       os = bht_strides(o, "o"), gs = bht_strides(dq, "dq"), gk = bht_strides(dk, "dk"), gv = bht_strides(dv, "dv");
+  TORCH_CHECK(gs.v[0] == gk.v[0] && gs.v[1] == gk.v[1] && gs.v[2] == gk.v[2] && gs.v[0] == gv.v[0] &&
+              gs.v[1] == gv.v[1] && gs.v[2] == gv.v[2], "attn bwd: dq/dk/dv must share strides");
+  TORCH_CHECK(q.sizes() == k.sizes() && q.sizes() == v.sizes() && q.sizes() == o.sizes() && q.sizes() == dout.sizes() &&
+              q.sizes() == dq.sizes() && q.sizes() == dk.sizes() && q.sizes() == dv.sizes(), "attn bwd: shape mismatch");
+  const int B = q.size(0), H = q.size(1), T = q.size(2), Dh = q.size(3);
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() && lse.numel() == (int64_t)B * H * T,
+              "attn bwd: lse must be fp32 [B,H,T]");
+  auto delta = at::empty({(int64_t)B * H * T}, q.options().dtype(at::kFloat));
+  int rc = pdt_attn_bwd_drop(reinterpret_cast<const uint16_t*>(dout.data_ptr()), dos.v,
+                             reinterpret_cast<const uint16_t*>(q.data_ptr()), qs.v,
+                             reinterpret_cast<const uint16_t*>(k.data_ptr()), ks.v,
+                             reinterpret_cast<const uint16_t*>(v.data_ptr()), vs.v,
+                             reinterpret_cast<const uint16_t*>(o.data_ptr()), os.v, lse.data_ptr<float>(),
+                             delta.data_ptr<float>(), reinterpret_cast<uint16_t*>(dq.data_ptr()),
+                             reinterpret_cast<uint16_t*>(dk.data_ptr()), reinterpret_cast<uint16_t*>(dv.data_ptr()), gs.v, B,
+                             H, T, Dh, causal, (float)scale, ticket_ptr(ticket, q), (int)dstream, check_thr(thr),
+                             stream());
+  TORCH_CHECK(rc == 0, "pdt_attn_bwd_drop: unsupported head dim ", Dh);
 }
 
 // bias gradient of a Linear layer: column sum of dy [*, D] -> [D] in out_dtype (fp32 / bf16)
@@ -2628,6 +2779,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bias_gelu_bwd", &bias_gelu_bwd);
   m.def("attn_fwd_out", &attn_fwd_out);
   m.def("attn_bwd_out", &attn_bwd_out);
+  m.def("attn_fwd_drop_out", &attn_fwd_drop_out);
+  m.def("attn_bwd_drop_out", &attn_bwd_drop_out);
+  m.def("dropout_begin", &dropout_begin);
+  m.def("dropout_fwd", &dropout_fwd);
+  m.def("dropout_mask", &dropout_mask);
+  m.def("ln_fwd_drop", &ln_fwd_drop);
+  m.def("ln_bwd_drop", &ln_bwd_drop);
   m.def("colsum", &colsum);
   py::class_<P2PComm>(m, "P2PComm")
       .def(py::init<int, int, int64_t, int, int>(), py::arg("rank"), py::arg("world"), py::arg("capacity_bytes"),

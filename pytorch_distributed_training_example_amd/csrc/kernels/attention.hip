@@ -15,7 +15,20 @@
 //   dK/dV kernel: S = Q·K^T (lane = key), dV^T += dO^T·P, dK^T += Q^T·dS  (dO^T, Q^T by tr reads)
 //   dQ kernel:    forward structure, dQ^T += K^T·dS^T
 // so dQ needs no atomics and no cross-workgroup reduction (deterministic).
+//
+// Attention dropout (DROP instantiations): the keep mask of P is regenerated in all three kernels
+// from the ticket (philox.h, 4 x 4 query x key patches), never stored. A forward / dQ lane's four
+// keys 4g..4g+3 of a 16-key subtile are one word of one Philox call; a dK/dV lane's four queries
+// are one byte of each word of one call: one call per 4 scores everywhere. l and the LSE come from
+// the undropped P; the 1 / (1 - p_eff) scale is folded into the O and dV epilogues (one multiply
+// per output instead of one per score) and into dP.
+// The four lanes of a DPP quad (4 consecutive queries in forward / dQ, 4 consecutive keys in dK/dV)
+// all sit in the same patches, so they would compute the same Philox blocks: instead quad lane i
+// computes the i-th of the four blocks the quad needs next (the 4 key subtiles of a tile in
+// forward / dQ; the 2 key subtiles x 2 query subtiles of a 32-query step in dK/dV) and the words go
+// round by quad-broadcast DPP moves: one Philox call per 16 scores instead of one per 4.
 #include "../common.h"
+#include "../philox.h"
 
 #include <type_traits>
 
@@ -118,14 +131,42 @@ struct Stage {
   }
 };
 
+// Word held by quad lane J, in every lane of the quad (v_mov_dpp quad_perm:[J,J,J,J]).
+template <int J>
+__device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, J * 0x55, 0xF, 0xF, true);
+}
+__device__ __forceinline__ uint32_t quad_bcast_j(uint32_t v, int j) {  // j constant after unrolling
+  switch (j) {
+    case 0: return quad_bcast<0>(v);
+    case 1: return quad_bcast<1>(v);
+    case 2: return quad_bcast<2>(v);
+    default: return quad_bcast<3>(v);
+  }
+}
+// The whole Philox result of quad lane j.
+__device__ __forceinline__ PhiloxOut quad_block(const PhiloxOut& o, int j) {
+  return PhiloxOut{{quad_bcast_j(o.w[0], j), quad_bcast_j(o.w[1], j), quad_bcast_j(o.w[2], j), quad_bcast_j(o.w[3], j)}};
+}
+// Forward / dQ: the mask words of query qi for the 4 key subtiles of tile kv0 (keys kv0 + 16 ks + 4 g + r).
+// Quad lane i (= qi & 3: qbase and 16 qb are multiples of 4) computes the block of subtile ks = i.
+__device__ __forceinline__ void drop_tile_words(const DropSite& site, uint64_t bh, int TP, int qi, int kv0, int g,
+                                                int lane, uint32_t (&mw)[4]) {
+  const PhiloxOut mine = drop_block(site, drop_attn_block(bh, TP, qi, kv0 + (lane & 3) * 16 + 4 * g));
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) mw[ks] = drop_pick(quad_block(mine, ks), qi & 3);
+}
+
 // ============================================================================ forward
 // grid (ceil(T/128), H, B), 256 threads; wave w owns queries [blk*128 + 32w, +32) as 2 x 16.
 // ~155 VGPRs: 3 waves per SIMD. Measured alternatives (tools/attn_bench.py, GPT-2 shape): forcing
 // 4 waves/SIMD spills (-14%); prefetching K/V two tiles ahead (+24 VGPR) is -7%.
-template <bool CAUSAL>
+template <bool CAUSAL, bool DROP = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(Tensor4 Q, Tensor4 K, Tensor4 V, uint16_t* __restrict__ O,
                                                        int64_t o_sb, int64_t o_sh, int64_t o_st,
-                                                       float* __restrict__ LSE, int H, int T, float sl2) {
+                                                       float* __restrict__ LSE, int H, int T, float sl2,
+                                                       const int64_t* __restrict__ ticket = nullptr, int dstream = 0,
+                                                       int thr = 0) {
   __shared__ __attribute__((aligned(16))) char lds[2 * 64 * ROW_BYTES];
   char* Ks = lds;
   char* Vs = lds + 64 * ROW_BYTES;
@@ -138,6 +179,10 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(Tensor4 Q, Tensor4 K, 
   const int64_t koff = (int64_t)b * K.sb + (int64_t)h * K.sh;
   const int64_t voff = (int64_t)b * V.sb + (int64_t)h * V.sh;
   const __amdgpu_buffer_rsrc_t krs = slice_rsrc(K.p + koff, T, K.st), vrs = slice_rsrc(V.p + voff, T, V.st);
+  DropSite site;
+  if constexpr (DROP) site = drop_site(ticket, dstream, thr);
+  const uint64_t bh = (uint64_t)b * H + h;
+  const int TP = (T + 3) >> 2;
 
   // Q^T as B operand, held in registers: [qb][k-step]
   bf16x8 bq[2][2];
@@ -227,6 +272,15 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(Tensor4 Q, Tensor4 K, 
 #pragma unroll
         for (int n = 0; n < 4; ++n) oacc[qb][n] *= alpha;
       }
+      if constexpr (DROP) {  // after l: the sum is of the undropped probabilities
+        uint32_t mw[4];
+        drop_tile_words(site, bh, TP, qi, kv0, g, lane, mw);
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (!drop_keep(mw[ks], r, site.thr)) st[qb][ks][r] = 0.f;
+      }
       pb[qb][0] = pack8(st[qb][0], st[qb][1]);
       pb[qb][1] = pack8(st[qb][2], st[qb][3]);
     }
@@ -251,7 +305,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(Tensor4 Q, Tensor4 K, 
     lt += __shfl_xor(lt, 32, 64);
     const int qi = qbase + 16 * qb + c;
     if (qi >= T) continue;
-    const float inv = lt > 0.f ? 1.f / lt : 0.f;
+    float inv = lt > 0.f ? 1.f / lt : 0.f;
+    if constexpr (DROP) inv *= site.scale;
     uint16_t* orow = O + (int64_t)b * o_sb + (int64_t)h * o_sh + (int64_t)qi * o_st;
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
@@ -289,11 +344,13 @@ __global__ __launch_bounds__(256) void attn_bwd_pre_kernel(Tensor4 DO, Tensor4 O
 // ============================================================================ backward: dQ
 // Forward structure: S^T = K Q^T, dP^T = V dO^T (lane = query), dS^T = P^T (dP^T - delta),
 // dQ^T += K^T dS^T (K^T by transposed LDS reads).
-template <bool CAUSAL>
+template <bool CAUSAL, bool DROP = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(Tensor4 Q, Tensor4 K, Tensor4 V, Tensor4 DO,
                                                           const float* __restrict__ LSE, const float* __restrict__ DELTA,
                                                           uint16_t* __restrict__ DQ, int64_t dq_sb, int64_t dq_sh,
-                                                          int64_t dq_st, int H, int T, float sl2, float scale) {
+                                                          int64_t dq_st, int H, int T, float sl2, float scale,
+                                                          const int64_t* __restrict__ ticket = nullptr, int dstream = 0,
+                                                          int thr = 0) {
   __shared__ __attribute__((aligned(16))) char lds[2 * 64 * ROW_BYTES];
   char* Ks = lds;
   char* Vs = lds + 64 * ROW_BYTES;
@@ -307,6 +364,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(Tensor4 Q, Tensor4 
   const int64_t koff = (int64_t)b * K.sb + (int64_t)h * K.sh;
   const int64_t voff = (int64_t)b * V.sb + (int64_t)h * V.sh;
   const int64_t rowoff = ((int64_t)b * H + h) * T;
+  DropSite site;
+  if constexpr (DROP) site = drop_site(ticket, dstream, thr);
+  const uint64_t bh = (uint64_t)b * H + h;
+  const int TP = (T + 3) >> 2;
 
   bf16x8 bq[2][2], bdo[2][2];
   float lse2[2], dlt[2];
@@ -351,6 +412,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(Tensor4 Q, Tensor4 
     auto tile_body = [&](auto edge_c) {
       constexpr bool EDGE = decltype(edge_c)::value;
       bf16x8 dsb[2][2];
+      uint32_t mwq[2][4];
+      if constexpr (DROP) {
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb) drop_tile_words(site, bh, TP, qbase + 16 * qb + c, kv0, g, lane, mwq[qb]);
+      }
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
         const bf16x8 ka0 = lds_row8(Ks, ks * 16 + c, g), ka1 = lds_row8(Ks, ks * 16 + c, 4 + g);
@@ -363,6 +429,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(Tensor4 Q, Tensor4 
           dp = mfma(va0, bdo[qb][0], dp);
           dp = mfma(va1, bdo[qb][1], dp);
           const int qi = qbase + 16 * qb + c;
+          if constexpr (DROP) {  // dP = m * scale * (dO V^T)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) dp[r] = drop_keep(mwq[qb][ks], r, site.thr) ? dp[r] * site.scale : 0.f;
+          }
           f4 ds;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
@@ -412,12 +482,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(Tensor4 Q, Tensor4 
 // grid (ceil(T/128), H, B); wave w owns keys [blk*128 + 32w, +32) as 2 key subtiles of 16.
 // Per 64-query tile (Q, dO staged in LDS): S = Q K^T and dP = dO V^T with lane = key,
 // dV^T += dO^T P and dK^T += Q^T dS (dO^T, Q^T via transposed LDS reads).
-template <bool CAUSAL>
+template <bool CAUSAL, bool DROP = false>
 __global__ __launch_bounds__(256, DKDV_MINW) void attn_bwd_dkdv_kernel(Tensor4 Q, Tensor4 K, Tensor4 V, Tensor4 DO,
                                                             const float* __restrict__ LSE,
                                                             const float* __restrict__ DELTA, uint16_t* __restrict__ DK,
                                                             uint16_t* __restrict__ DV, int64_t g_sb, int64_t g_sh,
-                                                            int64_t g_st, int H, int T, float sl2, float scale) {
+                                                            int64_t g_st, int H, int T, float sl2, float scale,
+                                                            const int64_t* __restrict__ ticket = nullptr,
+                                                            int dstream = 0, int thr = 0) {
   __shared__ __attribute__((aligned(16))) char lds[2 * 64 * ROW_BYTES];
   __shared__ float srow[2][64];  // lse2, delta of the staged query tile
   char* Qs = lds;
@@ -432,6 +504,10 @@ __global__ __launch_bounds__(256, DKDV_MINW) void attn_bwd_dkdv_kernel(Tensor4 Q
   const int64_t koff = (int64_t)b * K.sb + (int64_t)h * K.sh;
   const int64_t voff = (int64_t)b * V.sb + (int64_t)h * V.sh;
   const int64_t rowoff = ((int64_t)b * H + h) * T;
+  DropSite site;
+  if constexpr (DROP) site = drop_site(ticket, dstream, thr);
+  const uint64_t bh = (uint64_t)b * H + h;
+  const int TP = (T + 3) >> 2;
 
   // K^T and V^T as B operands (lane = key column), held in registers: [key subtile][k-step]
   bf16x8 bk[2][2], bv[2][2];
@@ -485,6 +561,11 @@ __global__ __launch_bounds__(256, DKDV_MINW) void attn_bwd_dkdv_kernel(Tensor4 Q
 #pragma unroll
       for (int kq = 0; kq < 2; ++kq) {  // 32-query k-step for the dV/dK products
         bf16x8 pb[2], dsb[2];
+        // quad lane i (= key & 3) computes the block of (key subtile i >> 1, query subtile 2 kq + (i & 1))
+        PhiloxOut mine;
+        if constexpr (DROP)
+          mine = drop_block(site, drop_attn_block(bh, TP, q0 + (2 * kq + (lane & 1)) * 16 + 4 * g,
+                                                  kbase + 16 * ((lane >> 1) & 1) + c));
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
           f4 pp[2], dd[2];
@@ -499,14 +580,22 @@ __global__ __launch_bounds__(256, DKDV_MINW) void attn_bwd_dkdv_kernel(Tensor4 Q
             dp = mfma(da0, bv[kb][0], dp);
             dp = mfma(da1, bv[kb][1], dp);
             const int key = kbase + 16 * kb + c;
+            PhiloxOut mo;
+            if constexpr (DROP) mo = quad_block(mine, 2 * kb + half);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const int ql = qs * 16 + 4 * g + r;
               const int qi = q0 + ql;
               float p = fast_exp2(fmaf(s[r], sl2, -srow[0][ql]));
               if (EDGE && (qi >= T || key >= T || (CAUSAL && key > qi))) p = 0.f;
-              pp[half][r] = p;
-              dd[half][r] = p * (dp[r] - srow[1][ql]);
+              if constexpr (DROP) {  // dV takes P m (scale in the epilogue), dS = P (m scale dP - delta)
+                const bool keep = drop_keep(mo.w[r], key & 3, site.thr);
+                pp[half][r] = keep ? p : 0.f;
+                dd[half][r] = p * ((keep ? dp[r] * site.scale : 0.f) - srow[1][ql]);
+              } else {
+                pp[half][r] = p;
+                dd[half][r] = p * (dp[r] - srow[1][ql]);
+              }
             }
           }
           pb[kb] = pack8(pp[0], pp[1]);
@@ -536,6 +625,10 @@ __global__ __launch_bounds__(256, DKDV_MINW) void attn_bwd_dkdv_kernel(Tensor4 Q
     for (int n = 0; n < 4; ++n) {
       float a4[4] = {dk[kb][n][0] * scale, dk[kb][n][1] * scale, dk[kb][n][2] * scale, dk[kb][n][3] * scale};
       float v4[4] = {dv[kb][n][0], dv[kb][n][1], dv[kb][n][2], dv[kb][n][3]};
+      if constexpr (DROP) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v4[j] *= site.scale;
+      }
       Vec4<uint16_t>::st(DK + off, 16 * n + 4 * g, a4);
       Vec4<uint16_t>::st(DV + off, 16 * n + 4 * g, v4);
     }
@@ -584,6 +677,52 @@ int pdt_attn_bwd(const uint16_t* dout, const int64_t* dos, const uint16_t* q, co
                        gs[2], H, T, sl2, scale);
     hipLaunchKernelGGL(attn_bwd_dkdv_kernel<false>, grid, dim3(256), 0, s, Q, K, V, DO, lse, delta, dk, dv, gs[0],
                        gs[1], gs[2], H, T, sl2, scale);
+  }
+  return 0;
+}
+
+// Attention dropout (thr in 1..255; ticket int64[2] = (key, step), philox.h): same arguments otherwise.
+int pdt_attn_fwd_drop(const uint16_t* q, const int64_t* qs, const uint16_t* k, const int64_t* ks, const uint16_t* v,
+                      const int64_t* vs, uint16_t* o, const int64_t* os, float* lse, int B, int H, int T, int Dh,
+                      int causal, float scale, const int64_t* ticket, int dstream, int thr, hipStream_t s) {
+  if (Dh != D) return -1;
+  if (ticket == nullptr || thr < 1 || thr > 255) return -2;
+  const Tensor4 Q{q, qs[0], qs[1], qs[2]}, K{k, ks[0], ks[1], ks[2]}, V{v, vs[0], vs[1], vs[2]};
+  const dim3 grid((T + 127) / 128, H, B);
+  const float sl2 = scale * LOG2E;
+  if (causal)
+    hipLaunchKernelGGL((attn_fwd_kernel<true, true>), grid, dim3(256), 0, s, Q, K, V, o, os[0], os[1], os[2], lse, H,
+                       T, sl2, ticket, dstream, thr);
+  else
+    hipLaunchKernelGGL((attn_fwd_kernel<false, true>), grid, dim3(256), 0, s, Q, K, V, o, os[0], os[1], os[2], lse, H,
+                       T, sl2, ticket, dstream, thr);
+  return 0;
+}
+
+int pdt_attn_bwd_drop(const uint16_t* dout, const int64_t* dos, const uint16_t* q, const int64_t* qs,
+                      const uint16_t* k, const int64_t* ks, const uint16_t* v, const int64_t* vs, const uint16_t* o,
+                      const int64_t* os, const float* lse, float* delta, uint16_t* dq, uint16_t* dk, uint16_t* dv,
+                      const int64_t* gs, int B, int H, int T, int Dh, int causal, float scale, const int64_t* ticket,
+                      int dstream, int thr, hipStream_t s) {
+  if (Dh != D) return -1;
+  if (ticket == nullptr || thr < 1 || thr > 255) return -2;
+  const Tensor4 Q{q, qs[0], qs[1], qs[2]}, K{k, ks[0], ks[1], ks[2]}, V{v, vs[0], vs[1], vs[2]};
+  const Tensor4 DO{dout, dos[0], dos[1], dos[2]}, Ot{o, os[0], os[1], os[2]};
+  const int64_t rows = (int64_t)B * H * T;
+  hipLaunchKernelGGL(attn_bwd_pre_kernel, dim3((unsigned)((rows * 8 + 255) / 256)), dim3(256), 0, s, DO, Ot, delta, H,
+                     T, rows);
+  const dim3 grid((T + 127) / 128, H, B);
+  const float sl2 = scale * LOG2E;
+  if (causal) {
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<true, true>), grid, dim3(256), 0, s, Q, K, V, DO, lse, delta, dq, gs[0],
+                       gs[1], gs[2], H, T, sl2, scale, ticket, dstream, thr);
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<true, true>), grid, dim3(256), 0, s, Q, K, V, DO, lse, delta, dk, dv,
+                       gs[0], gs[1], gs[2], H, T, sl2, scale, ticket, dstream, thr);
+  } else {
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<false, true>), grid, dim3(256), 0, s, Q, K, V, DO, lse, delta, dq, gs[0],
+                       gs[1], gs[2], H, T, sl2, scale, ticket, dstream, thr);
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<false, true>), grid, dim3(256), 0, s, Q, K, V, DO, lse, delta, dk, dv,
+                       gs[0], gs[1], gs[2], H, T, sl2, scale, ticket, dstream, thr);
   }
   return 0;
 }

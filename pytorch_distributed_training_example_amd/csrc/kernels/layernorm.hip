@@ -13,6 +13,7 @@
 // (2 per block forward, 2 per block backward) and one full read of s.
 #include "../common.h"
 #include "../fp8_pack.h"
+#include "../philox.h"
 
 using namespace pdt;
 
@@ -49,16 +50,23 @@ __device__ __forceinline__ float ln_val(float v, float mean, float rstd, float w
 }
 
 // K = D / 256: 4-element groups per lane (D = 256*K)
-template <typename T, int K>
+// DROP (residual dropout, with res): s = x + round_T(h * m * scale), the mask regenerated from the
+// ticket (philox.h, flat layout: a lane's 4 elements are one word of one call). The dropped h is
+// rounded to T before the add, as dropout_kernel would have stored it, so s and y equal
+// add+LayerNorm of the separately dropped h bit for bit, with no extra byte moved.
+template <typename T, int K, bool DROP = false>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ res,
                                                      const float* __restrict__ w, const float* __restrict__ b,
                                                      T* __restrict__ y, T* __restrict__ sum_out,
                                                      float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                     int64_t N, float eps) {
+                                                     int64_t N, float eps, const int64_t* __restrict__ ticket = nullptr,
+                                                     int dstream = 0, int thr = 0) {
   constexpr int D = 256 * K;
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
   if (row >= N) return;
+  DropSite site;
+  if constexpr (DROP) site = drop_site(ticket, dstream, thr);
   const T* xr = x + row * D;
   float v[K][4];
 #pragma unroll
@@ -67,6 +75,11 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
     if (res != nullptr) {  // s = x + h, stored and normalised at storage precision
       float hv[4];
       Vec4<T>::ld(res + row * D, (int64_t)(k * 256 + lane * 4), hv);
+      if constexpr (DROP) {
+        const uint32_t mw = drop_flat_word(site, (uint64_t)(row * D + k * 256 + lane * 4));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) hv[j] = drop_keep(mw, j, site.thr) ? round_to<T>(hv[j] * site.scale) : 0.f;
+      }
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[k][j] = round_to<T>(v[k][j] + hv[j]);
       Vec4<T>::st(sum_out + row * D, (int64_t)(k * 256 + lane * 4), v[k]);
@@ -195,13 +208,25 @@ __global__ __launch_bounds__(512) void ln_fwd_fp8_kernel(const uint16_t* __restr
 }
 
 // Backward: dx per row; per-block partial dgamma/dbeta written to part[blk][2][D].
-template <typename T, int K>
+// DROP: a second output dh = round_T(dx * m * scale), the gradient of the dropped residual branch
+// (dx as stored, i.e. rounded to T first: what a separate dropout backward would have read). It is
+// formed in a second loop at the end of the kernel, each lane re-reading the dx values it wrote
+// itself (its own stores, still in L2: no HBM read). Forming dh next to dx in the main loop changed
+// how the compiler vectorised and contracted the dx / dgamma / dbeta arithmetic (1-ulp differences
+// from the non-DROP instantiation); with the main loop's code left exactly as it is, the DROP kernel's
+// dx, dgamma, dbeta equal the non-DROP kernel's bit for bit.
+template <typename T, int K, bool DROP = false>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                                      const T* __restrict__ dres,
                                                      const float* __restrict__ w, const float* __restrict__ mean,
                                                      const float* __restrict__ rstd, T* __restrict__ dx,
-                                                     float* __restrict__ part, int64_t N, int rows_per_block) {
+                                                     float* __restrict__ part, int64_t N, int rows_per_block,
+                                                     T* __restrict__ dh = nullptr,
+                                                     const int64_t* __restrict__ ticket = nullptr, int dstream = 0,
+                                                     int thr = 0) {
   constexpr int D = 256 * K;
+  DropSite site;
+  if constexpr (DROP) site = drop_site(ticket, dstream, thr);
   __shared__ float sdw[4][D];
   __shared__ float sdb[4][D];
   const int lane = threadIdx.x & 63, wv_id = threadIdx.x >> 6;
@@ -277,6 +302,20 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
   for (int c = threadIdx.x; c < D; c += 256) {
     part[((int64_t)blockIdx.x * 2 + 0) * D + c] = sdw[0][c] + sdw[1][c] + sdw[2][c] + sdw[3][c];
     part[((int64_t)blockIdx.x * 2 + 1) * D + c] = sdb[0][c] + sdb[1][c] + sdb[2][c] + sdb[3][c];
+  }
+  if constexpr (DROP) {  // the same (row, k, lane) ownership as the stores of dx above
+    for (int64_t row = r0 + wv_id; row < r1; row += 4) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const int64_t c = row * D + k * 256 + lane * 4;
+        float o[4];
+        Vec4<T>::ld(dx, c, o);
+        const uint32_t mw = drop_flat_word(site, (uint64_t)c);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = drop_keep(mw, j, site.thr) ? o[j] * site.scale : 0.f;
+        Vec4<T>::st(dh, c, o);
+      }
+    }
   }
 }
 
@@ -402,6 +441,36 @@ int pdt_ln_fwd_fp8(const uint16_t* x, const uint16_t* res, const float* w, const
   return 0;
 }
 
+// Residual dropout inside add+LayerNorm: s = x + dropout(res), y = LN(s). thr in 1..255.
+int pdt_ln_fwd_drop(const void* x, const void* res, int dtype, const float* w, const float* b, void* y,
+                    void* sum_out, float* mean, float* rstd, int64_t N, int D, float eps, const int64_t* ticket,
+                    int dstream, int thr, hipStream_t s) {
+  if (res == nullptr || sum_out == nullptr || ticket == nullptr || thr < 1 || thr > 255) return -2;
+  if (D % 256 != 0) return -1;
+  if (N == 0) return 0;
+  const dim3 grid((unsigned)((N + kRowsPerBlock - 1) / kRowsPerBlock));
+#define PDT_LNFD(K)                                                                                            \
+  if (dtype == 0)                                                                                              \
+    hipLaunchKernelGGL((ln_fwd_kernel<float, K, true>), grid, dim3(256), 0, s, (const float*)x, (const float*)res, \
+                       w, b, (float*)y, (float*)sum_out, mean, rstd, N, eps, ticket, dstream, thr);             \
+  else                                                                                                         \
+    hipLaunchKernelGGL((ln_fwd_kernel<uint16_t, K, true>), grid, dim3(256), 0, s, (const uint16_t*)x,           \
+                       (const uint16_t*)res, w, b, (uint16_t*)y, (uint16_t*)sum_out, mean, rstd, N, eps, ticket, \
+                       dstream, thr);
+  switch (D / 256) {
+    case 1: PDT_LNFD(1); break;
+    case 2: PDT_LNFD(2); break;
+    case 3: PDT_LNFD(3); break;
+    case 4: PDT_LNFD(4); break;
+    case 5: PDT_LNFD(5); break;
+    case 6: PDT_LNFD(6); break;
+    case 8: PDT_LNFD(8); break;
+    default: return -1;
+  }
+#undef PDT_LNFD
+  return 0;
+}
+
 // dres: optional gradient added into dx (residual stream), same dtype/layout as dx.
 int pdt_ln_bwd(const void* dy, const void* x, const void* dres, int dtype, const float* w, const float* mean,
                const float* rstd, void* dx, float* dw, float* db, int64_t N, int D, float* ws, hipStream_t s) {
@@ -427,6 +496,39 @@ int pdt_ln_bwd(const void* dy, const void* x, const void* dres, int dtype, const
     default: return -1;
   }
 #undef PDT_LNB
+  hipLaunchKernelGGL(ln_bwd_finalize_kernel, dim3((D + 15) / 16), dim3(256), 0, s, ws, nblk, D, dw, db);
+  return 0;
+}
+
+// The backward of pdt_ln_fwd_drop: dx as pdt_ln_bwd, and dh = dropout-backward of dx.
+int pdt_ln_bwd_drop(const void* dy, const void* x, const void* dres, int dtype, const float* w, const float* mean,
+                    const float* rstd, void* dx, void* dh, float* dw, float* db, int64_t N, int D, float* ws,
+                    const int64_t* ticket, int dstream, int thr, hipStream_t s) {
+  if (dh == nullptr || ticket == nullptr || thr < 1 || thr > 255) return -2;
+  if (D % 256 != 0 || D > 2048) return -1;
+  if (N == 0) return 0;
+  int rpb;
+  const int nblk = ln_bwd_blocks(N, rpb);
+#define PDT_LNBD(K)                                                                                           \
+  if (dtype == 0)                                                                                             \
+    hipLaunchKernelGGL((ln_bwd_kernel<float, K, true>), dim3(nblk), dim3(256), 0, s, (const float*)dy,         \
+                       (const float*)x, (const float*)dres, w, mean, rstd, (float*)dx, ws, N, rpb, (float*)dh, \
+                       ticket, dstream, thr);                                                                 \
+  else                                                                                                        \
+    hipLaunchKernelGGL((ln_bwd_kernel<uint16_t, K, true>), dim3(nblk), dim3(256), 0, s, (const uint16_t*)dy,   \
+                       (const uint16_t*)x, (const uint16_t*)dres, w, mean, rstd, (uint16_t*)dx, ws, N, rpb,    \
+                       (uint16_t*)dh, ticket, dstream, thr);
+  switch (D / 256) {
+    case 1: PDT_LNBD(1); break;
+    case 2: PDT_LNBD(2); break;
+    case 3: PDT_LNBD(3); break;
+    case 4: PDT_LNBD(4); break;
+    case 5: PDT_LNBD(5); break;
+    case 6: PDT_LNBD(6); break;
+    case 8: PDT_LNBD(8); break;
+    default: return -1;
+  }
+#undef PDT_LNBD
   hipLaunchKernelGGL(ln_bwd_finalize_kernel, dim3((D + 15) / 16), dim3(256), 0, s, ws, nblk, D, dw, db);
   return 0;
 }

@@ -75,6 +75,12 @@ def set_rng_state(st: Dict[str, Any]) -> None:
         torch.cuda.set_rng_state(st["cuda"])
 
 
+def _dropout_state() -> Dict[str, int]:
+    """{"seed", "step"} of the dropout counter (ops/dropout.py), plain ints (weights_only loads)."""
+    from ..ops.dropout import get_state
+    return get_state()
+
+
 def save_checkpoint(path: str, model: nn.Module, optimizer=None, scheduler=None, scaler=None,
                     sampler=None, epoch: int = 0, step: int = 0, extra: Optional[dict] = None) -> None:
     rank = launcher.get_rank()
@@ -90,6 +96,7 @@ def save_checkpoint(path: str, model: nn.Module, optimizer=None, scheduler=None,
             "step": step,
             "world_size": launcher.get_world_size(),
             "rng": rng_state(),
+            "dropout": _dropout_state(),
             "extra": extra or {},
         }
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -111,6 +118,9 @@ def load_checkpoint(path: str, model: nn.Module, optimizer=None, scheduler=None,
         scaler.load_state_dict(ck["scaler"])
     if sampler is not None and ck.get("sampler") is not None and hasattr(sampler, "load_state_dict"):
         sampler.load_state_dict(ck["sampler"])
+    if ck.get("dropout") is not None:  # absent in checkpoints written before dropout existed
+        from ..ops.dropout import set_state
+        set_state(int(ck["dropout"]["seed"]), int(ck["dropout"]["step"]))
     if restore_rng and ck.get("rng") is not None:
         try:
             set_rng_state(ck["rng"])

@@ -14,6 +14,7 @@ import torch
 from torch import nn
 
 from ..ops.cross_entropy import cross_entropy
+from ..ops.dropout import begin_forward, dropout
 from ..ops.embedding import token_position_embedding
 from ..ops.layernorm import LayerNorm
 from .transformer import Block, init_weights, run_blocks
@@ -26,6 +27,7 @@ class GPTConfig:
     n_embd: int = 1024
     block_size: int = 1024
     vocab_size: int = 50304   # 50257 padded to a multiple of 64
+    dropout: float = 0.0      # GPT-2's embedding / attention / residual dropout (0.1 as published)
 
 
 class GPT(nn.Module):
@@ -35,7 +37,8 @@ class GPT(nn.Module):
         self.transformer = nn.ModuleDict(dict(
             wte=nn.Embedding(cfg.vocab_size, cfg.n_embd),
             wpe=nn.Embedding(cfg.block_size, cfg.n_embd),
-            h=nn.ModuleList([Block(cfg.n_embd, cfg.n_head, 4.0, causal=True, approximate="tanh")
+            h=nn.ModuleList([Block(cfg.n_embd, cfg.n_head, 4.0, causal=True, approximate="tanh",
+                                   dropout=cfg.dropout)
                              for _ in range(cfg.n_layer)]),
             ln_f=LayerNorm(cfg.n_embd),
         ))
@@ -46,7 +49,10 @@ class GPT(nn.Module):
     def forward(self, idx: torch.Tensor, targets: torch.Tensor | None = None):
         # one fused gather pass forward, deterministic scatter backward (ops/embedding.py)
         x = token_position_embedding(idx, self.transformer.wte.weight, self.transformer.wpe.weight)
-        x = run_blocks(self.transformer.h, x, self.transformer.ln_f)  # == ln_f(h[-1](...h[0](x)))
+        # one ticket per training forward (ops/dropout.py); eval / dropout=0: none, nothing launched
+        ticket = begin_forward(x.device) if self.training and self.cfg.dropout > 0 else None
+        x = dropout(x, self.cfg.dropout, ticket)  # embedding dropout
+        x = run_blocks(self.transformer.h, x, self.transformer.ln_f, ticket)  # == ln_f(h[-1](...h[0](x)))
         logits = self.lm_head(x)
         if targets is None:
             return logits

@@ -7,7 +7,12 @@ Not in the reference (LeNet only). MI355X-first choices:
     (ops/gelu.py), so the [tokens, 4·D] activation is read/written once;
   * LayerNorm is the wave-per-row HIP kernel (ops/layernorm.py) with fp32 parameters;
   * attention goes through ``ops.attention.attention`` ([B, H, T, Dh] bf16);
-  * the LM / classifier loss is the fused softmax-cross-entropy kernel.
+  * the LM / classifier loss is the fused softmax-cross-entropy kernel;
+  * dropout (``Block(..., dropout=p)``: attention probabilities, attention ``c_proj`` output, MLP
+    ``c_proj`` output) draws counter-generated masks (ops/dropout.py): inside the flash kernels and
+    inside the add+LayerNorm kernels, no mask tensor anywhere. The model's forward opens a ticket
+    (``begin_forward``) and passes it down; eval mode and ``dropout=0`` pass ``None`` and run
+    exactly the code without dropout.
 """
 from __future__ import annotations
 
@@ -20,6 +25,7 @@ from torch import nn
 
 from ..config import SW
 from ..ops.attention import attention_qkv
+from ..ops.dropout import begin_forward, dropout
 from ..ops.fp8 import add_layer_norm_fp8, fp8_input_slot, fp8_linear, fp8_mlp
 from ..ops.gelu import bias_gelu
 from ..ops.layernorm import LayerNorm, add_layer_norm
@@ -47,9 +53,10 @@ class SelfAttention(nn.Module):
         self.c_proj = nn.Linear(dim, dim, bias=bias)
         self.dropout = dropout
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, ticket=None) -> torch.Tensor:
         qkv = linear(x, self.c_attn)  # [B, T, 3D]; attention reads Q/K/V in place
-        y = attention_qkv(qkv, self.heads, causal=self.causal, dropout_p=self.dropout if self.training else 0.0)
+        y = attention_qkv(qkv, self.heads, causal=self.causal, dropout_p=self.dropout if self.training else 0.0,
+                          ticket=ticket)
         return linear(y, self.c_proj)
 
 
@@ -79,40 +86,53 @@ class Block(nn.Module):
     """Pre-norm transformer block: x + attn(ln_1(x)), then x + mlp(ln_2(x))."""
 
     def __init__(self, dim: int, heads: int, mlp_ratio: float = 4.0, causal: bool = False,
-                 approximate: str = "none", eps: float = 1e-5):
+                 approximate: str = "none", eps: float = 1e-5, dropout: float = 0.0):
         super().__init__()
         self.ln_1 = LayerNorm(dim, eps=eps)
-        self.attn = SelfAttention(dim, heads, causal)
+        self.attn = SelfAttention(dim, heads, causal, dropout=dropout)
         self.ln_2 = LayerNorm(dim, eps=eps)
         self.mlp = MLP(dim, int(dim * mlp_ratio), approximate)
+        self.dropout = dropout
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        x = x + self.attn(self.ln_1(x))
-        x = x + self.mlp(self.ln_2(x))
+    def forward(self, x: torch.Tensor, ticket=None) -> torch.Tensor:
+        """Unfused path (PDT_FUSED_ADDLN=0, or a block called on its own): elementwise dropout op."""
+        p = self.dropout if self.training else 0.0
+        if p and ticket is None:
+            ticket = begin_forward(x.device)
+        x = x + dropout(self.attn(self.ln_1(x), ticket), p, ticket)
+        x = x + dropout(self.mlp(self.ln_2(x)), p, ticket)
         return x
 
 
-def run_blocks(blocks, x: torch.Tensor, final_ln: nn.Module) -> torch.Tensor:
+def run_blocks(blocks, x: torch.Tensor, final_ln: nn.Module, ticket=None) -> torch.Tensor:
     """``final_ln(blocks(x))`` for pre-norm blocks, with every residual add fused into the
     LayerNorm that follows it (the block's ln_2, the next block's ln_1, finally ``final_ln``):
     one add+LN kernel per residual step forward and one LN-backward-with-accumulate backward,
-    instead of separate add kernels each way (ops/layernorm.py add_layer_norm)."""
+    instead of separate add kernels each way (ops/layernorm.py add_layer_norm). ``ticket`` (the
+    model's ``begin_forward``; None in eval mode or without dropout) carries the blocks' residual and
+    attention dropout into those same kernels."""
     blocks = list(blocks)
     if not blocks or not SW.fused_addln:
         for blk in blocks:
-            x = blk(x)
+            x = blk(x, ticket) if ticket is not None else blk(x)
         return final_ln(x)
     y = blocks[0].ln_1(x)
     for i, blk in enumerate(blocks):
-        x, y = _add_ln(x, blk.attn(y), blk.ln_2, blk.mlp)
+        p = blk.dropout if (ticket is not None and blk.training) else 0.0
+        tk = ticket if p else None
+        x, y = _add_ln(x, blk.attn(y, tk), blk.ln_2, blk.mlp, p, tk)
         nxt, cons = (blocks[i + 1].ln_1, blocks[i + 1].attn.c_attn) if i + 1 < len(blocks) else (final_ln, None)
-        x, y = _add_ln(x, blk.mlp(y), nxt, cons)
+        x, y = _add_ln(x, blk.mlp(y), nxt, cons, p, tk)
     return y
 
 
-def _add_ln(x, h, ln, consumer):
+def _add_ln(x, h, ln, consumer, p=0.0, ticket=None):
     """add_layer_norm, or its fp8-emitting form when ``consumer`` (the module the normalised output
-    feeds) runs an fp8 GEMM on it (ops/fp8.py fp8_input_slot)."""
+    feeds) runs an fp8 GEMM on it (ops/fp8.py fp8_input_slot). With residual dropout (``p > 0`` and
+    a ticket) always the bf16 dropout-add-LN kernel: the fp8-emitting form has no dropout, and the
+    consumer GEMM casts its input as it does for any plain tensor."""
+    if p and ticket is not None:
+        return add_layer_norm(x, h, ln, p, ticket)
     if consumer is not None and getattr(ln, "weight", None) is not None and h.shape == x.shape:
         t = fp8_input_slot(consumer, x)
         if (t is not None and x.dtype == torch.bfloat16 and h.dtype == x.dtype and x.shape[-1] % 256 == 0

@@ -5,6 +5,11 @@ patches), learned position embedding, class token, 12 pre-norm blocks (D=768, 12
 MLP 3072, exact-erf GELU), final LayerNorm, linear head on the class token. Parameter names
 follow torchvision's ``vit_b_16`` layout loosely (``conv_proj``, ``class_token``,
 ``encoder.pos_embedding``, ``encoder.layers.{i}``, ``encoder.ln``, ``heads.head``).
+
+``dropout=p`` (0.1 when trained from scratch): after the position-embedding add, on the attention
+probabilities and on both residual branches (models/transformer.py). torchvision's ViT also drops
+inside the MLP after the GELU; that site is NOT applied here — it would have to live in the fused
+bias+GELU kernel — so ``dropout=p`` regularises slightly less than torchvision's ``dropout=p``.
 """
 from __future__ import annotations
 
@@ -12,21 +17,26 @@ import torch
 from torch import nn
 
 from ..ops.conv import PatchConv2d
+from ..ops.dropout import begin_forward, dropout
 from ..ops.layernorm import LayerNorm
 from .transformer import Block, init_weights, run_blocks
 
 
 class _Encoder(nn.Module):
-    def __init__(self, seq: int, dim: int, depth: int, heads: int, mlp_ratio: float):
+    def __init__(self, seq: int, dim: int, depth: int, heads: int, mlp_ratio: float, dropout: float = 0.0):
         super().__init__()
         self.pos_embedding = nn.Parameter(torch.empty(1, seq, dim).normal_(std=0.02))
-        self.layers = nn.ModuleList([Block(dim, heads, mlp_ratio, causal=False, approximate="none", eps=1e-6)
+        self.layers = nn.ModuleList([Block(dim, heads, mlp_ratio, causal=False, approximate="none", eps=1e-6,
+                                           dropout=dropout)
                                      for _ in range(depth)])
         self.ln = LayerNorm(dim, eps=1e-6)
+        self.dropout = dropout
 
     def forward(self, x):
         x = x + self.pos_embedding.to(x.dtype)
-        return run_blocks(self.layers, x, self.ln)  # == ln(layers[-1](...layers[0](x)))
+        ticket = begin_forward(x.device) if self.training and self.dropout > 0 else None
+        x = dropout(x, self.dropout, ticket)
+        return run_blocks(self.layers, x, self.ln, ticket)  # == ln(layers[-1](...layers[0](x)))
 
 
 class _Heads(nn.Module):
@@ -40,14 +50,14 @@ class _Heads(nn.Module):
 
 class VisionTransformer(nn.Module):
     def __init__(self, image_size: int = 224, patch_size: int = 16, dim: int = 768, depth: int = 12,
-                 heads: int = 12, mlp_ratio: float = 4.0, num_classes: int = 1000, **_):
+                 heads: int = 12, mlp_ratio: float = 4.0, num_classes: int = 1000, dropout: float = 0.0, **_):
         super().__init__()
         self.patch_size = patch_size
         n = (image_size // patch_size) ** 2
         # patchify + one GEMM on the GPU (ops/conv.py PatchConv2d; nn.Conv2d parameters / state_dict)
         self.conv_proj = PatchConv2d(3, dim, kernel_size=patch_size, stride=patch_size)
         self.class_token = nn.Parameter(torch.zeros(1, 1, dim))
-        self.encoder = _Encoder(n + 1, dim, depth, heads, mlp_ratio)
+        self.encoder = _Encoder(n + 1, dim, depth, heads, mlp_ratio, dropout)
         self.heads = _Heads(dim, num_classes)
         init_weights(self)
         nn.init.zeros_(self.heads.head.weight)

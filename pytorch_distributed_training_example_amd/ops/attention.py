@@ -53,20 +53,68 @@ class _FlashQKVFn(torch.autograd.Function):
         return dqkv, None, None, None
 
 
+class _FlashQKVDropFn(torch.autograd.Function):
+    """_FlashQKVFn with dropout on the attention probabilities: the DROP kernels regenerate the mask
+    from (ticket, stream) in the forward, dQ and dK/dV kernels (csrc/philox.h); nothing else is saved."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, causal, scale, ticket, stream, thr):
+        B, T, _ = qkv.shape
+        (q, k, v), dh = _views(qkv, heads)
+        out = torch.empty(B, T, heads, dh, device=qkv.device, dtype=qkv.dtype)
+        lse = torch.empty(B, heads, T, device=qkv.device, dtype=torch.float32)
+        native().attn_fwd_drop_out(q, k, v, out.permute(0, 2, 1, 3), lse, causal, scale, ticket, stream, thr)
+        ctx.save_for_backward(qkv, out, lse, ticket)
+        ctx.heads, ctx.causal, ctx.scale, ctx.stream, ctx.thr = heads, causal, scale, stream, thr
+        return out.view(B, T, heads * dh)
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse, ticket = ctx.saved_tensors
+        B, T, _ = qkv.shape
+        heads = ctx.heads
+        (q, k, v), dh = _views(qkv, heads)
+        dout = dout.contiguous().view(B, T, heads, dh).permute(0, 2, 1, 3)
+        dqkv = torch.empty_like(qkv)
+        (dq, dk, dv), _ = _views(dqkv, heads)
+        native().attn_bwd_drop_out(dout, q, k, v, out.permute(0, 2, 1, 3), lse, dq, dk, dv, ctx.causal, ctx.scale,
+                                   ticket, ctx.stream, ctx.thr)
+        return dqkv, None, None, None, None, None, None
+
+
 def attention_qkv(qkv: torch.Tensor, heads: int, causal: bool = False, dropout_p: float = 0.0,
-                  scale: float | None = None) -> torch.Tensor:
-    """Packed-QKV attention: [B, T, 3·H·Dh] -> [B, T, H·Dh]."""
+                  scale: float | None = None, ticket=None, stream: int | None = None) -> torch.Tensor:
+    """Packed-QKV attention: [B, T, 3·H·Dh] -> [B, T, H·Dh].
+
+    ``dropout_p > 0`` with a ``ticket`` (ops/dropout.py) drops attention probabilities with the
+    counter-generated mask and stays on the flash kernels (GPU) / the masked math reference (CPU).
+    Without a ticket (or under PDT_DROPOUT_FUSED=0) ``dropout_p > 0`` is aten's: SDPA on the GPU."""
     B, T, C3 = qkv.shape
     dh = C3 // (3 * heads)
     scale = scale if scale is not None else 1.0 / math.sqrt(dh)
-    if (use_native(qkv) and qkv.dtype == torch.bfloat16 and dh in KERNEL_HEAD_DIMS and dropout_p == 0.0
-            and qkv.stride(-1) == 1 and hasattr(native(), "attn_fwd_out")):
+    thr = 0
+    if dropout_p != 0.0 and ticket is not None and ticket.tensor is not None:
+        from .dropout import threshold
+        thr = threshold(dropout_p)
+        if stream is None:
+            stream = ticket.next_stream()
+        if thr == 0:
+            dropout_p = 0.0
+    flash = (use_native(qkv) and qkv.dtype == torch.bfloat16 and dh in KERNEL_HEAD_DIMS
+             and qkv.stride(-1) == 1 and hasattr(native(), "attn_fwd_out"))
+    if flash and thr > 0:
+        return _FlashQKVDropFn.apply(qkv.contiguous(), heads, causal, scale, ticket.tensor, int(stream), thr)
+    if flash and dropout_p == 0.0:
         return _FlashQKVFn.apply(qkv.contiguous(), heads, causal, scale)
     (q, k, v), _ = _views(qkv, heads)
-    if qkv.is_cuda:
+    if thr > 0:  # our mask off the flash kernels (CPU, other head dims / dtypes): masked math reference
+        from .dropout import dropout_mask
+        m = dropout_mask(ticket.tensor, stream, (B, heads, T, T), dropout_p, "attn")
+        y = attention_reference(q, k, v, causal, scale, keep=m, keep_scale=256.0 / (256 - thr)).to(qkv.dtype)
+    elif qkv.is_cuda:
         y = F.scaled_dot_product_attention(q, k, v, dropout_p=dropout_p, is_causal=causal, scale=scale)
     else:
-        y = attention_reference(q, k, v, causal, scale).to(qkv.dtype)
+        y = attention_reference(q, k, v, causal, scale, aten_dropout_p=dropout_p).to(qkv.dtype)
     return y.transpose(1, 2).reshape(B, T, heads * dh)
 
 
@@ -76,12 +124,18 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = 
     return F.scaled_dot_product_attention(q, k, v, dropout_p=dropout_p, is_causal=causal, scale=scale)
 
 
-def attention_reference(q, k, v, causal=False, scale=None):
-    """fp32 math reference (tests, CPU)."""
+def attention_reference(q, k, v, causal=False, scale=None, keep=None, keep_scale=1.0, aten_dropout_p=0.0):
+    """fp32 math reference (tests, CPU). ``keep`` [B, H, T, T] bool: dropout of the probabilities
+    (softmax(S) * keep * keep_scale); ``aten_dropout_p``: ``F.dropout`` on them instead."""
     scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
     s = (q.float() @ k.float().transpose(-1, -2)) * scale
     if causal:
         T, S = s.shape[-2], s.shape[-1]
         mask = torch.ones(T, S, dtype=torch.bool, device=q.device).tril(S - T)
         s = s.masked_fill(~mask, float("-inf"))
-    return torch.softmax(s, dim=-1) @ v.float()
+    p = torch.softmax(s, dim=-1)
+    if keep is not None:
+        p = p * keep.to(p.dtype) * keep_scale
+    elif aten_dropout_p:
+        p = F.dropout(p, aten_dropout_p, training=True)
+    return p @ v.float()

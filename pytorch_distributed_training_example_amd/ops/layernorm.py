@@ -64,10 +64,49 @@ def _ln_native_ok(x, weight, bias, normalized_shape) -> bool:
             and weight.dtype == torch.float32 and bias.dtype == torch.float32)
 
 
-def add_layer_norm(x: torch.Tensor, h: torch.Tensor, ln: nn.LayerNorm):
+class _DropAddLNFn(torch.autograd.Function):
+    """(s, y) = (x + dropout(h), LayerNorm(s)) in one kernel; backward dx = LN'(dy) + ds and
+    dh = dropout'(dx) from one kernel too. The mask is regenerated from (ticket, stream) both ways
+    (csrc/philox.h); bit for bit ``_AddLNFn`` on the separately dropped ``h``."""
+
+    @staticmethod
+    def forward(ctx, x, h, weight, bias, eps, ticket, stream, thr):
+        y, mean, rstd, s = native().ln_fwd_drop(x, weight, bias, eps, h, ticket, stream, thr)
+        ctx.save_for_backward(s, weight, mean, rstd, ticket)
+        ctx.stream, ctx.thr = stream, thr
+        return s, y
+
+    @staticmethod
+    def backward(ctx, ds, dy):
+        s, weight, mean, rstd, ticket = ctx.saved_tensors
+        if dy is None:
+            dy = torch.zeros_like(s)
+        dres = ds.contiguous() if ds is not None else None
+        dx, dh, dw, db = native().ln_bwd_drop(dy.contiguous(), s, weight, mean, rstd, dres, ticket, ctx.stream,
+                                              ctx.thr)
+        return dx, dh, dw, db, None, None, None, None
+
+
+def add_layer_norm(x: torch.Tensor, h: torch.Tensor, ln: nn.LayerNorm, p: float = 0.0, ticket=None,
+                   stream: int | None = None):
     """Pre-norm residual step: returns ``(s, ln(s))`` with ``s = x + h``. On the native path the
     add, the LayerNorm and (in backward) the two gradients of ``s`` are one kernel each way,
-    instead of an add kernel + LayerNorm forward and LayerNorm backward + an add kernel."""
+    instead of an add kernel + LayerNorm forward and LayerNorm backward + an add kernel.
+
+    ``p > 0`` with a ``ticket`` (ops/dropout.py): ``s = x + dropout(h)`` — residual dropout inside
+    the same kernels where the native path applies (no extra pass forward, one extra write of
+    ``dh`` backward), else the elementwise dropout op followed by the ``p == 0`` path."""
+    if p != 0.0 and ticket is not None:
+        from .dropout import dropout, threshold
+        thr = threshold(p)
+        if ticket.tensor is not None and thr > 0:
+            if stream is None:
+                stream = ticket.next_stream()
+            if (_ln_native_ok(x, ln.weight, ln.bias, ln.normalized_shape) and h.shape == x.shape
+                    and h.dtype == x.dtype):
+                return _DropAddLNFn.apply(x.contiguous(), h.contiguous(), ln.weight, ln.bias, float(ln.eps),
+                                          ticket.tensor, int(stream), thr)
+        h = dropout(h, p, ticket, stream)
     if (_ln_native_ok(x, ln.weight, ln.bias, ln.normalized_shape) and h.shape == x.shape
             and h.dtype == x.dtype):
         return _AddLNFn.apply(x.contiguous(), h.contiguous(), ln.weight, ln.bias, float(ln.eps))

@@ -33,7 +33,8 @@ def main():
         n = re.sub(r"\(anonymous namespace\)::", "", n)
         n = n[:n.find("(")] if "(" in n else n
         print(f"{n[:110]:110s} VGPR {r.get('VGPRs', '?'):>4} AGPR {r.get('AGPRs', '?'):>4} "
-              f"spill {r.get('VGPRs Spill', '?'):>3} LDS {r.get('LDS Size [bytes/block]', '?'):>6} "
+              f"spill {r.get('VGPRs Spill', '?'):>3} scratch {r.get('ScratchSize [bytes/lane]', '?'):>3} "
+              f"LDS {r.get('LDS Size [bytes/block]', '?'):>6} "
               f"occ {r.get('Occupancy [waves/SIMD]', '?')}")
 
 
