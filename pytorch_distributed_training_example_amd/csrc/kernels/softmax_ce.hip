@@ -8,6 +8,8 @@
 // online max / sum-exp, the target logit and the mean logit (label smoothing), and stores
 // the row's log-sum-exp. Backward recomputes softmax from the logits and LSE and writes
 // dlogits = (softmax - smoothed one-hot) * dloss in the logits' dtype.
+// -inf logits (masked vocabulary columns) are allowed off the target column when smoothing == 0:
+// they carry zero probability and zero gradient, as in F.cross_entropy.
 #include "../common.h"
 
 using namespace pdt;
@@ -31,16 +33,18 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* __restrict__ logit
 #pragma unroll
       for (int j = 1; j < 8; ++j) lm = fmaxf(lm, v[j]);
       const float nm = fmaxf(m, lm);
-      s *= __expf(m - nm);
+      const float sub = (nm == -INFINITY) ? 0.f : nm;  // all -inf so far: exp(-inf - 0) = 0, not exp(NaN)
+      s *= __expf(m - sub);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) { s += __expf(v[j] - nm); sum += v[j]; }
+      for (int j = 0; j < 8; ++j) { s += __expf(v[j] - sub); sum += v[j]; }
       m = nm;
     }
   } else {
     for (int64_t i = threadIdx.x; i < V; i += 256) {
       const float v = Elt<T>::ld(x, i);
       const float nm = fmaxf(m, v);
-      s = s * __expf(m - nm) + __expf(v - nm);
+      const float sub = (nm == -INFINITY) ? 0.f : nm;  // as above
+      s = s * __expf(m - sub) + __expf(v - sub);
       m = nm;
       sum += v;
     }
@@ -60,7 +64,8 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* __restrict__ logit
       const float xt = Elt<T>::ld(x, t);
       const float nll = lse - xt;
       const float smooth = lse - bsum / (float)V;
-      loss[row] = (1.f - smoothing) * nll + smoothing * smooth;
+      // smoothing == 0: a -inf logit (masked vocabulary column) makes `smooth` +inf, and 0 * inf is NaN
+      loss[row] = smoothing == 0.f ? nll : (1.f - smoothing) * nll + smoothing * smooth;
     }
   }
 }

@@ -83,7 +83,7 @@ def test_elementwise_dropout_ragged_tail(n):
 # ------------------------------------------------------------------ 10. fused add + LayerNorm
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
 @pytest.mark.parametrize("p", [0.1, 0.5])
-@pytest.mark.parametrize("Dm", [256, 768, 1024])
+@pytest.mark.parametrize("Dm", [256, 512, 768, 1024, 1280, 1536, 2048])
 def test_fused_dropout_add_layernorm_bitwise(Dm, p, dtype):
     D = _D()
     from pytorch_distributed_training_example_amd.ops.layernorm import LayerNorm, add_layer_norm
