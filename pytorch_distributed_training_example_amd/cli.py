@@ -45,9 +45,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--world-size", type=int, default=None, help="ranks to spawn (default: visible GPUs, 1 on CPU)")
     p.add_argument("--backend", default=None, help="nccl (RCCL) | gloo")
     p.add_argument("--loss", default=None, help="cross_entropy | nll_on_probs (reference) | prob_nll (reference loss from logits) | mse")
-    p.add_argument("--optimizer", default=None, help="adadelta | sgd | adamw | adam")
+    p.add_argument("--optimizer", default=None, help="adadelta | sgd | adamw | adam | lars | lamb")
     p.add_argument("--momentum", type=float, default=0.9)
     p.add_argument("--weight-decay", type=float, default=0.0)
+    p.add_argument("--trust-coefficient", type=float, default=0.001, help="LARS trust coefficient (--optimizer lars)")
+    p.add_argument("--layer-adapt-1d", action="store_true",
+                   help="lars / lamb: adapt and decay 1-D parameters (norm scales, biases) too; by default they "
+                        "form a second group with weight_decay 0 and no trust ratio")
     p.add_argument("--scheduler", default="step", help="step (StepLR per epoch) | cosine | none")
     p.add_argument("--precision", default="fp32", help="fp32 | bf16 | fp8 (transformer GEMMs) | amp_bf16 | amp_fp16")
     p.add_argument("--grad-accum", type=int, default=1, help="micro-batches per optimizer step (no_sync)")
@@ -183,11 +187,18 @@ def run(rank: int, world: int, args) -> dict:
     else:
         wrapped = model
     opt_kw = {}
+    opt_params = model.parameters()
     if opt_name == "sgd":
         opt_kw = dict(momentum=args.momentum, weight_decay=args.weight_decay)
     elif opt_name in ("adamw", "adam", "adadelta"):
         opt_kw = dict(weight_decay=args.weight_decay)
-    optimizer = build_optimizer(opt_name, model.parameters(), lr=args.lr, **opt_kw)
+    elif opt_name in ("lars", "lamb"):
+        from .optim import layerwise_param_groups
+        opt_kw = dict(weight_decay=args.weight_decay)
+        if opt_name == "lars":
+            opt_kw.update(momentum=args.momentum, trust_coefficient=args.trust_coefficient)
+        opt_params = layerwise_param_groups(model, args.weight_decay, skip_1d=not args.layer_adapt_1d)
+    optimizer = build_optimizer(opt_name, opt_params, lr=args.lr, **opt_kw)
     scheduler = build_scheduler(args.scheduler, optimizer, gamma=args.gamma, step_size=1,
                                 total_steps=args.epochs)
     scaler = None

@@ -22,6 +22,15 @@ int pdt_adam(int n, void* const* p, void* const* g, void* const* m, void* const*
 int pdt_adadelta(int n, void* const* p, void* const* g, void* const* sa, void* const* ad, void* const* copy,
                  const int64_t* numel, int p_dtype, int g_dtype, float lr, const float* lr_ptr, float rho, float eps,
                  float wd, int maximize, const float* inv_scale, const float* found_inf, hipStream_t s);
+int64_t pdt_layerwise_chunks(int n, const int64_t* numel);
+int pdt_lars(int n, void* const* p, void* const* g, void* const* buf, void* const* copy, const int64_t* numel,
+             int p_dtype, int g_dtype, float lr, const float* lr_ptr, float momentum, float dampening, float wd,
+             int nesterov, int first, float tc, float eps, int maximize, const float* inv_scale,
+             const float* found_inf, float* partials, double* sums, float* ratio, int norms_only, hipStream_t s);
+int pdt_lamb(int n, void* const* p, void* const* g, void* const* m, void* const* v, void* const* copy,
+             const int64_t* numel, int p_dtype, int g_dtype, float lr, const float* lr_ptr, float beta1, float beta2,
+             float eps, float wd, const float* step_ptr, float step_host, int maximize, const float* inv_scale,
+             const float* found_inf, float* partials, double* sums, float* ratio, int norms_only, hipStream_t s);
 int pdt_amp_unscale(int n, void* const* g, const int64_t* numel, int dtype, const float* inv_scale, float* found_inf,
                     hipStream_t s);
 int pdt_amp_update(float* scale, int* growth_tracker, const float* found_inf, float growth, float backoff,
@@ -403,6 +412,93 @@ void adadelta(std::vector<Tensor> params, std::vector<Tensor> grads, std::vector
                         pd, gd, (float)lr, opt_fptr(lr_t), (float)rho, (float)eps, (float)wd, maximize,
                         opt_fptr(inv_scale), opt_fptr(found_inf), stream());
   TORCH_CHECK(rc == 0, "pdt_adadelta failed");
+}
+
+// Layer-wise optimizers (kernels/layerwise.hip). The scratch belongs to the caller and is allocated once:
+// partials fp32 [>= 2 * layerwise_chunks(params)], sums fp64 [>= 2 n], ratio fp32 [>= n]; slot t belongs to
+// params[t]. All three undefined: no trust ratio (r = 1), update pass only.
+int64_t layerwise_chunks(std::vector<Tensor> params) {
+  auto ne = numels(params);
+  return pdt_layerwise_chunks((int)ne.size(), ne.data());
+}
+
+struct LayerwiseScratch {
+  float* partials = nullptr;
+  double* sums = nullptr;
+  float* ratio = nullptr;
+  LayerwiseScratch(const std::vector<Tensor>& params, const c10::optional<Tensor>& partials_t,
+                   const c10::optional<Tensor>& sums_t, const c10::optional<Tensor>& ratio_t, bool norms_only) {
+    for (const auto& p : params)
+      TORCH_CHECK(p.numel() > 0, "pdt layerwise: zero-element parameters have no trust-ratio slot; leave them out");
+    const bool has = ratio_t.has_value() && ratio_t->defined();
+    TORCH_CHECK(has || !norms_only, "pdt layerwise: norms_only needs the scratch tensors");
+    if (!has) return;
+    TORCH_CHECK(partials_t.has_value() && partials_t->defined() && sums_t.has_value() && sums_t->defined(),
+                "pdt layerwise: partials, sums and ratio come together");
+    const int64_t n = (int64_t)params.size();
+    const auto dev = params[0].device();
+    TORCH_CHECK(partials_t->is_cuda() && partials_t->device() == dev && partials_t->scalar_type() == at::kFloat &&
+                    partials_t->is_contiguous() && partials_t->numel() >= 2 * layerwise_chunks(params),
+                "pdt layerwise: partials must be fp32 [2 * chunks] on the parameters' device");
+    TORCH_CHECK(sums_t->is_cuda() && sums_t->device() == dev && sums_t->scalar_type() == at::kDouble &&
+                    sums_t->is_contiguous() && sums_t->numel() >= 2 * n,
+                "pdt layerwise: sums must be fp64 [n, 2] on the parameters' device");
+    TORCH_CHECK(ratio_t->is_cuda() && ratio_t->device() == dev && ratio_t->scalar_type() == at::kFloat &&
+                    ratio_t->is_contiguous() && ratio_t->numel() >= n,
+                "pdt layerwise: ratio must be fp32 [n] on the parameters' device");
+    partials = partials_t->data_ptr<float>();
+    sums = sums_t->data_ptr<double>();
+    ratio = ratio_t->data_ptr<float>();
+  }
+};
+
+void lars(std::vector<Tensor> params, std::vector<Tensor> grads, std::vector<Tensor> bufs,
+          std::vector<Tensor> copies, double lr, c10::optional<Tensor> lr_t, double momentum, double dampening,
+          double wd, bool nesterov, bool first, double trust_coefficient, double eps, bool maximize,
+          c10::optional<Tensor> inv_scale, c10::optional<Tensor> found_inf, c10::optional<Tensor> partials,
+          c10::optional<Tensor> sums, c10::optional<Tensor> ratio, bool norms_only) {
+  if (params.empty()) return;
+  const size_t n = params.size();
+  const int pd = uniform_dtype(params), gd = uniform_dtype(grads);
+  TORCH_CHECK(grads.size() == n, "pdt_lars: one gradient per parameter");
+  check_same_numel(params, grads, "grads");
+  check_same_numel(params, bufs, "momentum_buffer");
+  check_same_numel(params, copies, "model_copy");
+  auto P = Lists::from(params, "params", pd, n), G = Lists::from(grads, "grads", gd, n),
+       B = Lists::from(bufs, "momentum_buffer", 0, n), C = Lists::from(copies, "model_copy", 1, n);
+  LayerwiseScratch sc(params, partials, sums, ratio, norms_only);
+  auto ne = numels(params);
+  int rc = pdt_lars((int)n, P.ptrs.data(), G.ptrs.data(), B.ptrs.data(), C.ptrs.data(), ne.data(), pd, gd, (float)lr,
+                    opt_fptr(lr_t), (float)momentum, (float)dampening, (float)wd, nesterov, first,
+                    (float)trust_coefficient, (float)eps, maximize, opt_fptr(inv_scale), opt_fptr(found_inf),
+                    sc.partials, sc.sums, sc.ratio, norms_only, stream());
+  TORCH_CHECK(rc == 0, "pdt_lars failed: ", rc);
+}
+
+void lamb(std::vector<Tensor> params, std::vector<Tensor> grads, std::vector<Tensor> exp_avg,
+          std::vector<Tensor> exp_avg_sq, std::vector<Tensor> copies, double lr, c10::optional<Tensor> lr_t,
+          double beta1, double beta2, double eps, double wd, c10::optional<Tensor> step_t, double step,
+          bool maximize, c10::optional<Tensor> inv_scale, c10::optional<Tensor> found_inf,
+          c10::optional<Tensor> partials, c10::optional<Tensor> sums, c10::optional<Tensor> ratio, bool norms_only) {
+  if (params.empty()) return;
+  const size_t n = params.size();
+  const int pd = uniform_dtype(params), gd = uniform_dtype(grads);
+  TORCH_CHECK(grads.size() == n, "pdt_lamb: one gradient per parameter");
+  TORCH_CHECK(exp_avg.size() == n && exp_avg_sq.size() == n, "pdt_lamb: states required");
+  check_same_numel(params, grads, "grads");
+  check_same_numel(params, exp_avg, "exp_avg");
+  check_same_numel(params, exp_avg_sq, "exp_avg_sq");
+  check_same_numel(params, copies, "model_copy");
+  auto P = Lists::from(params, "params", pd, n), G = Lists::from(grads, "grads", gd, n),
+       M = Lists::from(exp_avg, "exp_avg", 0, n), V = Lists::from(exp_avg_sq, "exp_avg_sq", 0, n),
+       C = Lists::from(copies, "model_copy", 1, n);
+  LayerwiseScratch sc(params, partials, sums, ratio, norms_only);
+  auto ne = numels(params);
+  int rc = pdt_lamb((int)n, P.ptrs.data(), G.ptrs.data(), M.ptrs.data(), V.ptrs.data(), C.ptrs.data(), ne.data(), pd,
+                    gd, (float)lr, opt_fptr(lr_t), (float)beta1, (float)beta2, (float)eps, (float)wd,
+                    opt_fptr(step_t), (float)step, maximize, opt_fptr(inv_scale), opt_fptr(found_inf), sc.partials,
+                    sc.sums, sc.ratio, norms_only, stream());
+  TORCH_CHECK(rc == 0, "pdt_lamb failed: ", rc);
 }
 
 // ----------------------------------------------------------------------------- amp / buffers
@@ -2675,6 +2771,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sgd", &sgd);
   m.def("adam", &adam);
   m.def("adadelta", &adadelta);
+  m.def("lars", &lars);
+  m.def("lamb", &lamb);
+  m.def("layerwise_chunks", &layerwise_chunks);
   m.def("amp_unscale", &amp_unscale);
   m.def("amp_update", &amp_update);
   m.def("mt_scale", &mt_scale);
