@@ -63,7 +63,7 @@ int pdt_conv1x1_bwd_fused(const uint16_t* dy, const uint16_t* z, const uint8_t* 
                           const uint8_t* bm, const float* bmean, float* bpart, const float* xcoef, uint8_t* mask_out,
                           uint16_t* dxa, uint16_t* dw, float* ws, int M, int C4, int CW, hipStream_t s);
 void pdt_conv1x1_bwd_fused_tune(int grid);
-void pdt_bn_tune(int variant, int target_blocks, int u_fwd, int u_bwd);
+int pdt_bn_tune(int variant, int target_blocks, int u_fwd, int u_bwd);
 int pdt_bn_fwd_train(const uint16_t* x, const uint16_t* res, const float* res_a, const float* res_b,
                      const float* gamma, const float* beta,
                      float* running_mean, float* running_var, float momentum, float eps, int64_t M, int C, int relu,
@@ -2781,7 +2781,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("l2norm_sq", &l2norm_sq);
   m.def("clip_coef", &clip_coef);
   m.def("bn_tune", [](int variant, int target_blocks, int u_fwd, int u_bwd) {
-    pdt_bn_tune(variant, target_blocks, u_fwd, u_bwd);
+    if (pdt_bn_tune(variant, target_blocks, u_fwd, u_bwd) != 0)
+      throw py::value_error("bn_tune: variant must be 0 (keep), 3 (in-kernel finalize) or 5 (finalize kernel), got " +
+                            std::to_string(variant));
   }, py::arg("variant") = 0, py::arg("target_blocks") = 0, py::arg("u_fwd") = 0, py::arg("u_bwd") = 0);
   m.def("bn_fwd_train", &bn_fwd_train, py::arg("x"), py::arg("res"), py::arg("weight"), py::arg("bias"),
         py::arg("running_mean"), py::arg("running_var"), py::arg("momentum"), py::arg("eps"), py::arg("relu"),

@@ -1035,9 +1035,9 @@ struct ReduceGeo {
   int64_t rows_per_block;
 };
 
-// Reduce-kernel tuning (bn_tune): variant 3/4 = in-kernel last-arriver finalize (4: also the
-// centred second pass), 5 = separate finalize kernel; total workgroups targeted per call; rows in
-// flight per lane for the forward / backward reduce.
+// Reduce-kernel tuning (bn_tune): variant 3 = in-kernel last-arriver finalize, 5 = separate finalize
+// kernel (no other value is accepted: every reduce launch ends in exactly one of the two finalizes);
+// total workgroups targeted per call; rows in flight per lane for the forward / backward reduce.
 struct BnTune {
   int variant = 5;
   int target_blocks = 512;  // tools/bn_reduce_sweep.py: 2 workgroups per CU beat 4-16 (10.5 vs 11.5+ ms/step)
@@ -1086,7 +1086,7 @@ int64_t launch_reduce(const uint16_t* x, const uint16_t* dy, const uint8_t* mask
     const int cc = chunk3(C);
 #define PDT_R3(LPR, UU)                                                                                      \
   hipLaunchKernelGGL((bn_reduce3_kernel<MODE, LPR, UU>), dim3(g.nrow, g.nchunks), dim3(kThreads), 0, s, x, dy, \
-                     mask, mean, M, C, g.rows_per_block, g.nrow, part, gpart, counters, fa, g_tune.variant >= 4)
+                     mask, mean, M, C, g.rows_per_block, g.nrow, part, gpart, counters, fa, g_tune.variant == 5)
 #define PDT_R3U(LPR)              \
   if (U >= 8) PDT_R3(LPR, 8);     \
   else if (U >= 4) PDT_R3(LPR, 4); \
@@ -1171,11 +1171,14 @@ int64_t pdt_bn_workspace_floats(int64_t M, int C) {
 void pdt_bn_tiles_fused(int on) { g_tiles_fused = on; }
 
 // Select the reduce implementation / grid (benchmarking). Values <= 0 keep the current setting.
-void pdt_bn_tune(int variant, int target_blocks, int u_fwd, int u_bwd) {
-  if (variant >= 3 && variant <= 5) g_tune.variant = variant;
+// variant: 0 (keep), 3 or 5; anything else changes nothing and returns -1.
+int pdt_bn_tune(int variant, int target_blocks, int u_fwd, int u_bwd) {
+  if (variant != 0 && variant != 3 && variant != 5) return -1;
+  if (variant != 0) g_tune.variant = variant;
   if (target_blocks > 0) g_tune.target_blocks = target_blocks;
   if (u_fwd > 0) g_tune.u_fwd = u_fwd;
   if (u_bwd > 0) g_tune.u_bwd = u_bwd;
+  return 0;
 }
 
 // Training forward. Outputs: y (bf16), mask (uint8, M*C/8, when relu), mean/invstd (f32 [C]);

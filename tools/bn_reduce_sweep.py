@@ -23,8 +23,8 @@ SHAPES = [
     (512, 14, 1, True, False), (512, 7, 5, True, False), (2048, 7, 3, True, True), (2048, 7, 1, False, False),
 ]
 TUNINGS = [  # (variant, target_blocks, u_fwd, u_bwd)
-    (2, 512, 8, 4), (3, 512, 8, 4), (3, 512, 4, 4), (3, 512, 8, 8), (3, 512, 4, 2), (3, 1024, 8, 4),
-    (3, 1024, 4, 2), (3, 256, 8, 4), (3, 768, 4, 4), (2, 512, 8, 4),
+    (5, 512, 8, 4), (3, 512, 8, 4), (3, 512, 4, 4), (3, 512, 8, 8), (3, 512, 4, 2), (3, 1024, 8, 4),
+    (3, 1024, 4, 2), (3, 256, 8, 4), (3, 768, 4, 4), (5, 512, 8, 4),
 ]
 
 
