@@ -1,9 +1,11 @@
 """In-tree build of the gfx950 extension (``_C``) with hipcc.
 
 Each ``csrc/kernels/*.hip`` file is a standalone HIP translation unit (no PyTorch headers,
-seconds to compile) exposing C-ABI launchers; ``csrc/binding.cpp`` is the only file that
-includes the PyTorch headers. Objects are rebuilt only when their source or a shared header
-is newer, compiled in parallel, and linked into
+seconds to compile) defining C-ABI launchers; ``csrc/launchers.h`` declares them all once and
+is included by every ``.hip`` and by ``csrc/binding.cpp``, the only file that includes the
+PyTorch headers, so a launcher and its caller cannot disagree on a parameter list. Objects
+(``binding.o`` included) are rebuilt only when their source or a shared header is newer,
+compiled in parallel, and linked into
 ``pytorch_distributed_training_example_amd/_C.<abi>.so`` next to this file, so the built
 library travels with the repository snapshot to the GPU box (no JIT cache).
 
@@ -71,7 +73,7 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False) -
     bsrc = os.path.join(CSRC, "binding.cpp")
     bobj = os.path.join(BUILD, "binding.o")
     objs.append(bobj)
-    if force or _stale(bobj, bsrc, []):
+    if force or _stale(bobj, bsrc, hdrs):
         inc = sum([["-I", d] for d in torch_inc + [py_inc]], [])
         jobs_list.append((bobj, [HIPCC, *common, *inc, "-DTORCH_EXTENSION_NAME=_C", "-DTORCH_API_INCLUDE_EXTENSION_H",
                                  "-D_GLIBCXX_USE_CXX11_ABI=1", "-DUSE_ROCM=1", "-c", bsrc, "-o", bobj]))

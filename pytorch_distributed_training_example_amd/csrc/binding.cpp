@@ -11,281 +11,8 @@
 #include <map>
 #include <vector>
 
-extern "C" {
-int pdt_sgd(int n, void* const* p, void* const* g, void* const* buf, void* const* copy, const int64_t* numel,
-            int p_dtype, int g_dtype, float lr, const float* lr_ptr, float momentum, float dampening, float wd,
-            int nesterov, int first, int maximize, const float* inv_scale, const float* found_inf, hipStream_t s);
-int pdt_adam(int n, void* const* p, void* const* g, void* const* m, void* const* v, void* const* copy,
-             const int64_t* numel, int p_dtype, int g_dtype, float lr, const float* lr_ptr, float beta1, float beta2,
-             float eps, float wd, int decoupled, const float* step_ptr, float step_host, int maximize,
-             const float* inv_scale, const float* found_inf, hipStream_t s);
-int pdt_adadelta(int n, void* const* p, void* const* g, void* const* sa, void* const* ad, void* const* copy,
-                 const int64_t* numel, int p_dtype, int g_dtype, float lr, const float* lr_ptr, float rho, float eps,
-                 float wd, int maximize, const float* inv_scale, const float* found_inf, hipStream_t s);
-int64_t pdt_layerwise_chunks(int n, const int64_t* numel);
-int pdt_lars(int n, void* const* p, void* const* g, void* const* buf, void* const* copy, const int64_t* numel,
-             int p_dtype, int g_dtype, float lr, const float* lr_ptr, float momentum, float dampening, float wd,
-             int nesterov, int first, float tc, float eps, int maximize, const float* inv_scale,
-             const float* found_inf, float* partials, double* sums, float* ratio, int norms_only, hipStream_t s);
-int pdt_lamb(int n, void* const* p, void* const* g, void* const* m, void* const* v, void* const* copy,
-             const int64_t* numel, int p_dtype, int g_dtype, float lr, const float* lr_ptr, float beta1, float beta2,
-             float eps, float wd, const float* step_ptr, float step_host, int maximize, const float* inv_scale,
-             const float* found_inf, float* partials, double* sums, float* ratio, int norms_only, hipStream_t s);
-int pdt_amp_unscale(int n, void* const* g, const int64_t* numel, int dtype, const float* inv_scale, float* found_inf,
-                    hipStream_t s);
-int pdt_amp_update(float* scale, int* growth_tracker, const float* found_inf, float growth, float backoff,
-                   int interval, hipStream_t s);
-int pdt_mt_scale(int n, void* const* x, const int64_t* numel, int dtype, const float* scale_ptr, float scale,
-                 hipStream_t s);
-int pdt_mt_copy(int n, void* const* src, void* const* dst, const int64_t* numel, int sdt, int ddt,
-                const float* scale_ptr, float scale, hipStream_t s);
-int pdt_l2norm_sq(int n, void* const* x, const int64_t* numel, int dtype, float* out, hipStream_t s);
-int pdt_clip_coef(const float* sumsq, float max_norm, float* coef, float* norm, hipStream_t s);
-int64_t pdt_bn_workspace_floats(int64_t M, int C);
-int pdt_lenet_tail_fwd(const float* p1, const float* w2, const float* b2, const float* w3, const float* b3,
-                       const float* fw1, const float* fb1, const float* fw2, const float* fb2, float slope, int N,
-                       float* logits, uint8_t* code2, float* p2, float* h3, float* h4, hipStream_t s);
-int64_t pdt_lenet_tail_ws_floats(int N);
-int pdt_lenet_tail_bwd(const float* dl, const float* p1, const float* w2, const float* b2, const float* w3,
-                       const float* b3, const float* fw1, const float* fb1, const float* fw2, const float* fb2,
-                       float slope, int N, const uint8_t* code2, const float* p2, const float* h3, const float* h4,
-                       float* ws, float* dp1, float* dw2, float* db2, float* dw3, float* db3, float* dfw1, float* dfb1,
-                       float* dfw2, float* dfb2, hipStream_t s);
-int pdt_bn_bwd_coef(const uint16_t* dy, const uint16_t* x, const uint8_t* mask, const float* gamma, const float* mean,
-                    const float* invstd, int64_t M, int C, int relu, float* coef, float* dgamma, float* dbeta, float* ws,
-                    unsigned* counters, hipStream_t s);
-int pdt_bn_bwd_coef_tiles(const float* part, int T, const float* gamma, const float* invstd, int64_t M, int C,
-                          float* coef, float* dgamma, float* dbeta, float* ws, hipStream_t s);
-int pdt_conv1x1_bwd_fused_ok(int C4, int CW);
-int pdt_conv1x1_bwd_fused_grid(int M, int C4, int CW);
-int pdt_conv1x1_bwd_fused(const uint16_t* dy, const uint16_t* z, const uint8_t* mz, const float* mean, const float* A,
-                          const float* B, const float* D, const uint16_t* wt, const uint16_t* xa, const uint16_t* bx,
-                          const uint8_t* bm, const float* bmean, float* bpart, const float* xcoef, uint8_t* mask_out,
-                          uint16_t* dxa, uint16_t* dw, float* ws, int M, int C4, int CW, hipStream_t s);
-void pdt_conv1x1_bwd_fused_tune(int grid);
-int pdt_bn_tune(int variant, int target_blocks, int u_fwd, int u_bwd);
-int pdt_bn_fwd_train(const uint16_t* x, const uint16_t* res, const float* res_a, const float* res_b,
-                     const float* gamma, const float* beta,
-                     float* running_mean, float* running_var, float momentum, float eps, int64_t M, int C, int relu,
-                     uint16_t* y, uint8_t* mask, float* mean, float* invstd, float* ws, unsigned* counters,
-                     hipStream_t s);
-int pdt_bn_fwd_eval(const uint16_t* x, const uint16_t* res, const float* gamma, const float* beta,
-                    const float* running_mean, const float* running_var, float eps, int64_t M, int C, int relu,
-                    uint16_t* y, float* ws, hipStream_t s);
-int pdt_bn_bwd_train(const uint16_t* dy, const uint16_t* x, const uint8_t* mask, const float* gamma,
-                     const float* mean, const float* invstd, int64_t M, int C, int relu, int has_res, uint16_t* dx,
-                     uint16_t* dres, float* dgamma, float* dbeta, float* ws, unsigned* counters, hipStream_t s);
-int pdt_bn_sync_fwd_stats(const uint16_t* x, int64_t M, int C, float* stats, float* count, float* ws,
-                          unsigned* counters, hipStream_t s);
-int pdt_bn_sync_fwd_merge(const float* gathered, int W, int C, const float* gamma, const float* beta,
-                          float* running_mean, float* running_var, float momentum, float eps, float* mean,
-                          float* invstd, float* ab, int64_t* ntot, hipStream_t s);
-int pdt_bn_apply_coef(const uint16_t* x, const uint16_t* res, const float* ab, int64_t M, int C, int relu,
-                      uint16_t* y, uint8_t* mask, hipStream_t s);
-int pdt_bn_sync_bwd_sums(const uint16_t* dy, const uint16_t* x, const uint8_t* mask, const float* mean, int64_t M,
-                         int C, int relu, float* sums, float* ws, unsigned* counters, hipStream_t s);
-int pdt_bn_sync_bwd_merge(const float* gathered, int W, int rank, int C, const float* gamma, const float* invstd,
-                          const int64_t* ntot, float* coef, float* dgamma, float* dbeta, hipStream_t s);
-int pdt_bn_bwd_apply_coef(const uint16_t* dy, const uint16_t* x, const uint8_t* mask, const float* mean,
-                          const float* coef, int64_t M, int C, int relu, int has_res, uint16_t* dx, uint16_t* dres,
-                          hipStream_t s);
-int pdt_ce_fwd(const void* logits, int dtype, const int64_t* target, int64_t N, int64_t V, float smoothing,
-               int64_t ignore_index, float* loss, float* lse, hipStream_t s);
-int pdt_ce_bwd(const void* logits, int dtype, const int64_t* target, const float* lse, const float* dloss,
-               float dloss_scale, int64_t N, int64_t V, float smoothing, int64_t ignore_index, void* dlogits,
-               hipStream_t s);
-int64_t pdt_ln_workspace_floats(int64_t N, int D);
-int pdt_ln_fwd(const void* x, const void* res, int dtype, const float* w, const float* b, void* y, void* sum_out,
-               float* mean, float* rstd, int64_t N, int D, float eps, hipStream_t s);
-int pdt_ln_fwd_fp8(const uint16_t* x, const uint16_t* res, const float* w, const float* b, uint16_t* sum_out,
-                   uint8_t* yq, uint8_t* yqt, float* mean, float* rstd, int64_t N, int D, float eps,
-                   const float* scale, float* amax, int striped, hipStream_t s);
-int pdt_ln_bwd(const void* dy, const void* x, const void* dres, int dtype, const float* w, const float* mean,
-               const float* rstd, void* dx, float* dw, float* db, int64_t N, int D, float* ws, hipStream_t s);
-int pdt_attn_fwd(const uint16_t* q, const int64_t* qs, const uint16_t* k, const int64_t* ks, const uint16_t* v,
-                 const int64_t* vs, uint16_t* o, const int64_t* os, float* lse, int B, int H, int T, int Dh,
-                 int causal, float scale, hipStream_t s);
-int pdt_attn_bwd(const uint16_t* dout, const int64_t* dos, const uint16_t* q, const int64_t* qs, const uint16_t* k,
-                 const int64_t* ks, const uint16_t* v, const int64_t* vs, const uint16_t* o, const int64_t* os,
-                 const float* lse, float* delta, uint16_t* dq, uint16_t* dk, uint16_t* dv, const int64_t* gs, int B,
-                 int H, int T, int Dh, int causal, float scale, hipStream_t s);
-int pdt_dropout_begin(int64_t* state, int64_t* ticket, hipStream_t s);
-int pdt_dropout(const void* x, void* y, int dtype, int64_t n, const int64_t* ticket, int stream, int thr,
-                hipStream_t s);
-int pdt_dropout_mask_flat(uint8_t* out, int64_t n, const int64_t* ticket, int stream, int thr, hipStream_t s);
-int pdt_dropout_mask_attn(uint8_t* out, int64_t BH, int T, const int64_t* ticket, int stream, int thr,
-                          hipStream_t s);
-int pdt_ln_fwd_drop(const void* x, const void* res, int dtype, const float* w, const float* b, void* y,
-                    void* sum_out, float* mean, float* rstd, int64_t N, int D, float eps, const int64_t* ticket,
-                    int dstream, int thr, hipStream_t s);
-int pdt_ln_bwd_drop(const void* dy, const void* x, const void* dres, int dtype, const float* w, const float* mean,
-                    const float* rstd, void* dx, void* dh, float* dw, float* db, int64_t N, int D, float* ws,
-                    const int64_t* ticket, int dstream, int thr, hipStream_t s);
-int pdt_attn_fwd_drop(const uint16_t* q, const int64_t* qs, const uint16_t* k, const int64_t* ks, const uint16_t* v,
-                      const int64_t* vs, uint16_t* o, const int64_t* os, float* lse, int B, int H, int T, int Dh,
-                      int causal, float scale, const int64_t* ticket, int dstream, int thr, hipStream_t s);
-int pdt_attn_bwd_drop(const uint16_t* dout, const int64_t* dos, const uint16_t* q, const int64_t* qs,
-                      const uint16_t* k, const int64_t* ks, const uint16_t* v, const int64_t* vs, const uint16_t* o,
-                      const int64_t* os, const float* lse, float* delta, uint16_t* dq, uint16_t* dk, uint16_t* dv,
-                      const int64_t* gs, int B, int H, int T, int Dh, int causal, float scale, const int64_t* ticket,
-                      int dstream, int thr, hipStream_t s);
-int64_t pdt_gelu_workspace_floats(int64_t N, int D);
-int pdt_bias_gelu_fwd(const void* x, int dtype, const void* bias, void* y, int64_t N, int D, int tanh_form,
-                      hipStream_t s, int bias_bf16);
-int pdt_bias_gelu_bwd(const void* dy, const void* x, int dtype, const void* bias, void* dx, void* dbias,
-                      int64_t N, int D, int tanh_form, float* ws, hipStream_t s, int bias_bf16);
-int pdt_bn_relu_maxpool_fwd_train(const uint16_t* x, const float* gamma, const float* beta, float* running_mean,
-                                  float* running_var, float momentum, float eps, int N, int H, int W, int C,
-                                  uint16_t* y, uint8_t* code, float* mean, float* invstd, float* ws,
-                                  unsigned* counters, hipStream_t s);
-int pdt_conv3x3s1_fwd(const uint16_t* x, const uint16_t* w, uint16_t* y, int N, int H, int W, int Ci, int Co,
-                      hipStream_t s);
-int pdt_conv3x3_flip_weights(const uint16_t* w, uint16_t* wf, int Co, int Ci, hipStream_t s);
-int64_t pdt_conv3x3_wgrad_ws_floats(int N, int H, int W, int Ci, int Co, int* nsplit_out);
-int pdt_conv3x3s1_wgrad(const uint16_t* x, const uint16_t* dy, uint16_t* dw, float* ws, int N, int H, int W, int Ci,
-                        int Co, hipStream_t s);
-void pdt_conv3x3_wgrad_tune(int target_wgs, int co_tile);
-int pdt_conv3x3s1_fwd_bnbwd(const uint16_t* x, const uint16_t* w, uint16_t* y, const uint16_t* bn_x,
-                            const uint8_t* bn_mask, const float* bn_mean, float* bn_part, int N, int H, int W, int Ci,
-                            int Co, hipStream_t s);
-int pdt_conv3x3s2_fwd(const uint16_t* x, const uint16_t* w, uint16_t* y, float* part, int N, int H, int W, int Ci,
-                      int Co, hipStream_t s);
-int pdt_conv3x3s2_dgrad(const uint16_t* dy, const uint16_t* wf, uint16_t* dx, const uint16_t* bn_x,
-                        const uint8_t* bn_mask, const float* bn_mean, float* bn_part, int N, int H, int W, int Ci,
-                        int Co, hipStream_t s);
-int pdt_conv3x3s2_dgrad_tiles(int N, int H, int W);
-int64_t pdt_conv3x3s2_wgrad_ws_floats(int N, int H, int W, int Ci, int Co, int* nsplit_out);
-int pdt_conv3x3s2_wgrad(const uint16_t* x, const uint16_t* dy, uint16_t* dw, float* ws, int N, int H, int W, int Ci,
-                        int Co, hipStream_t s);
-int pdt_conv3x3s1_fwd_stats(const uint16_t* x, const uint16_t* w, uint16_t* y, float* part, int N, int H, int W,
-                            int Ci, int Co, hipStream_t s);
-int64_t pdt_stem_conv_wprep_elems();
-int64_t pdt_stem_stats_parts(int N, int H, int W);
-int pdt_stem_conv_fwd_stats(const uint16_t* x, const uint16_t* w, uint16_t* wp, uint16_t* y, float* part, int N, int H,
-                            int W, hipStream_t s);
-int64_t pdt_bn_parts_ws_floats(int P, int C);
-int pdt_bn_relu_maxpool_fwd_train_parts(const float* part, int P, const uint16_t* x, const float* gamma,
-                                        const float* beta, float* running_mean, float* running_var, float momentum,
-                                        float eps, int N, int H, int W, int C, uint16_t* y, uint8_t* code, float* mean,
-                                        float* invstd, float* ws, hipStream_t s);
-int pdt_stem_conv_fwd(const uint16_t* x, const uint16_t* w, uint16_t* wp, uint16_t* y, int N, int H, int W,
-                      hipStream_t s);
-int64_t pdt_stem_wgrad_ws_floats();
-int pdt_stem_conv_wgrad(const uint16_t* x, const uint16_t* dy, uint16_t* dw, float* ws, int N, int H, int W,
-                        hipStream_t s);
-int pdt_stem_conv_wgrad_bn_pool(const uint16_t* x, const uint16_t* dyp, const uint8_t* code, const uint16_t* xb,
-                                const float* coef, const float* mean, uint16_t* dw, float* ws, int N, int H, int W,
-                                hipStream_t s);
-int pdt_stem_conv_wgrad_bn(const uint16_t* x, const uint16_t* dz, const uint16_t* xb, const float* coef,
-                           const float* mean, uint16_t* dw, float* ws, int N, int H, int W, hipStream_t s);
-int pdt_maxpool3s2_bwd(const uint16_t* dy, const uint8_t* code, uint16_t* dz, int N, int H, int W, int C,
-                       hipStream_t s);
-int pdt_conv1x1_tile_rows();
-int64_t pdt_conv1x1_wgrad_ws_floats(int M, int Ci, int Co, int* nsplit_out);
-int64_t pdt_conv1x1_wgrad_seg_ws_floats(int M, int Ci, int co1, int co2, int* rows_out);
-int pdt_conv1x1_wgrad_seg(const uint16_t* x, const uint16_t* dy1, int co1, const uint16_t* dy2, int co2, float* out,
-                          float* ws, int M, int Ci, hipStream_t s);
-int pdt_conv1x1_gemm_seg(const uint16_t* a1, int k1, const uint16_t* a2, int k2, int rep2, const uint16_t* b,
-                         uint16_t* y, int M, int N, const uint16_t* bn_x, const uint8_t* bn_mask, const float* bn_mean,
-                         float* bn_part, hipStream_t s);
-int pdt_bn_alg_fix_s2(float* part, int T, const float* wg, const uint16_t* W, int C4, int CW, hipStream_t s);
-int pdt_bn_alg_ds_part(float* part, const float* s1, const float* mean, const float* wg, const uint16_t* W, int C4,
-                       int CW, hipStream_t s);
-int pdt_bn_alg_small_gemm(const uint16_t* W, const uint16_t* Wt, const float* coef, const float* wg, float* G,
-                          float* BWG, int C4, int CW, hipStream_t s);
-int pdt_bn_alg_assemble(const uint16_t* W, const float* coef, const float* mean, const float* G, const float* wg,
-                        const float* BWG, uint16_t* bcat, uint16_t* dW, int C4, int CW, int rep, hipStream_t s);
-int pdt_conv1x1_wgrad(const uint16_t* x, const uint16_t* dy, uint16_t* dw, float* ws, int M, int Ci, int Co,
-                      hipStream_t s);
-void pdt_conv1x1_wgrad_tune(int target_wgs, int variant, int interleave);
-int pdt_conv1x1_gemm(const uint16_t* a, const uint16_t* b, uint16_t* y, const uint16_t* c, const uint8_t* cm,
-                     float* part, int M, int K, int N, const uint16_t* bn_x, const uint8_t* bn_mask,
-                     const float* bn_mean, float* bn_part, int c_s, int c_H, int c_W, const float* acoef,
-                     hipStream_t s, int nostore);
-void pdt_conv1x1_probe(int probe);
-int pdt_conv1x1_persist(int mode);
-int pdt_conv1x1_last_persistent();
-int pdt_conv3x3_opt(int v);
-int pdt_conv3x3s1_stats_tile_rows(int N, int H, int W, int Ci, int Co);
-int pdt_conv3x3s1_bnbwd_tile_rows(int N, int H, int W, int Ci, int Co);
-void pdt_bn_tiles_fused(int on);
-void pdt_maxpool_bwd_v2(int on);
-void pdt_pool_fwd_contig(int on);
-void pdt_bn_apply_wgs(int n);
-void pdt_bn_row_wgs(int n);
-int pdt_gap_bwd_parts(int64_t M, int C);
-int pdt_gap_bwd(const uint16_t* g, int N, int HW, int C, uint16_t* dy, const uint16_t* xb, const uint8_t* mask,
-                const float* mean, float* part, hipStream_t s);
-int pdt_weight_prep_max_items();
-int pdt_weight_prep(const uint16_t* const* src, uint16_t* const* dst, const int* R, const int* C, const int* taps,
-                    int n, hipStream_t s);
-int pdt_conv1x1_gemm_apply(const uint16_t* a, const uint16_t* b, uint16_t* y, const uint16_t* res, const float* ab,
-                           const float* rab, uint8_t* mask, int M, int K, int N, const float* acoef, hipStream_t s);
-int pdt_maxpool_bn_parts(int N, int H);
-int pdt_maxpool3s2_bwd_bn(const uint16_t* dy, const uint8_t* code, uint16_t* dz, int N, int H, int W, int C,
-                          const uint16_t* x, const float* gamma, const float* mean, const float* invstd, uint16_t* dx,
-                          float* dgamma, float* dbeta, float* part, float* ws, hipStream_t s);
-int pdt_maxpool3s2_bwd_bn_coef(const uint16_t* dy, const uint8_t* code, uint16_t* dz, int N, int H, int W, int C,
-                               const uint16_t* x, const float* gamma, const float* mean, const float* invstd,
-                               float* coef, float* dgamma, float* dbeta, float* part, float* ws, hipStream_t s);
-int pdt_bn_bwd_train_tiles(const float* part, int T, int BMt, const uint16_t* dy, const uint16_t* x,
-                           const uint8_t* mask, const float* gamma, const float* mean, const float* invstd, int64_t M,
-                           int C, int relu, int has_res, uint16_t* dx, uint16_t* dres, float* dgamma, float* dbeta,
-                           float* ws, hipStream_t s);
-int64_t pdt_bn_tiles_ws_floats(int T, int C);
-int pdt_bn_fwd_train_tiles(const float* part, int T, int BMt, const uint16_t* x, const uint16_t* res,
-                           const float* res_a, const float* res_b,
-                           const float* gamma, const float* beta, float* running_mean, float* running_var,
-                           float momentum, float eps, int64_t M, int C, int relu, uint16_t* y, uint8_t* mask,
-                           float* mean, float* invstd, float* ws, hipStream_t s, uint16_t* sub_y, int sub_H,
-                           int sub_W, int sub_s);
-int pdt_fp8_cast_transpose(const uint16_t* x, int64_t M, int64_t K, const float* scale, uint8_t* out,
-                           uint8_t* out_t, float* amax, int striped, hipStream_t s);
-int pdt_fp8_update_scales(float* state, int n, int L, float margin_scale, int striped, hipStream_t s);
-// fp8 state rows of at least this many floats carry 16 amax stripes (csrc/fp8_pack.h kAmaxRowMin)
-constexpr int64_t kFp8StripedRow = 261;
-inline int fp8_striped(const at::Tensor& row) { return row.numel() >= kFp8StripedRow ? 1 : 0; }
-int64_t pdt_fp8_gelu_cast_workspace_floats(int64_t M, int D);
-int pdt_fp8_gelu_cast(const uint16_t* h, const uint16_t* dg, const float* bias, int64_t M, int D, int tanh_form,
-                      const float* scale, uint8_t* out, uint8_t* out_t, float* amax, float* part, int striped,
-                      hipStream_t s);
-int pdt_fp8_cast_multi(int n, const uint16_t* const* x, const int* M, const int* K, float* const* st,
-                       const int* striped, uint8_t* const* out, uint8_t* const* out_t, hipStream_t s);
-int pdt_colsum_finalize(const float* part, int nblk, int D, void* out, int odtype, hipStream_t s);
-int pdt_fp8_cast_colsum(const uint16_t* x, int64_t M, int D, const float* scale, uint8_t* out, uint8_t* out_t,
-                        float* amax, float* part, int striped, hipStream_t s);
-int pdt_embedding_fwd(const int64_t* idx, const uint16_t* wte, const uint16_t* wpe, uint16_t* out, int64_t n, int T,
-                      int D, int V, int* err, hipStream_t s);
-int64_t pdt_embedding_bwd_ws_ints(int64_t n, int V);
-int pdt_gemm_nt(const uint16_t* A, const uint16_t* B, uint16_t* C, uint16_t* G, const void* bias, int bias_f32,
-                int epi, int tanh_form, int M, int N, int K, hipStream_t s);
-int pdt_gemm_nt_fp8_ksplit(int M, int N, int K);
-int pdt_gemm_nt_fp8(const uint8_t* A, const uint8_t* B, uint16_t* C, const float* sa, const float* sb,
-                    const void* bias, int bias_f32, int epi, int M, int N, int K, float* ws, int ksplit, hipStream_t s);
-int pdt_embedding_bwd(const int64_t* idx, const uint16_t* dout, uint16_t* dwte, uint16_t* dwpe, int* ws, int64_t n,
-                      int B, int T, int V, int D, int* err, hipStream_t s);
-int64_t pdt_p2p_flags_bytes();
-int64_t pdt_p2p_data_bytes(int64_t cap);
-int pdt_p2p_allreduce(const void* in, void* out, int64_t n, int dtype, char* const* data_ptrs,
-                      uint32_t* const* flag_ptrs, int rank, int world, int64_t cap, float post_scale,
-                      uint32_t* st, int algo, int max_blocks, double timeout_s, hipStream_t s);
-int pdt_colsum(const void* x, int dtype, int64_t N, int D, void* out, int odtype, float* ws, hipStream_t s);
-int pdt_slice_sum_bf16(const uint16_t* x, uint16_t* out, int S, int64_t n, hipStream_t s);
-int pdt_subsample_gather(const uint16_t* x, uint16_t* xs, int N, int H, int W, int C, int s, hipStream_t st);
-int pdt_subsample_scatter_add(const uint16_t* t, uint16_t* full, int N, int H, int W, int C, int s, hipStream_t st);
-int pdt_lenet_stem_fwd(const float* x, const float* w, const float* b, int64_t N, float slope, float* y,
-                       uint8_t* code, hipStream_t s);
-int64_t pdt_lenet_stem_slab_floats(int64_t N, int ipb);
-int pdt_lenet_stem_bwd(const float* dy, const uint8_t* code, const float* x, int64_t N, int ipb, float slope,
-                       float* slab, float* dw, float* db, hipStream_t s);
-int pdt_leaky_pool_fwd(const float* x, int64_t planes, int H, int W, float slope, float* y, uint8_t* code,
-                       hipStream_t s);
-int pdt_leaky_pool_bwd(const float* dy, const uint8_t* code, int64_t planes, int H, int W, float slope, float* dx,
-                       hipStream_t s);
-int pdt_softmax_nll_small(const void* logits, int dtype, const int64_t* target, int64_t N, int V, int mode,
-                          float smoothing, float* loss, void* dlogits, float dscale, double* acc, hipStream_t s);
-int pdt_mean_small(const float* v, int64_t n, float scale, float* out, hipStream_t s);
-}
+#include "fp8_pack.h"
+#include "launchers.h"
 
 namespace {
 
@@ -305,15 +32,70 @@ void check_cuda(const Tensor& t, const char* name) {
 
 bool dense(const Tensor& t) { return t.is_contiguous() || t.is_non_overlapping_and_dense(); }
 
-const float* opt_fptr(const c10::optional<Tensor>& t) {
-  if (!t.has_value() || !t->defined()) return nullptr;
-  TORCH_CHECK(t->scalar_type() == at::kFloat, "pdt: scalar tensors must be fp32");
+// ----------------------------------------------------------------------------- checks and pointer accessors
+// The vocabulary every binding below is written in. A binding reads: checks, allocate, pdt_x(...), check rc.
+bool has(const c10::optional<Tensor>& t) { return t.has_value() && t->defined(); }
+
+// The only casts of a tensor's storage to the launchers' element types: bf16 travels as uint16_t, fp8 and
+// bool as uint8_t. bf16_ptr for operands, bf16_out for results.
+uint16_t* bf16_out(const Tensor& t) { return static_cast<uint16_t*>(t.data_ptr()); }
+const uint16_t* bf16_ptr(const Tensor& t) { return bf16_out(t); }
+uint8_t* byte_ptr(const Tensor& t) { return static_cast<uint8_t*>(t.data_ptr()); }
+
+// An optional output (allocated or left undefined by the binding): its pointer, or nullptr.
+template <class T>
+T* ptr_or_null(const Tensor& t) {
+  return t.defined() ? t.data_ptr<T>() : nullptr;
+}
+template <>
+uint16_t* ptr_or_null<uint16_t>(const Tensor& t) {
+  return t.defined() ? bf16_out(t) : nullptr;
+}
+
+// An op's name, for the error text, and the device of its first tensor: every tensor whose raw pointer
+// goes to the launcher has to live there (the launch runs on that device's current stream).
+struct Op {
+  const char* name;
+  c10::Device dev;
+  Op(const char* name, const Tensor& first) : name(name), dev(first.device()) {
+    TORCH_CHECK(first.is_cuda(), name, ": the first tensor must be a GPU tensor");
+  }
+};
+
+void check_flat(const Op& op, const char* name, const Tensor& t, at::ScalarType dtype, int64_t numel) {
+  TORCH_CHECK(t.defined() && t.scalar_type() == dtype && t.is_contiguous() && t.numel() == numel &&
+                  t.device() == op.dev,
+              op.name, ": ", name, " must be a contiguous ", dtype, " tensor of ", numel, " elements on ", op.dev);
+}
+
+float* f32_ptr(const Op& op, const char* name, const Tensor& t, int64_t numel) {
+  check_flat(op, name, t, at::kFloat, numel);
+  return t.data_ptr<float>();
+}
+uint8_t* u8_ptr(const Op& op, const char* name, const Tensor& t, int64_t numel) {
+  check_flat(op, name, t, at::kByte, numel);
+  return t.data_ptr<uint8_t>();
+}
+float* opt_f32_ptr(const Op& op, const char* name, const c10::optional<Tensor>& t, int64_t numel) {
+  return has(t) ? f32_ptr(op, name, *t, numel) : nullptr;
+}
+uint8_t* opt_u8_ptr(const Op& op, const char* name, const c10::optional<Tensor>& t, int64_t numel) {
+  return has(t) ? u8_ptr(op, name, *t, numel) : nullptr;
+}
+// fp8 state rows (ops/fp8.py Fp8State) of at least pdt::kAmaxRowMin floats carry the 16 amax stripes.
+int fp8_striped(const Tensor& row) { return row.numel() >= pdt::kAmaxRowMin ? 1 : 0; }
+
+// A device-side scalar (learning rate, loss scale, step count): the kernel reads element 0.
+const float* opt_scalar_ptr(const Op& op, const char* name, const c10::optional<Tensor>& t) {
+  if (!has(t)) return nullptr;
+  TORCH_CHECK(t->scalar_type() == at::kFloat && t->numel() >= 1 && t->device() == op.dev, op.name, ": ", name,
+              " must be an fp32 tensor on ", op.dev);
   return t->data_ptr<float>();
 }
 
 struct Lists {
   std::vector<void*> ptrs;
-  static Lists from(const std::vector<Tensor>& ts, const char* name, int expect_dtype, size_t n) {
+  static Lists from(const Op& op, const std::vector<Tensor>& ts, const char* name, int expect_dtype, size_t n) {
     Lists l;
     if (ts.empty()) {
       l.ptrs.assign(n, nullptr);
@@ -321,7 +103,7 @@ struct Lists {
     }
     TORCH_CHECK(ts.size() == n, "pdt: list ", name, " has ", ts.size(), " tensors, expected ", n);
     for (const auto& t : ts) {
-      check_cuda(t, name);
+      TORCH_CHECK(t.device() == op.dev, op.name, ": ", name, " tensors must be on ", op.dev);
       TORCH_CHECK(dense(t), "pdt: ", name, " tensors must be dense");
       if (expect_dtype >= 0) TORCH_CHECK(dcode(t) == expect_dtype, "pdt: ", name, " dtype mismatch");
       l.ptrs.push_back(t.data_ptr());
@@ -357,17 +139,19 @@ void sgd(std::vector<Tensor> params, std::vector<Tensor> grads, std::vector<Tens
          double wd, bool nesterov, bool first, bool maximize, c10::optional<Tensor> inv_scale,
          c10::optional<Tensor> found_inf) {
   if (params.empty()) return;
+  const Op op("sgd", params[0]);
   const size_t n = params.size();
   const int pd = uniform_dtype(params), gd = uniform_dtype(grads);
   check_same_numel(params, grads, "grads");
   check_same_numel(params, bufs, "momentum_buffer");
   check_same_numel(params, copies, "model_copy");
-  auto P = Lists::from(params, "params", pd, n), G = Lists::from(grads, "grads", gd, n),
-       B = Lists::from(bufs, "momentum_buffer", 0, n), C = Lists::from(copies, "model_copy", 1, n);
+  auto P = Lists::from(op, params, "params", pd, n), G = Lists::from(op, grads, "grads", gd, n),
+       B = Lists::from(op, bufs, "momentum_buffer", 0, n), C = Lists::from(op, copies, "model_copy", 1, n);
   auto ne = numels(params);
   int rc = pdt_sgd((int)n, P.ptrs.data(), G.ptrs.data(), B.ptrs.data(), C.ptrs.data(), ne.data(), pd, gd, (float)lr,
-                   opt_fptr(lr_t), (float)momentum, (float)dampening, (float)wd, nesterov, first, maximize,
-                   opt_fptr(inv_scale), opt_fptr(found_inf), stream());
+                   opt_scalar_ptr(op, "lr_t", lr_t), (float)momentum, (float)dampening, (float)wd, nesterov, first,
+                   maximize, opt_scalar_ptr(op, "inv_scale", inv_scale), opt_scalar_ptr(op, "found_inf", found_inf),
+                   stream());
   TORCH_CHECK(rc == 0, "pdt_sgd failed");
 }
 
@@ -376,6 +160,7 @@ void adam(std::vector<Tensor> params, std::vector<Tensor> grads, std::vector<Ten
           double beta1, double beta2, double eps, double wd, bool decoupled, c10::optional<Tensor> step_t,
           double step, bool maximize, c10::optional<Tensor> inv_scale, c10::optional<Tensor> found_inf) {
   if (params.empty()) return;
+  const Op op("adam", params[0]);
   const size_t n = params.size();
   const int pd = uniform_dtype(params), gd = uniform_dtype(grads);
   check_same_numel(params, grads, "grads");
@@ -383,13 +168,14 @@ void adam(std::vector<Tensor> params, std::vector<Tensor> grads, std::vector<Ten
   check_same_numel(params, exp_avg_sq, "exp_avg_sq");
   check_same_numel(params, copies, "model_copy");
   TORCH_CHECK(!exp_avg.empty() && !exp_avg_sq.empty(), "pdt_adam: states required");
-  auto P = Lists::from(params, "params", pd, n), G = Lists::from(grads, "grads", gd, n),
-       M = Lists::from(exp_avg, "exp_avg", 0, n), V = Lists::from(exp_avg_sq, "exp_avg_sq", 0, n),
-       C = Lists::from(copies, "model_copy", 1, n);
+  auto P = Lists::from(op, params, "params", pd, n), G = Lists::from(op, grads, "grads", gd, n),
+       M = Lists::from(op, exp_avg, "exp_avg", 0, n), V = Lists::from(op, exp_avg_sq, "exp_avg_sq", 0, n),
+       C = Lists::from(op, copies, "model_copy", 1, n);
   auto ne = numels(params);
   int rc = pdt_adam((int)n, P.ptrs.data(), G.ptrs.data(), M.ptrs.data(), V.ptrs.data(), C.ptrs.data(), ne.data(), pd,
-                    gd, (float)lr, opt_fptr(lr_t), (float)beta1, (float)beta2, (float)eps, (float)wd, decoupled,
-                    opt_fptr(step_t), (float)step, maximize, opt_fptr(inv_scale), opt_fptr(found_inf), stream());
+                    gd, (float)lr, opt_scalar_ptr(op, "lr_t", lr_t), (float)beta1, (float)beta2, (float)eps, (float)wd,
+                    decoupled, opt_scalar_ptr(op, "step_t", step_t), (float)step, maximize,
+                    opt_scalar_ptr(op, "inv_scale", inv_scale), opt_scalar_ptr(op, "found_inf", found_inf), stream());
   TORCH_CHECK(rc == 0, "pdt_adam failed");
 }
 
@@ -398,19 +184,21 @@ void adadelta(std::vector<Tensor> params, std::vector<Tensor> grads, std::vector
               double rho, double eps, double wd, bool maximize, c10::optional<Tensor> inv_scale,
               c10::optional<Tensor> found_inf) {
   if (params.empty()) return;
+  const Op op("adadelta", params[0]);
   const size_t n = params.size();
   const int pd = uniform_dtype(params), gd = uniform_dtype(grads);
   check_same_numel(params, grads, "grads");
   check_same_numel(params, square_avg, "square_avg");
   check_same_numel(params, acc_delta, "acc_delta");
   check_same_numel(params, copies, "model_copy");
-  auto P = Lists::from(params, "params", pd, n), G = Lists::from(grads, "grads", gd, n),
-       S = Lists::from(square_avg, "square_avg", 0, n), A = Lists::from(acc_delta, "acc_delta", 0, n),
-       C = Lists::from(copies, "model_copy", 1, n);
+  auto P = Lists::from(op, params, "params", pd, n), G = Lists::from(op, grads, "grads", gd, n),
+       S = Lists::from(op, square_avg, "square_avg", 0, n), A = Lists::from(op, acc_delta, "acc_delta", 0, n),
+       C = Lists::from(op, copies, "model_copy", 1, n);
   auto ne = numels(params);
   int rc = pdt_adadelta((int)n, P.ptrs.data(), G.ptrs.data(), S.ptrs.data(), A.ptrs.data(), C.ptrs.data(), ne.data(),
-                        pd, gd, (float)lr, opt_fptr(lr_t), (float)rho, (float)eps, (float)wd, maximize,
-                        opt_fptr(inv_scale), opt_fptr(found_inf), stream());
+                        pd, gd, (float)lr, opt_scalar_ptr(op, "lr_t", lr_t), (float)rho, (float)eps, (float)wd,
+                        maximize, opt_scalar_ptr(op, "inv_scale", inv_scale),
+                        opt_scalar_ptr(op, "found_inf", found_inf), stream());
   TORCH_CHECK(rc == 0, "pdt_adadelta failed");
 }
 
@@ -430,11 +218,10 @@ struct LayerwiseScratch {
                    const c10::optional<Tensor>& sums_t, const c10::optional<Tensor>& ratio_t, bool norms_only) {
     for (const auto& p : params)
       TORCH_CHECK(p.numel() > 0, "pdt layerwise: zero-element parameters have no trust-ratio slot; leave them out");
-    const bool has = ratio_t.has_value() && ratio_t->defined();
-    TORCH_CHECK(has || !norms_only, "pdt layerwise: norms_only needs the scratch tensors");
-    if (!has) return;
-    TORCH_CHECK(partials_t.has_value() && partials_t->defined() && sums_t.has_value() && sums_t->defined(),
-                "pdt layerwise: partials, sums and ratio come together");
+    const bool given = has(ratio_t);
+    TORCH_CHECK(given || !norms_only, "pdt layerwise: norms_only needs the scratch tensors");
+    if (!given) return;
+    TORCH_CHECK(has(partials_t) && has(sums_t), "pdt layerwise: partials, sums and ratio come together");
     const int64_t n = (int64_t)params.size();
     const auto dev = params[0].device();
     TORCH_CHECK(partials_t->is_cuda() && partials_t->device() == dev && partials_t->scalar_type() == at::kFloat &&
@@ -458,20 +245,21 @@ void lars(std::vector<Tensor> params, std::vector<Tensor> grads, std::vector<Ten
           c10::optional<Tensor> inv_scale, c10::optional<Tensor> found_inf, c10::optional<Tensor> partials,
           c10::optional<Tensor> sums, c10::optional<Tensor> ratio, bool norms_only) {
   if (params.empty()) return;
+  const Op op("lars", params[0]);
   const size_t n = params.size();
   const int pd = uniform_dtype(params), gd = uniform_dtype(grads);
   TORCH_CHECK(grads.size() == n, "pdt_lars: one gradient per parameter");
   check_same_numel(params, grads, "grads");
   check_same_numel(params, bufs, "momentum_buffer");
   check_same_numel(params, copies, "model_copy");
-  auto P = Lists::from(params, "params", pd, n), G = Lists::from(grads, "grads", gd, n),
-       B = Lists::from(bufs, "momentum_buffer", 0, n), C = Lists::from(copies, "model_copy", 1, n);
+  auto P = Lists::from(op, params, "params", pd, n), G = Lists::from(op, grads, "grads", gd, n),
+       B = Lists::from(op, bufs, "momentum_buffer", 0, n), C = Lists::from(op, copies, "model_copy", 1, n);
   LayerwiseScratch sc(params, partials, sums, ratio, norms_only);
   auto ne = numels(params);
   int rc = pdt_lars((int)n, P.ptrs.data(), G.ptrs.data(), B.ptrs.data(), C.ptrs.data(), ne.data(), pd, gd, (float)lr,
-                    opt_fptr(lr_t), (float)momentum, (float)dampening, (float)wd, nesterov, first,
-                    (float)trust_coefficient, (float)eps, maximize, opt_fptr(inv_scale), opt_fptr(found_inf),
-                    sc.partials, sc.sums, sc.ratio, norms_only, stream());
+                    opt_scalar_ptr(op, "lr_t", lr_t), (float)momentum, (float)dampening, (float)wd, nesterov, first,
+                    (float)trust_coefficient, (float)eps, maximize, opt_scalar_ptr(op, "inv_scale", inv_scale),
+                    opt_scalar_ptr(op, "found_inf", found_inf), sc.partials, sc.sums, sc.ratio, norms_only, stream());
   TORCH_CHECK(rc == 0, "pdt_lars failed: ", rc);
 }
 
@@ -481,6 +269,7 @@ void lamb(std::vector<Tensor> params, std::vector<Tensor> grads, std::vector<Ten
           bool maximize, c10::optional<Tensor> inv_scale, c10::optional<Tensor> found_inf,
           c10::optional<Tensor> partials, c10::optional<Tensor> sums, c10::optional<Tensor> ratio, bool norms_only) {
   if (params.empty()) return;
+  const Op op("lamb", params[0]);
   const size_t n = params.size();
   const int pd = uniform_dtype(params), gd = uniform_dtype(grads);
   TORCH_CHECK(grads.size() == n, "pdt_lamb: one gradient per parameter");
@@ -489,14 +278,15 @@ void lamb(std::vector<Tensor> params, std::vector<Tensor> grads, std::vector<Ten
   check_same_numel(params, exp_avg, "exp_avg");
   check_same_numel(params, exp_avg_sq, "exp_avg_sq");
   check_same_numel(params, copies, "model_copy");
-  auto P = Lists::from(params, "params", pd, n), G = Lists::from(grads, "grads", gd, n),
-       M = Lists::from(exp_avg, "exp_avg", 0, n), V = Lists::from(exp_avg_sq, "exp_avg_sq", 0, n),
-       C = Lists::from(copies, "model_copy", 1, n);
+  auto P = Lists::from(op, params, "params", pd, n), G = Lists::from(op, grads, "grads", gd, n),
+       M = Lists::from(op, exp_avg, "exp_avg", 0, n), V = Lists::from(op, exp_avg_sq, "exp_avg_sq", 0, n),
+       C = Lists::from(op, copies, "model_copy", 1, n);
   LayerwiseScratch sc(params, partials, sums, ratio, norms_only);
   auto ne = numels(params);
   int rc = pdt_lamb((int)n, P.ptrs.data(), G.ptrs.data(), M.ptrs.data(), V.ptrs.data(), C.ptrs.data(), ne.data(), pd,
-                    gd, (float)lr, opt_fptr(lr_t), (float)beta1, (float)beta2, (float)eps, (float)wd,
-                    opt_fptr(step_t), (float)step, maximize, opt_fptr(inv_scale), opt_fptr(found_inf), sc.partials,
+                    gd, (float)lr, opt_scalar_ptr(op, "lr_t", lr_t), (float)beta1, (float)beta2, (float)eps, (float)wd,
+                    opt_scalar_ptr(op, "step_t", step_t), (float)step, maximize,
+                    opt_scalar_ptr(op, "inv_scale", inv_scale), opt_scalar_ptr(op, "found_inf", found_inf), sc.partials,
                     sc.sums, sc.ratio, norms_only, stream());
   TORCH_CHECK(rc == 0, "pdt_lamb failed: ", rc);
 }
@@ -504,37 +294,42 @@ void lamb(std::vector<Tensor> params, std::vector<Tensor> grads, std::vector<Ten
 // ----------------------------------------------------------------------------- amp / buffers
 void amp_unscale(std::vector<Tensor> grads, Tensor inv_scale, Tensor found_inf) {
   if (grads.empty()) return;
+  const Op op("amp_unscale", grads[0]);
   const int d = uniform_dtype(grads);
-  auto G = Lists::from(grads, "grads", d, grads.size());
+  auto G = Lists::from(op, grads, "grads", d, grads.size());
   auto ne = numels(grads);
-  TORCH_CHECK(pdt_amp_unscale((int)grads.size(), G.ptrs.data(), ne.data(), d, inv_scale.data_ptr<float>(),
-                              found_inf.data_ptr<float>(), stream()) == 0, "pdt_amp_unscale failed");
+  TORCH_CHECK(pdt_amp_unscale((int)grads.size(), G.ptrs.data(), ne.data(), d, f32_ptr(op, "inv_scale", inv_scale, 1),
+                              f32_ptr(op, "found_inf", found_inf, 1), stream()) == 0, "pdt_amp_unscale failed");
 }
 
 void amp_update(Tensor scale, Tensor growth_tracker, Tensor found_inf, double growth, double backoff, int64_t interval) {
-  TORCH_CHECK(growth_tracker.scalar_type() == at::kInt, "growth_tracker must be int32");
-  pdt_amp_update(scale.data_ptr<float>(), growth_tracker.data_ptr<int>(), found_inf.data_ptr<float>(), (float)growth,
-                 (float)backoff, (int)interval, stream());
+  const Op op("amp_update", scale);
+  TORCH_CHECK(growth_tracker.scalar_type() == at::kInt && growth_tracker.numel() == 1 &&
+                  growth_tracker.device() == op.dev, "amp_update: growth_tracker must be int32 [1] on ", op.dev);
+  pdt_amp_update(f32_ptr(op, "scale", scale, 1), growth_tracker.data_ptr<int>(), f32_ptr(op, "found_inf", found_inf, 1),
+                 (float)growth, (float)backoff, (int)interval, stream());
 }
 
 void mt_scale(std::vector<Tensor> xs, c10::optional<Tensor> scale_t, double scale) {
   if (xs.empty()) return;
+  const Op op("mt_scale", xs[0]);
   const int d = uniform_dtype(xs);
-  auto X = Lists::from(xs, "x", d, xs.size());
+  auto X = Lists::from(op, xs, "x", d, xs.size());
   auto ne = numels(xs);
-  TORCH_CHECK(pdt_mt_scale((int)xs.size(), X.ptrs.data(), ne.data(), d, opt_fptr(scale_t), (float)scale, stream()) == 0,
-              "pdt_mt_scale failed");
+  TORCH_CHECK(pdt_mt_scale((int)xs.size(), X.ptrs.data(), ne.data(), d, opt_scalar_ptr(op, "scale_t", scale_t),
+                           (float)scale, stream()) == 0, "pdt_mt_scale failed");
 }
 
 void mt_copy(std::vector<Tensor> src, std::vector<Tensor> dst, c10::optional<Tensor> scale_t, double scale) {
   if (src.empty()) return;
+  const Op op("mt_copy", src[0]);
   TORCH_CHECK(src.size() == dst.size(), "mt_copy: list size mismatch");
   check_same_numel(src, dst, "dst");
   const int sd = uniform_dtype(src), dd = uniform_dtype(dst);
-  auto S = Lists::from(src, "src", sd, src.size()), D = Lists::from(dst, "dst", dd, dst.size());
+  auto S = Lists::from(op, src, "src", sd, src.size()), D = Lists::from(op, dst, "dst", dd, dst.size());
   auto ne = numels(src);
-  TORCH_CHECK(pdt_mt_copy((int)src.size(), S.ptrs.data(), D.ptrs.data(), ne.data(), sd, dd, opt_fptr(scale_t),
-                          (float)scale, stream()) == 0, "pdt_mt_copy failed");
+  TORCH_CHECK(pdt_mt_copy((int)src.size(), S.ptrs.data(), D.ptrs.data(), ne.data(), sd, dd,
+                          opt_scalar_ptr(op, "scale_t", scale_t), (float)scale, stream()) == 0, "pdt_mt_copy failed");
 }
 
 void l2norm_sq(std::vector<Tensor> xs, Tensor out) {
@@ -543,26 +338,81 @@ void l2norm_sq(std::vector<Tensor> xs, Tensor out) {
     out.zero_();
     return;
   }
+  const Op op("l2norm_sq", xs[0]);
+  TORCH_CHECK(out.device() == op.dev, "l2norm_sq: out must be on ", op.dev);
   const int d = uniform_dtype(xs);
-  auto X = Lists::from(xs, "x", d, xs.size());
+  auto X = Lists::from(op, xs, "x", d, xs.size());
   auto ne = numels(xs);
   pdt_l2norm_sq((int)xs.size(), X.ptrs.data(), ne.data(), d, out.data_ptr<float>(), stream());
 }
 
 void clip_coef(Tensor sumsq, double max_norm, Tensor coef, c10::optional<Tensor> norm) {
-  pdt_clip_coef(sumsq.data_ptr<float>(), (float)max_norm, coef.data_ptr<float>(),
-                norm.has_value() ? norm->data_ptr<float>() : nullptr, stream());
+  const Op op("clip_coef", sumsq);
+  pdt_clip_coef(f32_ptr(op, "sumsq", sumsq, 1), (float)max_norm, f32_ptr(op, "coef", coef, 1),
+                opt_f32_ptr(op, "norm", norm, 1), stream());
 }
 
 // ----------------------------------------------------------------------------- batchnorm (NHWC bf16)
-void check_nhwc_bf16(const Tensor& t, const char* name) {
-  check_cuda(t, name);
-  TORCH_CHECK(t.scalar_type() == at::kBFloat16, "pdt bn: ", name, " must be bf16");
+// A BatchNorm / conv activation: bf16 on the op's device, channels_last when 4-D, [M, C] contiguous when 2-D.
+void check_nhwc_bf16(const Op& op, const char* name, const Tensor& t) {
+  TORCH_CHECK(t.defined() && t.device() == op.dev && t.scalar_type() == at::kBFloat16, op.name, ": ", name,
+              " must be a bf16 tensor on ", op.dev);
   if (t.dim() == 4) {
-    TORCH_CHECK(t.is_contiguous(at::MemoryFormat::ChannelsLast), "pdt bn: ", name, " must be channels_last");
+    TORCH_CHECK(t.is_contiguous(at::MemoryFormat::ChannelsLast), op.name, ": ", name, " must be channels_last");
   } else {
-    TORCH_CHECK(t.dim() == 2 && t.is_contiguous(), "pdt bn: ", name, " must be [M, C] contiguous or NHWC");
+    TORCH_CHECK(t.dim() == 2 && t.is_contiguous(), op.name, ": ", name, " must be [M, C] contiguous or NHWC");
   }
+}
+
+// The residual added by a BatchNorm over x (or nullptr): x's sizes and strides, so bf16 channels_last as x.
+const uint16_t* residual_ptr(const Op& op, const Tensor& x, const c10::optional<Tensor>& res) {
+  if (!has(res)) return nullptr;
+  check_nhwc_bf16(op, "residual", *res);
+  TORCH_CHECK(res->sizes() == x.sizes() && res->strides() == x.strides(), op.name, ": residual layout mismatch");
+  return bf16_ptr(*res);
+}
+
+// The ReLU bit-mask [M C / 8] a BatchNorm backward with relu reads (nullptr without relu).
+const uint8_t* relu_mask_ptr(const Op& op, const c10::optional<Tensor>& mask, bool relu, int64_t bytes) {
+  if (!relu) return nullptr;
+  TORCH_CHECK(has(mask), op.name, ": relu needs the mask");
+  return u8_ptr(op, "mask", *mask, bytes);
+}
+
+// dgamma / dbeta fp32 [C] of a BatchNorm backward: allocated with need_dgamma, else undefined (null pointers).
+struct GammaGrads {
+  Tensor dg, db;
+  GammaGrads(bool need_dgamma, int64_t C, const at::TensorOptions& fopt) {
+    if (need_dgamma) {
+      dg = at::empty({C}, fopt);
+      db = at::empty({C}, fopt);
+    }
+  }
+  float* dg_ptr() const { return ptr_or_null<float>(dg); }
+  float* db_ptr() const { return ptr_or_null<float>(db); }
+};
+
+// bn_x / bn_mask / bn_mean of a producer op: its output [M, C] is the gradient at the output of a BatchNorm
+// with input bn_x (bf16 [M, C] as check_nhwc_bf16), ReLU bit-mask bn_mask (uint8 [M C / 8], or none) and batch
+// mean bn_mean (fp32 [C]), whose backward partials the producer accumulates. sum_only: bn_x is not read.
+struct BnSide {
+  const uint16_t* x = nullptr;
+  const uint8_t* mask = nullptr;
+  const float* mean = nullptr;
+};
+BnSide bn_side(const Op& op, const c10::optional<Tensor>& bn_x, const c10::optional<Tensor>& bn_mask,
+               const c10::optional<Tensor>& bn_mean, int64_t M, int64_t C, bool sum_only) {
+  BnSide s;
+  if (!sum_only) {
+    TORCH_CHECK(has(bn_x), op.name, ": bn_x is required");
+    check_nhwc_bf16(op, "bn_x", *bn_x);
+    TORCH_CHECK(bn_x->numel() == M * C, op.name, ": bn_x must be [M, C] = [", M, ", ", C, "]");
+    s.x = bf16_ptr(*bn_x);
+  }
+  TORCH_CHECK(has(bn_mean), op.name, ": bn_mean is required with bn_x");
+  s.mean = f32_ptr(op, "bn_mean", *bn_mean, C);
+  s.mask = opt_u8_ptr(op, "bn_mask", bn_mask, M * C / 8);
+  return s;
 }
 
 int64_t bn_ws_floats(int64_t M, int64_t C) { return pdt_bn_workspace_floats(M, (int)C); }
@@ -582,22 +432,16 @@ unsigned* bn_counters(const Tensor& like) {
 // res_ab [2, C] (optional): the residual is a deferred BatchNorm's input, added as ab[0]*res + ab[1].
 // apply = false: statistics only -> {undefined, undefined, mean, invstd, ab [2, C]} (the y = a x + b
 // coefficients, for a consumer that applies them itself).
-std::pair<const float*, const float*> res_ab_ptrs(const c10::optional<Tensor>& res_ab, int64_t C) {
-  if (!res_ab.has_value() || !res_ab->defined()) return {nullptr, nullptr};
-  TORCH_CHECK(res_ab->scalar_type() == at::kFloat && res_ab->is_contiguous() && res_ab->numel() == 2 * C &&
-              res_ab->is_cuda(), "pdt bn: res_ab must be fp32 [2, C]");
-  return {res_ab->data_ptr<float>(), res_ab->data_ptr<float>() + C};
-}
-
 std::vector<Tensor> bn_fwd_train(Tensor x, c10::optional<Tensor> res, c10::optional<Tensor> weight,
                                  c10::optional<Tensor> bias, c10::optional<Tensor> running_mean,
                                  c10::optional<Tensor> running_var, double momentum, double eps, bool relu,
                                  c10::optional<Tensor> res_ab, bool apply) {
-  check_nhwc_bf16(x, "x");
+  const Op op("bn_fwd_train", x);
+  check_nhwc_bf16(op, "x", x);
   const int64_t C = x.size(1);
   const int64_t M = x.numel() / C;
   TORCH_CHECK(C % 64 == 0 && C <= 64 * 4096, "pdt bn: C must be a multiple of 64");
-  const auto rab = res_ab_ptrs(res_ab, C);
+  const float* rab = opt_f32_ptr(op, "res_ab", res_ab, 2 * C);
   Tensor y;
   if (apply) y = at::empty_like(x);
   Tensor mask;
@@ -605,19 +449,11 @@ std::vector<Tensor> bn_fwd_train(Tensor x, c10::optional<Tensor> res, c10::optio
   auto fopt = x.options().dtype(at::kFloat);
   auto mean = at::empty({C}, fopt), invstd = at::empty({C}, fopt);
   auto ws = at::empty({bn_ws_floats(M, C)}, fopt);
-  const uint16_t* rp = nullptr;
-  if (res.has_value() && res->defined()) {
-    check_nhwc_bf16(*res, "residual");
-    TORCH_CHECK(res->sizes() == x.sizes() && res->strides() == x.strides(), "pdt bn: residual layout mismatch");
-    rp = reinterpret_cast<const uint16_t*>(res->data_ptr());
-  }
-  float* rm = running_mean.has_value() && running_mean->defined() ? running_mean->data_ptr<float>() : nullptr;
-  float* rv = running_var.has_value() && running_var->defined() ? running_var->data_ptr<float>() : nullptr;
-  int rc = pdt_bn_fwd_train(reinterpret_cast<const uint16_t*>(x.data_ptr()), rp, rab.first, rab.second,
-                            opt_fptr(weight), opt_fptr(bias), rm, rv,
-                            (float)momentum, (float)eps, M, (int)C, relu,
-                            apply ? reinterpret_cast<uint16_t*>(y.data_ptr()) : nullptr,
-                            (relu && apply) ? mask.data_ptr<uint8_t>() : nullptr, mean.data_ptr<float>(),
+  int rc = pdt_bn_fwd_train(bf16_ptr(x), residual_ptr(op, x, res), rab, rab ? rab + C : nullptr,
+                            opt_f32_ptr(op, "weight", weight, C), opt_f32_ptr(op, "bias", bias, C),
+                            opt_f32_ptr(op, "running_mean", running_mean, C),
+                            opt_f32_ptr(op, "running_var", running_var, C), (float)momentum, (float)eps, M, (int)C,
+                            relu, ptr_or_null<uint16_t>(y), ptr_or_null<uint8_t>(mask), mean.data_ptr<float>(),
                             invstd.data_ptr<float>(), ws.data_ptr<float>(), bn_counters(x), stream());
   TORCH_CHECK(rc == 0, "pdt_bn_fwd_train failed: ", rc);
   if (!apply) return {Tensor(), Tensor(), mean, invstd, ws.narrow(0, bn_ws_floats(M, C) - 4 * C, 2 * C).view({2, C})};
@@ -628,7 +464,8 @@ std::vector<Tensor> bn_fwd_train(Tensor x, c10::optional<Tensor> res, c10::optio
 std::vector<Tensor> bn_relu_maxpool_fwd(Tensor x, c10::optional<Tensor> weight, c10::optional<Tensor> bias,
                                         c10::optional<Tensor> running_mean, c10::optional<Tensor> running_var,
                                         double momentum, double eps) {
-  check_nhwc_bf16(x, "x");
+  const Op op("bn_relu_maxpool_fwd", x);
+  check_nhwc_bf16(op, "x", x);
   TORCH_CHECK(x.dim() == 4, "bn_relu_maxpool: 4-D NHWC input");
   const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   TORCH_CHECK(C % 64 == 0, "pdt bn: C must be a multiple of 64");
@@ -638,11 +475,11 @@ std::vector<Tensor> bn_relu_maxpool_fwd(Tensor x, c10::optional<Tensor> weight, 
   auto fopt = x.options().dtype(at::kFloat);
   auto mean = at::empty({C}, fopt), invstd = at::empty({C}, fopt);
   auto ws = at::empty({bn_ws_floats(N * H * W, C)}, fopt);
-  float* rm = running_mean.has_value() && running_mean->defined() ? running_mean->data_ptr<float>() : nullptr;
-  float* rv = running_var.has_value() && running_var->defined() ? running_var->data_ptr<float>() : nullptr;
-  int rc = pdt_bn_relu_maxpool_fwd_train(reinterpret_cast<const uint16_t*>(x.data_ptr()), opt_fptr(weight),
-                                         opt_fptr(bias), rm, rv, (float)momentum, (float)eps, (int)N, (int)H, (int)W,
-                                         (int)C, reinterpret_cast<uint16_t*>(y.data_ptr()), code.data_ptr<uint8_t>(),
+  int rc = pdt_bn_relu_maxpool_fwd_train(bf16_ptr(x), opt_f32_ptr(op, "weight", weight, C),
+                                         opt_f32_ptr(op, "bias", bias, C),
+                                         opt_f32_ptr(op, "running_mean", running_mean, C),
+                                         opt_f32_ptr(op, "running_var", running_var, C), (float)momentum, (float)eps,
+                                         (int)N, (int)H, (int)W, (int)C, bf16_out(y), code.data_ptr<uint8_t>(),
                                          mean.data_ptr<float>(), invstd.data_ptr<float>(), ws.data_ptr<float>(),
                                          bn_counters(x), stream());
   TORCH_CHECK(rc == 0, "pdt_bn_relu_maxpool_fwd_train failed");
@@ -653,12 +490,12 @@ std::vector<Tensor> bn_relu_maxpool_fwd(Tensor x, c10::optional<Tensor> weight, 
 std::vector<Tensor> bn_relu_maxpool_fwd_parts(Tensor x, Tensor part, c10::optional<Tensor> weight,
                                               c10::optional<Tensor> bias, c10::optional<Tensor> running_mean,
                                               c10::optional<Tensor> running_var, double momentum, double eps) {
-  check_nhwc_bf16(x, "x");
+  const Op op("bn_relu_maxpool_fwd_parts", x);
+  check_nhwc_bf16(op, "x", x);
   TORCH_CHECK(x.dim() == 4, "bn_relu_maxpool: 4-D NHWC input");
   const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   TORCH_CHECK(C == 64, "bn_relu_maxpool_fwd_parts: C == 64 (the stem)");
-  TORCH_CHECK(part.is_cuda() && part.scalar_type() == at::kFloat && part.is_contiguous() && part.dim() == 1 &&
-                  part.numel() % (2 * C + 1) == 0, "bn_relu_maxpool_fwd_parts: part [P * (2 C + 1)] f32");
+  TORCH_CHECK(part.dim() == 1 && part.numel() % (2 * C + 1) == 0, "bn_relu_maxpool_fwd_parts: part [P * (2 C + 1)] f32");
   const int64_t P = part.numel() / (2 * C + 1);
   const int64_t Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   auto y = at::empty({N, C, Ho, Wo}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
@@ -666,12 +503,11 @@ std::vector<Tensor> bn_relu_maxpool_fwd_parts(Tensor x, Tensor part, c10::option
   auto fopt = x.options().dtype(at::kFloat);
   auto mean = at::empty({C}, fopt), invstd = at::empty({C}, fopt);
   auto ws = at::empty({pdt_bn_parts_ws_floats((int)P, (int)C)}, fopt);
-  float* rm = running_mean.has_value() && running_mean->defined() ? running_mean->data_ptr<float>() : nullptr;
-  float* rv = running_var.has_value() && running_var->defined() ? running_var->data_ptr<float>() : nullptr;
-  int rc = pdt_bn_relu_maxpool_fwd_train_parts(part.data_ptr<float>(), (int)P,
-                                               reinterpret_cast<const uint16_t*>(x.data_ptr()), opt_fptr(weight),
-                                               opt_fptr(bias), rm, rv, (float)momentum, (float)eps, (int)N, (int)H,
-                                               (int)W, (int)C, reinterpret_cast<uint16_t*>(y.data_ptr()),
+  int rc = pdt_bn_relu_maxpool_fwd_train_parts(f32_ptr(op, "part", part, P * (2 * C + 1)), (int)P, bf16_ptr(x),
+                                               opt_f32_ptr(op, "weight", weight, C), opt_f32_ptr(op, "bias", bias, C),
+                                               opt_f32_ptr(op, "running_mean", running_mean, C),
+                                               opt_f32_ptr(op, "running_var", running_var, C), (float)momentum,
+                                               (float)eps, (int)N, (int)H, (int)W, (int)C, bf16_out(y),
                                                code.data_ptr<uint8_t>(), mean.data_ptr<float>(),
                                                invstd.data_ptr<float>(), ws.data_ptr<float>(), stream());
   TORCH_CHECK(rc == 0, "pdt_bn_relu_maxpool_fwd_train_parts failed: ", rc);
@@ -683,70 +519,60 @@ std::vector<Tensor> bn_relu_maxpool_fwd_parts(Tensor x, Tensor part, c10::option
 // (the input of bn_bwd_train_tiles); {dy} alone when the reduction does not apply to C.
 std::vector<Tensor> gap_bwd(Tensor g, int64_t H, int64_t W, c10::optional<Tensor> bn_x, c10::optional<Tensor> bn_mask,
                             c10::optional<Tensor> bn_mean, bool bn_sum_only) {
-  check_cuda(g, "g");
+  const Op op("gap_bwd", g);
   TORCH_CHECK(g.dim() == 2 && g.scalar_type() == at::kBFloat16 && g.is_contiguous() && g.size(1) % 8 == 0,
               "gap_bwd: g [N, C] contiguous bf16, C % 8 == 0");
   const int64_t N = g.size(0), C = g.size(1), M = N * H * W;
   auto dy = at::empty({N, C, H, W}, g.options().memory_format(at::MemoryFormat::ChannelsLast));
-  const bool red = ((bn_x.has_value() && bn_x->defined()) || bn_sum_only) && pdt_gap_bwd_parts(M, (int)C) > 0;
+  const bool red = (has(bn_x) || bn_sum_only) && pdt_gap_bwd_parts(M, (int)C) > 0;
   Tensor part;
-  const uint16_t* xp = nullptr;
-  const uint8_t* mp = nullptr;
-  const float* mu = nullptr;
+  BnSide bn;
   if (red) {
-    if (!bn_sum_only) {
-      check_nhwc_bf16(*bn_x, "bn_x");
-      TORCH_CHECK(bn_x->sizes() == dy.sizes(), "gap_bwd: bn_x must be [N, C, H, W]");
-      xp = reinterpret_cast<const uint16_t*>(bn_x->data_ptr());
-    }
-    TORCH_CHECK(bn_mean.has_value() && bn_mean->defined() && bn_mean->scalar_type() == at::kFloat &&
-                    bn_mean->numel() == C && bn_mean->is_cuda(), "gap_bwd: bn_mean fp32 [C]");
-    if (bn_mask.has_value() && bn_mask->defined()) {
-      TORCH_CHECK(bn_mask->scalar_type() == at::kByte && bn_mask->numel() == M * C / 8, "gap_bwd: bn_mask uint8 [M C / 8]");
-      mp = bn_mask->data_ptr<uint8_t>();
-    }
-    mu = bn_mean->data_ptr<float>();
+    bn = bn_side(op, bn_x, bn_mask, bn_mean, M, C, bn_sum_only);
+    TORCH_CHECK(bn_sum_only || bn_x->sizes() == dy.sizes(), "gap_bwd: bn_x must be [N, C, H, W]");
     part = at::empty({2, pdt_gap_bwd_parts(M, (int)C), C}, g.options().dtype(at::kFloat));
   }
-  const int rc = pdt_gap_bwd(reinterpret_cast<const uint16_t*>(g.data_ptr()), (int)N, (int)(H * W), (int)C,
-                             reinterpret_cast<uint16_t*>(dy.data_ptr()), xp, mp, mu,
-                             red ? part.data_ptr<float>() : nullptr, stream());
+  const int rc = pdt_gap_bwd(bf16_ptr(g), (int)N, (int)(H * W), (int)C, bf16_out(dy), bn.x, bn.mask, bn.mean,
+                             ptr_or_null<float>(part), stream());
   TORCH_CHECK(rc == 0, "pdt_gap_bwd failed: ", rc);
   if (red) return {dy, part};
   return {dy};
 }
 
 Tensor maxpool3s2_bwd(Tensor dy, Tensor code, int64_t H, int64_t W) {
+  const Op op("maxpool3s2_bwd", dy);
   dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
-  check_nhwc_bf16(dy, "dy");
+  check_nhwc_bf16(op, "dy", dy);
   const int64_t N = dy.size(0), C = dy.size(1);
-  TORCH_CHECK(dy.size(2) == (H - 1) / 2 + 1 && dy.size(3) == (W - 1) / 2 + 1 && code.numel() == dy.numel(),
-              "maxpool3s2_bwd: shape mismatch");
+  TORCH_CHECK(dy.size(2) == (H - 1) / 2 + 1 && dy.size(3) == (W - 1) / 2 + 1, "maxpool3s2_bwd: shape mismatch");
   auto dz = at::empty({N, C, H, W}, dy.options().memory_format(at::MemoryFormat::ChannelsLast));
-  int rc = pdt_maxpool3s2_bwd(reinterpret_cast<const uint16_t*>(dy.data_ptr()), code.data_ptr<uint8_t>(),
-                              reinterpret_cast<uint16_t*>(dz.data_ptr()), (int)N, (int)H, (int)W, (int)C, stream());
+  int rc = pdt_maxpool3s2_bwd(bf16_ptr(dy), u8_ptr(op, "code", code, dy.numel()), bf16_out(dz), (int)N, (int)H, (int)W,
+                              (int)C, stream());
   TORCH_CHECK(rc == 0, "pdt_maxpool3s2_bwd failed");
   return dz;
 }
 
 Tensor bn_fwd_eval(Tensor x, c10::optional<Tensor> res, c10::optional<Tensor> weight, c10::optional<Tensor> bias,
                    Tensor running_mean, Tensor running_var, double eps, bool relu) {
-  check_nhwc_bf16(x, "x");
+  const Op op("bn_fwd_eval", x);
+  check_nhwc_bf16(op, "x", x);
   const int64_t C = x.size(1);
   const int64_t M = x.numel() / C;
   auto y = at::empty_like(x);
   auto ws = at::empty({2 * C}, x.options().dtype(at::kFloat));
-  const uint16_t* rp = (res.has_value() && res->defined()) ? reinterpret_cast<const uint16_t*>(res->data_ptr()) : nullptr;
-  int rc = pdt_bn_fwd_eval(reinterpret_cast<const uint16_t*>(x.data_ptr()), rp, opt_fptr(weight), opt_fptr(bias),
-                           running_mean.data_ptr<float>(), running_var.data_ptr<float>(), (float)eps, M, (int)C, relu,
-                           reinterpret_cast<uint16_t*>(y.data_ptr()), ws.data_ptr<float>(), stream());
+  int rc = pdt_bn_fwd_eval(bf16_ptr(x), residual_ptr(op, x, res), opt_f32_ptr(op, "weight", weight, C),
+                           opt_f32_ptr(op, "bias", bias, C), f32_ptr(op, "running_mean", running_mean, C),
+                           f32_ptr(op, "running_var", running_var, C), (float)eps, M, (int)C, relu, bf16_out(y),
+                           ws.data_ptr<float>(), stream());
   TORCH_CHECK(rc == 0, "pdt_bn_fwd_eval failed");
   return y;
 }
 
 std::vector<Tensor> bn_bwd_train(Tensor dy, Tensor x, c10::optional<Tensor> mask, c10::optional<Tensor> weight,
                                  Tensor mean, Tensor invstd, bool relu, bool has_res, bool need_dgamma) {
-  check_nhwc_bf16(x, "x");
+  const Op op("bn_bwd_train", x);
+  check_nhwc_bf16(op, "x", x);
+  check_nhwc_bf16(op, "dy", dy);
   TORCH_CHECK(dy.sizes() == x.sizes() && dy.strides() == x.strides(), "pdt bn bwd: dy layout mismatch");
   const int64_t C = x.size(1);
   const int64_t M = x.numel() / C;
@@ -755,58 +581,34 @@ std::vector<Tensor> bn_bwd_train(Tensor dy, Tensor x, c10::optional<Tensor> mask
   Tensor dres;
   if (has_res) dres = at::empty_like(x);
   auto fopt = x.options().dtype(at::kFloat);
-  Tensor dg, db;
-  if (need_dgamma) {
-    dg = at::empty({C}, fopt);
-    db = at::empty({C}, fopt);
-  }
+  const GammaGrads gg(need_dgamma, C, fopt);
   auto ws = at::empty({bn_ws_floats(M, C)}, fopt);
-  const uint8_t* mp = nullptr;
-  if (relu) {
-    TORCH_CHECK(mask.has_value() && mask->defined() && mask->numel() == M * C / 8, "pdt bn bwd: relu needs the mask");
-    mp = mask->data_ptr<uint8_t>();
-  }
-  int rc = pdt_bn_bwd_train(reinterpret_cast<const uint16_t*>(dy.data_ptr()), reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                            mp, opt_fptr(weight), mean.data_ptr<float>(), invstd.data_ptr<float>(), M, (int)C, relu,
-                            has_res, reinterpret_cast<uint16_t*>(dx.data_ptr()),
-                            has_res ? reinterpret_cast<uint16_t*>(dres.data_ptr()) : nullptr,
-                            need_dgamma ? dg.data_ptr<float>() : nullptr, need_dgamma ? db.data_ptr<float>() : nullptr,
-                            ws.data_ptr<float>(), bn_counters(x), stream());
+  int rc = pdt_bn_bwd_train(bf16_ptr(dy), bf16_ptr(x), relu_mask_ptr(op, mask, relu, M * C / 8),
+                            opt_f32_ptr(op, "weight", weight, C), f32_ptr(op, "mean", mean, C),
+                            f32_ptr(op, "invstd", invstd, C), M, (int)C, relu, has_res, bf16_out(dx),
+                            ptr_or_null<uint16_t>(dres), gg.dg_ptr(), gg.db_ptr(), ws.data_ptr<float>(), bn_counters(x),
+                            stream());
   TORCH_CHECK(rc == 0, "pdt_bn_bwd_train failed");
-  return {dx, dres, dg, db};
+  return {dx, dres, gg.dg, gg.db};
 }
 
 // ---- SyncBatchNorm (ops/sync_batchnorm.py): the train forward / backward split around the exchange.
-void check_f32_cuda(const Tensor& t, int64_t numel, const char* name) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == numel,
-              "pdt sync bn: ", name, " must be a contiguous fp32 GPU tensor of ", numel, " elements");
-}
-
-const uint8_t* relu_mask_ptr(const c10::optional<Tensor>& mask, bool relu, int64_t bytes) {
-  if (!relu) return nullptr;
-  TORCH_CHECK(mask.has_value() && mask->defined() && mask->is_cuda() && mask->scalar_type() == at::kByte &&
-              mask->numel() == bytes, "pdt sync bn: relu needs the uint8 mask [M C / 8]");
-  return mask->data_ptr<uint8_t>();
-}
-
 // This rank's raw statistics [2, C] = (mean_r, M2_r = sum (x - mean_r)^2). row (optional, fp32 [2C + 1]): written
 // in place as (mean_r, M2_r, M) — this rank's row of the exchange buffer — and returned.
 Tensor bn_sync_fwd_stats(Tensor x, c10::optional<Tensor> row) {
-  check_nhwc_bf16(x, "x");
+  const Op op("bn_sync_fwd_stats", x);
+  check_nhwc_bf16(op, "x", x);
   const int64_t C = x.size(1);
   TORCH_CHECK(C % 64 == 0 && C <= 64 * 4096 && x.numel() > 0, "pdt sync bn: C must be a multiple of 64, M >= 1");
   const int64_t M = x.numel() / C;
   auto fopt = x.options().dtype(at::kFloat);
-  const bool in_row = row.has_value() && row->defined();
-  if (in_row) {
-    check_f32_cuda(*row, 2 * C + 1, "row");
-    TORCH_CHECK(M < (1 << 24), "pdt sync bn: the row count travels as fp32 (M < 2^24)");
-  }
+  const bool in_row = has(row);
+  if (in_row) TORCH_CHECK(M < (1 << 24), "pdt sync bn: the row count travels as fp32 (M < 2^24)");
   auto stats = in_row ? *row : at::empty({2, C}, fopt);
+  float* sp = f32_ptr(op, "row", stats, in_row ? 2 * C + 1 : 2 * C);
   auto ws = at::empty({bn_ws_floats(M, C)}, fopt);
-  const int rc = pdt_bn_sync_fwd_stats(reinterpret_cast<const uint16_t*>(x.data_ptr()), M, (int)C,
-                                       stats.data_ptr<float>(), in_row ? stats.data_ptr<float>() + 2 * C : nullptr,
-                                       ws.data_ptr<float>(), bn_counters(x), stream());
+  const int rc = pdt_bn_sync_fwd_stats(bf16_ptr(x), M, (int)C, sp, in_row ? sp + 2 * C : nullptr, ws.data_ptr<float>(),
+                                       bn_counters(x), stream());
   TORCH_CHECK(rc == 0, "pdt_bn_sync_fwd_stats failed: ", rc);
   return stats;
 }
@@ -816,22 +618,18 @@ Tensor bn_sync_fwd_stats(Tensor x, c10::optional<Tensor> row) {
 std::vector<Tensor> bn_sync_fwd_merge(Tensor gathered, c10::optional<Tensor> weight, c10::optional<Tensor> bias,
                                       c10::optional<Tensor> running_mean, c10::optional<Tensor> running_var,
                                       double momentum, double eps) {
+  const Op op("bn_sync_fwd_merge", gathered);
   TORCH_CHECK(gathered.dim() == 2 && gathered.size(0) >= 1 && gathered.size(1) % 2 == 1,
               "pdt sync bn: gathered must be [W, 2C + 1]");
   const int64_t W = gathered.size(0), C = (gathered.size(1) - 1) / 2;
   TORCH_CHECK(C >= 64 && C % 64 == 0, "pdt sync bn: C must be a multiple of 64");
-  check_f32_cuda(gathered, W * (2 * C + 1), "gathered");
-  auto opt_c = [&](const c10::optional<Tensor>& t, const char* name) -> float* {
-    if (!t.has_value() || !t->defined()) return nullptr;
-    check_f32_cuda(*t, C, name);
-    return t->data_ptr<float>();
-  };
   auto mean = at::empty({C}, gathered.options()), invstd = at::empty({C}, gathered.options());
   auto ab = at::empty({2, C}, gathered.options());
   auto ntot = at::empty({1}, gathered.options().dtype(at::kLong));
-  const int rc = pdt_bn_sync_fwd_merge(gathered.data_ptr<float>(), (int)W, (int)C, opt_c(weight, "weight"),
-                                       opt_c(bias, "bias"), opt_c(running_mean, "running_mean"),
-                                       opt_c(running_var, "running_var"), (float)momentum, (float)eps,
+  const int rc = pdt_bn_sync_fwd_merge(f32_ptr(op, "gathered", gathered, W * (2 * C + 1)), (int)W, (int)C,
+                                       opt_f32_ptr(op, "weight", weight, C), opt_f32_ptr(op, "bias", bias, C),
+                                       opt_f32_ptr(op, "running_mean", running_mean, C),
+                                       opt_f32_ptr(op, "running_var", running_var, C), (float)momentum, (float)eps,
                                        mean.data_ptr<float>(), invstd.data_ptr<float>(), ab.data_ptr<float>(),
                                        ntot.data_ptr<int64_t>(), stream());
   TORCH_CHECK(rc == 0, "pdt_bn_sync_fwd_merge failed: ", rc);
@@ -840,23 +638,16 @@ std::vector<Tensor> bn_sync_fwd_merge(Tensor gathered, c10::optional<Tensor> wei
 
 // y = relu?(ab[0] x + ab[1] + res?) -> {y, mask (with relu)}.
 std::vector<Tensor> bn_apply_coef(Tensor x, c10::optional<Tensor> res, Tensor ab, bool relu) {
-  check_nhwc_bf16(x, "x");
+  const Op op("bn_apply_coef", x);
+  check_nhwc_bf16(op, "x", x);
   const int64_t C = x.size(1);
   TORCH_CHECK(C % 64 == 0 && x.numel() > 0, "pdt sync bn: C must be a multiple of 64, M >= 1");
   const int64_t M = x.numel() / C;
-  check_f32_cuda(ab, 2 * C, "ab");
-  const uint16_t* rp = nullptr;
-  if (res.has_value() && res->defined()) {
-    check_nhwc_bf16(*res, "residual");
-    TORCH_CHECK(res->sizes() == x.sizes() && res->strides() == x.strides(), "pdt sync bn: residual layout mismatch");
-    rp = reinterpret_cast<const uint16_t*>(res->data_ptr());
-  }
   auto y = at::empty_like(x);
   Tensor mask;
   if (relu) mask = at::empty({M * C / 8}, x.options().dtype(at::kByte));
-  const int rc = pdt_bn_apply_coef(reinterpret_cast<const uint16_t*>(x.data_ptr()), rp, ab.data_ptr<float>(), M, (int)C,
-                                   relu, reinterpret_cast<uint16_t*>(y.data_ptr()),
-                                   relu ? mask.data_ptr<uint8_t>() : nullptr, stream());
+  const int rc = pdt_bn_apply_coef(bf16_ptr(x), residual_ptr(op, x, res), f32_ptr(op, "ab", ab, 2 * C), M, (int)C, relu,
+                                   bf16_out(y), ptr_or_null<uint8_t>(mask), stream());
   TORCH_CHECK(rc == 0, "pdt_bn_apply_coef failed: ", rc);
   return {y, mask};
 }
@@ -865,22 +656,19 @@ std::vector<Tensor> bn_apply_coef(Tensor x, c10::optional<Tensor> res, Tensor ab
 // row (optional, fp32 [2C]): written in place (this rank's row of the exchange buffer) and returned.
 Tensor bn_sync_bwd_sums(Tensor dy, Tensor x, c10::optional<Tensor> mask, Tensor mean, bool relu,
                         c10::optional<Tensor> row) {
-  check_nhwc_bf16(x, "x");
-  check_nhwc_bf16(dy, "dy");
+  const Op op("bn_sync_bwd_sums", x);
+  check_nhwc_bf16(op, "x", x);
+  check_nhwc_bf16(op, "dy", dy);
   TORCH_CHECK(dy.sizes() == x.sizes() && dy.strides() == x.strides(), "pdt sync bn: dy layout mismatch");
   const int64_t C = x.size(1);
   TORCH_CHECK(C % 64 == 0 && x.numel() > 0, "pdt sync bn: C must be a multiple of 64, M >= 1");
   const int64_t M = x.numel() / C;
-  check_f32_cuda(mean, C, "mean");
   auto fopt = x.options().dtype(at::kFloat);
-  const bool in_row = row.has_value() && row->defined();
-  if (in_row) check_f32_cuda(*row, 2 * C, "row");
-  auto sums = in_row ? *row : at::empty({2, C}, fopt);
+  auto sums = has(row) ? *row : at::empty({2, C}, fopt);
   auto ws = at::empty({bn_ws_floats(M, C)}, fopt);
-  const int rc = pdt_bn_sync_bwd_sums(reinterpret_cast<const uint16_t*>(dy.data_ptr()),
-                                      reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                                      relu_mask_ptr(mask, relu, M * C / 8), mean.data_ptr<float>(), M, (int)C, relu,
-                                      sums.data_ptr<float>(), ws.data_ptr<float>(), bn_counters(x), stream());
+  const int rc = pdt_bn_sync_bwd_sums(bf16_ptr(dy), bf16_ptr(x), relu_mask_ptr(op, mask, relu, M * C / 8),
+                                      f32_ptr(op, "mean", mean, C), M, (int)C, relu, f32_ptr(op, "row", sums, 2 * C),
+                                      ws.data_ptr<float>(), bn_counters(x), stream());
   TORCH_CHECK(rc == 0, "pdt_bn_sync_bwd_sums failed: ", rc);
   return sums;
 }
@@ -889,53 +677,40 @@ Tensor bn_sync_bwd_sums(Tensor dy, Tensor x, c10::optional<Tensor> mask, Tensor 
 // dgamma, dbeta from row `rank` only (undefined without need_dgamma)}.
 std::vector<Tensor> bn_sync_bwd_merge(Tensor gathered, int64_t rank, c10::optional<Tensor> weight, Tensor invstd,
                                       Tensor ntot, bool need_dgamma) {
+  const Op op("bn_sync_bwd_merge", gathered);
   TORCH_CHECK(gathered.dim() == 2 && gathered.size(0) >= 1 && gathered.size(1) % 2 == 0,
               "pdt sync bn: gathered must be [W, 2C]");
   const int64_t W = gathered.size(0), C = gathered.size(1) / 2;
   TORCH_CHECK(C >= 64 && C % 64 == 0, "pdt sync bn: C must be a multiple of 64");
   TORCH_CHECK(rank >= 0 && rank < W, "pdt sync bn: rank ", rank, " outside [0, ", W, ")");
-  check_f32_cuda(gathered, W * 2 * C, "gathered");
-  check_f32_cuda(invstd, C, "invstd");
-  TORCH_CHECK(ntot.is_cuda() && ntot.scalar_type() == at::kLong && ntot.numel() == 1, "pdt sync bn: ntot int64 [1]");
-  const float* gp = nullptr;
-  if (weight.has_value() && weight->defined()) {
-    check_f32_cuda(*weight, C, "weight");
-    gp = weight->data_ptr<float>();
-  }
+  TORCH_CHECK(ntot.device() == op.dev && ntot.scalar_type() == at::kLong && ntot.numel() == 1,
+              "pdt sync bn: ntot int64 [1]");
   auto coef = at::empty({3, C}, gathered.options());
-  Tensor dg, db;
-  if (need_dgamma) {
-    dg = at::empty({C}, gathered.options());
-    db = at::empty({C}, gathered.options());
-  }
-  const int rc = pdt_bn_sync_bwd_merge(gathered.data_ptr<float>(), (int)W, (int)rank, (int)C, gp,
-                                       invstd.data_ptr<float>(), ntot.data_ptr<int64_t>(), coef.data_ptr<float>(),
-                                       need_dgamma ? dg.data_ptr<float>() : nullptr,
-                                       need_dgamma ? db.data_ptr<float>() : nullptr, stream());
+  const GammaGrads gg(need_dgamma, C, gathered.options());
+  const int rc = pdt_bn_sync_bwd_merge(f32_ptr(op, "gathered", gathered, W * 2 * C), (int)W, (int)rank, (int)C,
+                                       opt_f32_ptr(op, "weight", weight, C), f32_ptr(op, "invstd", invstd, C),
+                                       ntot.data_ptr<int64_t>(), coef.data_ptr<float>(), gg.dg_ptr(), gg.db_ptr(),
+                                       stream());
   TORCH_CHECK(rc == 0, "pdt_bn_sync_bwd_merge failed: ", rc);
-  return {coef, dg, db};
+  return {coef, gg.dg, gg.db};
 }
 
 // dx = A dz + B (x - mean) + D from coef [3, C] -> {dx, dres = dz (with has_res)}.
 std::vector<Tensor> bn_bwd_apply_coef(Tensor dy, Tensor x, c10::optional<Tensor> mask, Tensor mean, Tensor coef,
                                       bool relu, bool has_res) {
-  check_nhwc_bf16(x, "x");
-  check_nhwc_bf16(dy, "dy");
+  const Op op("bn_bwd_apply_coef", x);
+  check_nhwc_bf16(op, "x", x);
+  check_nhwc_bf16(op, "dy", dy);
   TORCH_CHECK(dy.sizes() == x.sizes() && dy.strides() == x.strides(), "pdt sync bn: dy layout mismatch");
   const int64_t C = x.size(1);
   TORCH_CHECK(C % 64 == 0 && x.numel() > 0, "pdt sync bn: C must be a multiple of 64, M >= 1");
   const int64_t M = x.numel() / C;
-  check_f32_cuda(mean, C, "mean");
-  check_f32_cuda(coef, 3 * C, "coef");
   auto dx = at::empty_like(x);
   Tensor dres;
   if (has_res) dres = at::empty_like(x);
-  const int rc = pdt_bn_bwd_apply_coef(reinterpret_cast<const uint16_t*>(dy.data_ptr()),
-                                       reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                                       relu_mask_ptr(mask, relu, M * C / 8), mean.data_ptr<float>(),
-                                       coef.data_ptr<float>(), M, (int)C, relu, has_res,
-                                       reinterpret_cast<uint16_t*>(dx.data_ptr()),
-                                       has_res ? reinterpret_cast<uint16_t*>(dres.data_ptr()) : nullptr, stream());
+  const int rc = pdt_bn_bwd_apply_coef(bf16_ptr(dy), bf16_ptr(x), relu_mask_ptr(op, mask, relu, M * C / 8),
+                                       f32_ptr(op, "mean", mean, C), f32_ptr(op, "coef", coef, 3 * C), M, (int)C, relu,
+                                       has_res, bf16_out(dx), ptr_or_null<uint16_t>(dres), stream());
   TORCH_CHECK(rc == 0, "pdt_bn_bwd_apply_coef failed: ", rc);
   return {dx, dres};
 }
@@ -945,67 +720,63 @@ std::vector<Tensor> bn_bwd_apply_coef(Tensor dy, Tensor x, c10::optional<Tensor>
 // Returns {dx, dgamma, dbeta}.
 std::vector<Tensor> maxpool3s2_bwd_bn(Tensor dy, Tensor code, Tensor x, c10::optional<Tensor> weight, Tensor mean,
                                       Tensor invstd, bool need_dgamma) {
-  check_nhwc_bf16(dy, "dy");
-  check_nhwc_bf16(x, "x");
+  const Op op("maxpool3s2_bwd_bn", dy);
+  check_nhwc_bf16(op, "dy", dy);
+  check_nhwc_bf16(op, "x", x);
   const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   TORCH_CHECK(C == 64, "maxpool3s2_bwd_bn: C == 64");
   TORCH_CHECK(dy.size(0) == N && dy.size(1) == C && dy.size(2) == (H - 1) / 2 + 1 && dy.size(3) == (W - 1) / 2 + 1,
               "maxpool3s2_bwd_bn: dy shape");
-  TORCH_CHECK(code.scalar_type() == at::kByte && code.numel() == dy.numel(), "maxpool3s2_bwd_bn: code");
   auto dz = at::empty_like(x);
   auto dx = at::empty_like(x);
   auto fopt = x.options().dtype(at::kFloat);
-  Tensor dg, db;
-  if (need_dgamma) {
-    dg = at::empty({C}, fopt);
-    db = at::empty({C}, fopt);
-  }
+  const GammaGrads gg(need_dgamma, C, fopt);
   const int T = pdt_maxpool_bn_parts((int)N, (int)H);
   auto part = at::empty({2 * (int64_t)T * C}, fopt);
   auto ws = at::empty({pdt_bn_tiles_ws_floats(T, (int)C) + 2 * C}, fopt);
-  const int rc = pdt_maxpool3s2_bwd_bn(reinterpret_cast<const uint16_t*>(dy.data_ptr()), code.data_ptr<uint8_t>(),
-                                       reinterpret_cast<uint16_t*>(dz.data_ptr()), (int)N, (int)H, (int)W, (int)C,
-                                       reinterpret_cast<const uint16_t*>(x.data_ptr()), opt_fptr(weight),
-                                       mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                                       reinterpret_cast<uint16_t*>(dx.data_ptr()),
-                                       need_dgamma ? dg.data_ptr<float>() : nullptr,
-                                       need_dgamma ? db.data_ptr<float>() : nullptr, part.data_ptr<float>(),
-                                       ws.data_ptr<float>(), stream());
+  const int rc = pdt_maxpool3s2_bwd_bn(bf16_ptr(dy), u8_ptr(op, "code", code, dy.numel()), bf16_out(dz), (int)N, (int)H,
+                                       (int)W, (int)C, bf16_ptr(x), opt_f32_ptr(op, "weight", weight, C),
+                                       f32_ptr(op, "mean", mean, C), f32_ptr(op, "invstd", invstd, C), bf16_out(dx),
+                                       gg.dg_ptr(), gg.db_ptr(), part.data_ptr<float>(), ws.data_ptr<float>(),
+                                       stream());
   TORCH_CHECK(rc == 0, "pdt_maxpool3s2_bwd_bn failed: ", rc);
-  return {dx, dg, db};
+  return {dx, gg.dg, gg.db};
 }
 
 // Same without the BN apply: returns {dz (the max-pool gradient = dy at the BN output), coef [3, 64]
 // (A, B, D: dx = A dz + B (x - mean) + D), dgamma, dbeta} for stem_conv_wgrad_bn.
 std::vector<Tensor> maxpool3s2_bwd_bn_coef(Tensor dy, Tensor code, Tensor x, c10::optional<Tensor> weight,
                                            Tensor mean, Tensor invstd, bool need_dgamma, bool write_dz) {
-  check_nhwc_bf16(dy, "dy");
-  check_nhwc_bf16(x, "x");
+  const Op op("maxpool3s2_bwd_bn_coef", dy);
+  check_nhwc_bf16(op, "dy", dy);
+  check_nhwc_bf16(op, "x", x);
   const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   TORCH_CHECK(C == 64, "maxpool3s2_bwd_bn_coef: C == 64");
   TORCH_CHECK(dy.size(0) == N && dy.size(1) == C && dy.size(2) == (H - 1) / 2 + 1 && dy.size(3) == (W - 1) / 2 + 1,
               "maxpool3s2_bwd_bn_coef: dy shape");
-  TORCH_CHECK(code.scalar_type() == at::kByte && code.numel() == dy.numel(), "maxpool3s2_bwd_bn_coef: code");
   Tensor dz;
   if (write_dz) dz = at::empty_like(x);
   auto fopt = x.options().dtype(at::kFloat);
   auto coef = at::empty({3, C}, fopt);
-  Tensor dg, db;
-  if (need_dgamma) {
-    dg = at::empty({C}, fopt);
-    db = at::empty({C}, fopt);
-  }
+  const GammaGrads gg(need_dgamma, C, fopt);
   const int T = pdt_maxpool_bn_parts((int)N, (int)H);
   auto part = at::empty({2 * (int64_t)T * C}, fopt);
   auto ws = at::empty({pdt_bn_tiles_ws_floats(T, (int)C) + 2 * C}, fopt);
-  const int rc = pdt_maxpool3s2_bwd_bn_coef(
-      reinterpret_cast<const uint16_t*>(dy.data_ptr()), code.data_ptr<uint8_t>(),
-      write_dz ? reinterpret_cast<uint16_t*>(dz.data_ptr()) : nullptr, (int)N, (int)H, (int)W, (int)C,
-      reinterpret_cast<const uint16_t*>(x.data_ptr()), opt_fptr(weight), mean.data_ptr<float>(),
-      invstd.data_ptr<float>(), coef.data_ptr<float>(), need_dgamma ? dg.data_ptr<float>() : nullptr,
-      need_dgamma ? db.data_ptr<float>() : nullptr, part.data_ptr<float>(), ws.data_ptr<float>(), stream());
+  const int rc = pdt_maxpool3s2_bwd_bn_coef(bf16_ptr(dy), u8_ptr(op, "code", code, dy.numel()),
+                                            ptr_or_null<uint16_t>(dz), (int)N, (int)H, (int)W, (int)C, bf16_ptr(x),
+                                            opt_f32_ptr(op, "weight", weight, C), f32_ptr(op, "mean", mean, C),
+                                            f32_ptr(op, "invstd", invstd, C), coef.data_ptr<float>(), gg.dg_ptr(),
+                                            gg.db_ptr(), part.data_ptr<float>(), ws.data_ptr<float>(), stream());
   TORCH_CHECK(rc == 0, "pdt_maxpool3s2_bwd_bn_coef failed: ", rc);
-  return {dz, coef, dg, db};
+  return {dz, coef, gg.dg, gg.db};
+}
+
+// The per-tile partials [2, T, C] fp32 a producer op left for a BatchNorm over C channels; returns T.
+int64_t check_tile_parts(const Op& op, const Tensor& part, int64_t C) {
+  TORCH_CHECK(part.dim() == 3 && part.size(0) == 2 && part.size(1) >= 1 && part.size(2) == C, op.name,
+              ": partials [2, T, C] fp32 expected");
+  f32_ptr(op, "part", part, part.numel());
+  return part.size(1);
 }
 
 // BN training backward with the reduction taken from the dy producer's per-tile partials
@@ -1013,40 +784,29 @@ std::vector<Tensor> maxpool3s2_bwd_bn_coef(Tensor dy, Tensor code, Tensor x, c10
 std::vector<Tensor> bn_bwd_train_tiles(Tensor dy, Tensor x, Tensor part, c10::optional<Tensor> mask,
                                        c10::optional<Tensor> weight, Tensor mean, Tensor invstd, bool relu,
                                        bool has_res, bool need_dgamma) {
-  check_nhwc_bf16(x, "x");
+  const Op op("bn_bwd_train_tiles", x);
+  check_nhwc_bf16(op, "x", x);
+  check_nhwc_bf16(op, "dy", dy);
   TORCH_CHECK(dy.sizes() == x.sizes() && dy.strides() == x.strides(), "pdt bn bwd: dy layout mismatch");
   const int64_t C = x.size(1);
   const int64_t M = x.numel() / C;
   const int BMt = pdt_conv1x1_tile_rows();
-  // any tile count: backward partials are plain sums (stride-2 data gradient: 4 phases of tiles)
-  const int64_t T = part.dim() == 3 ? part.size(1) : 0;
   TORCH_CHECK(C % 64 == 0, "pdt bn bwd: C must be a multiple of 64");
-  TORCH_CHECK(part.scalar_type() == at::kFloat && part.is_contiguous() && part.dim() == 3 && part.size(0) == 2 &&
-              T >= 1 && part.size(2) == C, "bn_bwd_train_tiles: partials [2, T, C] fp32 expected");
+  // any tile count: backward partials are plain sums (stride-2 data gradient: 4 phases of tiles)
+  const int64_t T = check_tile_parts(op, part, C);
   auto dx = at::empty_like(x);
   Tensor dres;
   if (has_res) dres = at::empty_like(x);
   auto fopt = x.options().dtype(at::kFloat);
-  Tensor dg, db;
-  if (need_dgamma) {
-    dg = at::empty({C}, fopt);
-    db = at::empty({C}, fopt);
-  }
+  const GammaGrads gg(need_dgamma, C, fopt);
   auto ws = at::empty({pdt_bn_tiles_ws_floats((int)T, (int)C) + 2 * C}, fopt);
-  const uint8_t* mp = nullptr;
-  if (relu) {
-    TORCH_CHECK(mask.has_value() && mask->defined() && mask->numel() == M * C / 8, "pdt bn bwd: relu needs the mask");
-    mp = mask->data_ptr<uint8_t>();
-  }
-  const int rc = pdt_bn_bwd_train_tiles(part.data_ptr<float>(), (int)T, BMt, reinterpret_cast<const uint16_t*>(dy.data_ptr()),
-                                        reinterpret_cast<const uint16_t*>(x.data_ptr()), mp, opt_fptr(weight),
-                                        mean.data_ptr<float>(), invstd.data_ptr<float>(), M, (int)C, relu, has_res,
-                                        reinterpret_cast<uint16_t*>(dx.data_ptr()),
-                                        has_res ? reinterpret_cast<uint16_t*>(dres.data_ptr()) : nullptr,
-                                        need_dgamma ? dg.data_ptr<float>() : nullptr,
-                                        need_dgamma ? db.data_ptr<float>() : nullptr, ws.data_ptr<float>(), stream());
+  const int rc = pdt_bn_bwd_train_tiles(part.data_ptr<float>(), (int)T, BMt, bf16_ptr(dy), bf16_ptr(x),
+                                        relu_mask_ptr(op, mask, relu, M * C / 8), opt_f32_ptr(op, "weight", weight, C),
+                                        f32_ptr(op, "mean", mean, C), f32_ptr(op, "invstd", invstd, C), M, (int)C, relu,
+                                        has_res, bf16_out(dx), ptr_or_null<uint16_t>(dres), gg.dg_ptr(), gg.db_ptr(),
+                                        ws.data_ptr<float>(), stream());
   TORCH_CHECK(rc == 0, "pdt_bn_bwd_train_tiles failed: ", rc);
-  return {dx, dres, dg, db};
+  return {dx, dres, gg.dg, gg.db};
 }
 
 // BN training backward WITHOUT the apply: {coef [3, C] (A, B, D: dx = A dy m + B (x - mean) + D),
@@ -1054,41 +814,32 @@ std::vector<Tensor> bn_bwd_train_tiles(Tensor dy, Tensor x, Tensor part, c10::op
 // reduction comes from the dy producer's partials [2, T, C] when given, else from a pass over (dy, x).
 std::vector<Tensor> bn_bwd_coef(Tensor dy, Tensor x, c10::optional<Tensor> part, c10::optional<Tensor> mask,
                                 c10::optional<Tensor> weight, Tensor mean, Tensor invstd, bool relu, bool need_dgamma) {
-  check_nhwc_bf16(x, "x");
+  const Op op("bn_bwd_coef", x);
+  check_nhwc_bf16(op, "x", x);
   const int64_t C = x.size(1);
   const int64_t M = x.numel() / C;
   TORCH_CHECK(C % 64 == 0, "pdt bn coef: C must be a multiple of 64");
   auto fopt = x.options().dtype(at::kFloat);
   auto coef = at::empty({3, C}, fopt);
-  Tensor dg, db;
-  if (need_dgamma) {
-    dg = at::empty({C}, fopt);
-    db = at::empty({C}, fopt);
-  }
+  const GammaGrads gg(need_dgamma, C, fopt);
+  const float* gp = opt_f32_ptr(op, "weight", weight, C);
+  const float* ip = f32_ptr(op, "invstd", invstd, C);
   int rc;
-  if (part.has_value() && part->defined()) {
-    TORCH_CHECK(part->scalar_type() == at::kFloat && part->is_contiguous() && part->dim() == 3 && part->size(0) == 2 &&
-                part->size(1) >= 1 && part->size(2) == C, "bn_bwd_coef: partials [2, T, C] fp32 expected");
-    const int T = (int)part->size(1);
+  if (has(part)) {
+    const int T = (int)check_tile_parts(op, *part, C);
     auto ws = at::empty({pdt_bn_tiles_ws_floats(T, (int)C)}, fopt);
-    rc = pdt_bn_bwd_coef_tiles(part->data_ptr<float>(), T, opt_fptr(weight), invstd.data_ptr<float>(), M, (int)C,
-                               coef.data_ptr<float>(), need_dgamma ? dg.data_ptr<float>() : nullptr,
-                               need_dgamma ? db.data_ptr<float>() : nullptr, ws.data_ptr<float>(), stream());
+    rc = pdt_bn_bwd_coef_tiles(part->data_ptr<float>(), T, gp, ip, M, (int)C, coef.data_ptr<float>(), gg.dg_ptr(),
+                               gg.db_ptr(), ws.data_ptr<float>(), stream());
   } else {
+    check_nhwc_bf16(op, "dy", dy);
     TORCH_CHECK(dy.sizes() == x.sizes() && dy.strides() == x.strides(), "pdt bn coef: dy layout mismatch");
-    const uint8_t* mp = nullptr;
-    if (relu) {
-      TORCH_CHECK(mask.has_value() && mask->defined() && mask->numel() == M * C / 8, "pdt bn coef: relu needs the mask");
-      mp = mask->data_ptr<uint8_t>();
-    }
     auto ws = at::empty({bn_ws_floats(M, C)}, fopt);
-    rc = pdt_bn_bwd_coef(reinterpret_cast<const uint16_t*>(dy.data_ptr()), reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                         mp, opt_fptr(weight), mean.data_ptr<float>(), invstd.data_ptr<float>(), M, (int)C, relu,
-                         coef.data_ptr<float>(), need_dgamma ? dg.data_ptr<float>() : nullptr,
-                         need_dgamma ? db.data_ptr<float>() : nullptr, ws.data_ptr<float>(), bn_counters(x), stream());
+    rc = pdt_bn_bwd_coef(bf16_ptr(dy), bf16_ptr(x), relu_mask_ptr(op, mask, relu, M * C / 8), gp,
+                         f32_ptr(op, "mean", mean, C), ip, M, (int)C, relu, coef.data_ptr<float>(), gg.dg_ptr(),
+                         gg.db_ptr(), ws.data_ptr<float>(), bn_counters(x), stream());
   }
   TORCH_CHECK(rc == 0, "pdt bn_bwd_coef failed: ", rc);
-  return {coef, dg, db};
+  return {coef, gg.dg, gg.db};
 }
 
 // Fused backward of a bottleneck's last 1x1 conv (w [C4, CW, 1, 1]: CW -> C4) and the BatchNorm that
@@ -1104,25 +855,23 @@ std::vector<Tensor> conv1x1_bwd_fused(Tensor dy, Tensor z, Tensor mz, Tensor mea
                                       c10::optional<Tensor> bn_x, c10::optional<Tensor> bn_mask,
                                       c10::optional<Tensor> bn_mean, c10::optional<Tensor> xcoef,
                                       c10::optional<Tensor> wt_pre) {
-  check_nhwc_bf16(dy, "dy");
-  check_nhwc_bf16(z, "z");
-  TORCH_CHECK(xa.dim() == 4 && xa.is_cuda() && xa.scalar_type() == at::kBFloat16, "conv1x1_bwd_fused: xa");
-  const bool recomp = xcoef.has_value() && xcoef->defined();
-  if (!recomp) check_nhwc_bf16(xa, "xa");
+  const Op op("conv1x1_bwd_fused", dy);
+  check_nhwc_bf16(op, "dy", dy);
+  check_nhwc_bf16(op, "z", z);
+  TORCH_CHECK(xa.dim() == 4 && xa.device() == op.dev && xa.scalar_type() == at::kBFloat16, "conv1x1_bwd_fused: xa");
+  const bool recomp = has(xcoef);
+  if (!recomp) check_nhwc_bf16(op, "xa", xa);
   const int64_t C4 = z.size(1), CW = xa.size(1);
   const int64_t M = z.numel() / C4;
   if (!pdt_conv1x1_bwd_fused_ok((int)C4, (int)CW) || M * C4 >= ((int64_t)1 << 31)) return {};
   TORCH_CHECK(dy.sizes() == z.sizes() && dy.strides() == z.strides(), "conv1x1_bwd_fused: dy / z layout mismatch");
   TORCH_CHECK(xa.numel() == M * CW, "conv1x1_bwd_fused: xa pixels");
-  TORCH_CHECK(mz.scalar_type() == at::kByte && mz.numel() == M * C4 / 8 && mz.is_cuda(), "conv1x1_bwd_fused: mask");
-  TORCH_CHECK(mean.scalar_type() == at::kFloat && mean.numel() == C4 && coef.scalar_type() == at::kFloat &&
-              coef.is_contiguous() && coef.numel() == 3 * C4, "conv1x1_bwd_fused: mean [C4], coef [3, C4] fp32");
-  TORCH_CHECK(w.scalar_type() == at::kBFloat16 && w.numel() == C4 * CW && w.size(0) == C4,
+  TORCH_CHECK(w.scalar_type() == at::kBFloat16 && w.numel() == C4 * CW && w.size(0) == C4 && w.device() == op.dev,
               "conv1x1_bwd_fused: weight [C4, CW, 1, 1] bf16");
   Tensor wt;
-  if (wt_pre.has_value() && wt_pre->defined()) {  // W^T from the step's batched weight prep
+  if (has(wt_pre)) {  // W^T from the step's batched weight prep
     TORCH_CHECK(wt_pre->scalar_type() == at::kBFloat16 && wt_pre->is_contiguous() && wt_pre->dim() == 2 &&
-                    wt_pre->size(0) == CW && wt_pre->size(1) == C4,
+                    wt_pre->size(0) == CW && wt_pre->size(1) == C4 && wt_pre->device() == op.dev,
                 "conv1x1_bwd_fused: wt [CW, C4] bf16");
     wt = *wt_pre;
   } else {
@@ -1133,43 +882,26 @@ std::vector<Tensor> conv1x1_bwd_fused(Tensor dy, Tensor z, Tensor mz, Tensor mea
   const int G = pdt_conv1x1_bwd_fused_grid((int)M, (int)C4, (int)CW);
   auto fopt = z.options().dtype(at::kFloat);
   auto ws = at::empty({(int64_t)G * C4 * CW}, fopt);
-  const bool bst = bn_x.has_value() && bn_x->defined();
   Tensor part;
-  const uint16_t* bx = nullptr;
-  const uint8_t* bm = nullptr;
-  const float* bmu = nullptr;
-  if (bst) {
-    check_nhwc_bf16(*bn_x, "bn_x");
-    TORCH_CHECK(bn_x->numel() == M * CW && bn_mean.has_value() && bn_mean->defined() &&
-                bn_mean->scalar_type() == at::kFloat && bn_mean->numel() == CW, "conv1x1_bwd_fused: bn_x / bn_mean");
-    if (bn_mask.has_value() && bn_mask->defined()) {
-      TORCH_CHECK(bn_mask->scalar_type() == at::kByte && bn_mask->numel() == M * CW / 8, "conv1x1_bwd_fused: bn_mask");
-      bm = bn_mask->data_ptr<uint8_t>();
-    }
-    bx = reinterpret_cast<const uint16_t*>(bn_x->data_ptr());
-    bmu = bn_mean->data_ptr<float>();
+  BnSide bn;
+  if (has(bn_x)) {
+    bn = bn_side(op, bn_x, bn_mask, bn_mean, M, CW, false);
     part = at::empty({2, G, CW}, fopt);
   }
   const float* xcp = nullptr;
   uint8_t* mout = nullptr;
   if (recomp) {
-    TORCH_CHECK(bst && bm, "conv1x1_bwd_fused: xcoef needs bn_x, bn_mean and the bn_mask output");
-    TORCH_CHECK(xcoef->scalar_type() == at::kFloat && xcoef->is_contiguous() && xcoef->numel() == 2 * CW,
-                "conv1x1_bwd_fused: xcoef [2, CW] fp32");
-    xcp = xcoef->data_ptr<float>();
+    TORCH_CHECK(bn.x && bn.mask, "conv1x1_bwd_fused: xcoef needs bn_x, bn_mean and the bn_mask output");
+    xcp = f32_ptr(op, "xcoef", *xcoef, 2 * CW);
     mout = bn_mask->data_ptr<uint8_t>();
-    bm = nullptr;
+    bn.mask = nullptr;
   }
-  const float* cp = coef.data_ptr<float>();
-  const int rc = pdt_conv1x1_bwd_fused(reinterpret_cast<const uint16_t*>(dy.data_ptr()),
-                                       reinterpret_cast<const uint16_t*>(z.data_ptr()), mz.data_ptr<uint8_t>(),
-                                       mean.data_ptr<float>(), cp, cp + C4, cp + 2 * C4,
-                                       reinterpret_cast<const uint16_t*>(wt.data_ptr()),
-                                       recomp ? nullptr : reinterpret_cast<const uint16_t*>(xa.data_ptr()), bx, bm, bmu,
-                                       bst ? part.data_ptr<float>() : nullptr, xcp, mout,
-                                       reinterpret_cast<uint16_t*>(dxa.data_ptr()),
-                                       reinterpret_cast<uint16_t*>(dw.data_ptr()), ws.data_ptr<float>(), (int)M, (int)C4,
-                                       (int)CW, stream());
+  const float* cp = f32_ptr(op, "coef", coef, 3 * C4);
+  const int rc = pdt_conv1x1_bwd_fused(bf16_ptr(dy), bf16_ptr(z), u8_ptr(op, "mz", mz, M * C4 / 8),
+                                       f32_ptr(op, "mean", mean, C4), cp, cp + C4, cp + 2 * C4, bf16_ptr(wt),
+                                       recomp ? nullptr : bf16_ptr(xa), bn.x, bn.mask, bn.mean,
+                                       ptr_or_null<float>(part), xcp, mout, bf16_out(dxa), bf16_out(dw),
+                                       ws.data_ptr<float>(), (int)M, (int)C4, (int)CW, stream());
   TORCH_CHECK(rc == 0, "pdt_conv1x1_bwd_fused failed: ", rc);
   return {dxa, dw.view(w.sizes()), part};
 }
@@ -1234,6 +966,12 @@ std::vector<Tensor> lenet_tail_bwd(Tensor dl, Tensor p1, std::vector<Tensor> w, 
 }
 
 // ----------------------------------------------------------------------------- 1x1 conv GEMM (+ BN stats)
+// A row-major GEMM operand: 2-D contiguous bf16 on the op's device.
+void check_mat_bf16(const Op& op, const char* name, const Tensor& t) {
+  TORCH_CHECK(t.defined() && t.device() == op.dev && t.scalar_type() == at::kBFloat16 && t.dim() == 2 &&
+                  t.is_contiguous(), op.name, ": ", name, " must be 2-D contiguous bf16 on ", op.dev);
+}
+
 // out[M,N] = a[M,K] @ b[N,K]^T (+ out, when acc: in-place accumulate). a, b, out: row-major bf16
 // (a 1x1 conv's channels_last activations viewed as [N*H*W, C]). stats: also return the per-tile
 // partials [2, T, N] fp32 (tile sums, centred tile sums of squares; T = ceil(M / 256)).
@@ -1247,77 +985,47 @@ c10::optional<Tensor> conv1x1_gemm(Tensor a, Tensor b, Tensor out, bool acc, boo
                                    c10::optional<Tensor> bn_x, c10::optional<Tensor> bn_mask,
                                    c10::optional<Tensor> bn_mean, int64_t c_stride, int64_t c_H, int64_t c_W,
                                    c10::optional<Tensor> a_coef, bool bn_sum_only, bool no_store) {
-  for (const Tensor* t : {&a, &b, &out}) {
-    check_cuda(*t, "conv1x1_gemm operand");
-    TORCH_CHECK(t->scalar_type() == at::kBFloat16 && t->dim() == 2 && t->is_contiguous(),
-                "conv1x1_gemm: operands must be 2-D contiguous bf16");
-  }
+  const Op op("conv1x1_gemm", a);
+  check_mat_bf16(op, "a", a);
+  check_mat_bf16(op, "b", b);
+  check_mat_bf16(op, "out", out);
   const int64_t M = a.size(0), K = a.size(1), N = b.size(0);
   TORCH_CHECK(b.size(1) == K && out.size(0) == M && out.size(1) == N, "conv1x1_gemm: shape mismatch");
   TORCH_CHECK(K % 32 == 0 && N % 64 == 0, "conv1x1_gemm: K % 32 == 0 and N % 64 == 0 required");
   TORCH_CHECK(!(acc && stats), "conv1x1_gemm: acc and stats are exclusive");
   // acc source: out itself (in place), or c_in [M, N] (then optionally masked by c_mask, M*N/8 bytes)
-  const uint16_t* cp = acc ? reinterpret_cast<const uint16_t*>(out.data_ptr()) : nullptr;
-  const uint8_t* mp = nullptr;
-  if (c_in.has_value() && c_in->defined()) {
+  const uint16_t* cp = acc ? bf16_ptr(out) : nullptr;
+  if (has(c_in)) {
     TORCH_CHECK(acc, "conv1x1_gemm: c_in needs acc");
-    check_cuda(*c_in, "c_in");
     // c_stride > 0: c_in is the compact [M / (c_H c_W) * Hs * Ws, N] gradient of a stride subsampling
     TORCH_CHECK(c_stride <= 0 || (c_H > 0 && c_W > 0 && M % (c_H * c_W) == 0), "conv1x1_gemm: c_H * c_W must divide M");
-    TORCH_CHECK(c_stride <= 0 || !(c_mask.has_value() && c_mask->defined()), "conv1x1_gemm: c_stride excludes c_mask");
+    TORCH_CHECK(c_stride <= 0 || !has(c_mask), "conv1x1_gemm: c_stride excludes c_mask");
     const int64_t cm_rows = c_stride > 0 ? M / (c_H * c_W) * ((c_H - 1) / c_stride + 1) * ((c_W - 1) / c_stride + 1) : M;
-    TORCH_CHECK(c_in->scalar_type() == at::kBFloat16 && c_in->numel() == cm_rows * N && c_in->is_contiguous(
-                    c_in->dim() == 4 ? at::MemoryFormat::ChannelsLast : at::MemoryFormat::Contiguous),
+    TORCH_CHECK(c_in->device() == op.dev && c_in->scalar_type() == at::kBFloat16 && c_in->numel() == cm_rows * N &&
+                    c_in->is_contiguous(c_in->dim() == 4 ? at::MemoryFormat::ChannelsLast
+                                                         : at::MemoryFormat::Contiguous),
                 "conv1x1_gemm: c_in must be [M, N] bf16 (channels_last when 4-D)");
-    cp = reinterpret_cast<const uint16_t*>(c_in->data_ptr());
+    cp = bf16_ptr(*c_in);
   }
-  if (c_mask.has_value() && c_mask->defined()) {
-    TORCH_CHECK(acc && c_mask->scalar_type() == at::kByte && c_mask->numel() == M * N / 8,
-                "conv1x1_gemm: c_mask must be uint8 [M * N / 8] with acc");
-    mp = c_mask->data_ptr<uint8_t>();
-  }
-  TORCH_CHECK(c_stride <= 0 || (c_in.has_value() && c_in->defined()), "conv1x1_gemm: c_stride needs c_in");
+  TORCH_CHECK(acc || !has(c_mask), "conv1x1_gemm: c_mask must be uint8 [M * N / 8] with acc");
+  const uint8_t* mp = opt_u8_ptr(op, "c_mask", c_mask, M * N / 8);
+  TORCH_CHECK(c_stride <= 0 || has(c_in), "conv1x1_gemm: c_stride needs c_in");
   c10::optional<Tensor> part;
   const int64_t T = (M + pdt_conv1x1_tile_rows() - 1) / pdt_conv1x1_tile_rows();
   if (stats) part = at::empty({2, T, N}, a.options().dtype(at::kFloat));
   // bn_sum_only: the BatchNorm input is not read; only the partials' sum(dz) row is meaningful (ALG backward)
-  const bool bstats = (bn_x.has_value() && bn_x->defined()) || bn_sum_only;
-  const uint16_t* bx = nullptr;
-  const uint8_t* bm = nullptr;
-  const float* bmean = nullptr;
+  const bool bstats = has(bn_x) || bn_sum_only;
+  BnSide bn;
   if (bstats) {
     TORCH_CHECK(!stats, "conv1x1_gemm: stats and bn_x are exclusive");
-    if (!bn_sum_only) {
-      check_cuda(*bn_x, "bn_x");
-      TORCH_CHECK(bn_x->scalar_type() == at::kBFloat16 && bn_x->numel() == M * N && bn_x->is_contiguous(
-                      bn_x->dim() == 4 ? at::MemoryFormat::ChannelsLast : at::MemoryFormat::Contiguous),
-                  "conv1x1_gemm: bn_x must be [M, N] bf16 (channels_last when 4-D)");
-      bx = reinterpret_cast<const uint16_t*>(bn_x->data_ptr());
-    }
-    TORCH_CHECK(bn_mean.has_value() && bn_mean->defined() && bn_mean->scalar_type() == at::kFloat &&
-                bn_mean->numel() == N && bn_mean->is_contiguous() && bn_mean->is_cuda(),
-                "conv1x1_gemm: bn_mean must be fp32 [N]");
-    if (bn_mask.has_value() && bn_mask->defined()) {
-      TORCH_CHECK(bn_mask->scalar_type() == at::kByte && bn_mask->numel() == M * N / 8 && bn_mask->is_cuda(),
-                  "conv1x1_gemm: bn_mask must be uint8 [M * N / 8]");
-      bm = bn_mask->data_ptr<uint8_t>();
-    }
-    bmean = bn_mean->data_ptr<float>();
+    bn = bn_side(op, bn_x, bn_mask, bn_mean, M, N, bn_sum_only);
     part = at::empty({2, T, N}, a.options().dtype(at::kFloat));
   }
-  const float* acp = nullptr;
-  if (a_coef.has_value() && a_coef->defined()) {
-    TORCH_CHECK(!acc && !bstats, "conv1x1_gemm: a_coef is forward-only (no acc / bn_x)");
-    TORCH_CHECK(a_coef->scalar_type() == at::kFloat && a_coef->is_contiguous() && a_coef->numel() == 2 * K &&
-                a_coef->is_cuda(), "conv1x1_gemm: a_coef must be fp32 [2, K]");
-    acp = a_coef->data_ptr<float>();
-  }
-  const int rc = pdt_conv1x1_gemm(reinterpret_cast<const uint16_t*>(a.data_ptr()),
-                                  reinterpret_cast<const uint16_t*>(b.data_ptr()),
-                                  reinterpret_cast<uint16_t*>(out.data_ptr()), cp, mp,
-                                  stats ? part->data_ptr<float>() : nullptr, (int)M, (int)K, (int)N, bx, bm, bmean,
-                                  bstats ? part->data_ptr<float>() : nullptr, (int)c_stride, (int)c_H, (int)c_W, acp,
-                                  stream(), no_store ? 1 : 0);
+  TORCH_CHECK(!has(a_coef) || (!acc && !bstats), "conv1x1_gemm: a_coef is forward-only (no acc / bn_x)");
+  const int rc = pdt_conv1x1_gemm(bf16_ptr(a), bf16_ptr(b), bf16_out(out), cp, mp,
+                                  stats ? part->data_ptr<float>() : nullptr, (int)M, (int)K, (int)N, bn.x, bn.mask,
+                                  bn.mean, bstats ? part->data_ptr<float>() : nullptr, (int)c_stride, (int)c_H,
+                                  (int)c_W, opt_f32_ptr(op, "a_coef", a_coef, 2 * K), stream(), no_store ? 1 : 0);
   TORCH_CHECK(rc == 0, "pdt_conv1x1_gemm failed: ", rc);
   return part;
 }
@@ -1329,33 +1037,21 @@ c10::optional<Tensor> conv1x1_gemm(Tensor a, Tensor b, Tensor out, bool acc, boo
 // Returns {y, mask uint8 [M * N / 8]}.
 std::vector<Tensor> conv1x1_gemm_apply(Tensor a, Tensor b, Tensor res, Tensor ab, c10::optional<Tensor> rab,
                                        c10::optional<Tensor> a_coef) {
-  check_cuda(a, "a");
-  check_cuda(b, "b");
-  check_cuda(res, "res");
-  TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && a.size(1) == b.size(1) && a.scalar_type() == at::kBFloat16 &&
-                  b.scalar_type() == at::kBFloat16 && a.is_contiguous() && b.is_contiguous(),
-              "conv1x1_gemm_apply: a [M, K], b [N, K] contiguous bf16");
+  const Op op("conv1x1_gemm_apply", a);
+  check_mat_bf16(op, "a", a);
+  check_mat_bf16(op, "b", b);
+  TORCH_CHECK(a.size(1) == b.size(1), "conv1x1_gemm_apply: a [M, K], b [N, K] contiguous bf16");
   const int64_t M = a.size(0), K = a.size(1), N = b.size(0);
   const auto fmt = res.dim() == 4 ? at::MemoryFormat::ChannelsLast : at::MemoryFormat::Contiguous;
-  TORCH_CHECK(res.scalar_type() == at::kBFloat16 && res.numel() == M * N && res.is_contiguous(fmt) &&
-                  (res.dim() != 4 || res.size(1) == N),
+  TORCH_CHECK(res.device() == op.dev && res.scalar_type() == at::kBFloat16 && res.numel() == M * N &&
+                  res.is_contiguous(fmt) && (res.dim() != 4 || res.size(1) == N),
               "conv1x1_gemm_apply: res must be [M, N] bf16 (channels_last when 4-D)");
-  auto f32 = [&](const Tensor& t, int64_t n, const char* what) {
-    check_cuda(t, what);
-    TORCH_CHECK(t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == n, "conv1x1_gemm_apply: ", what,
-                " must be fp32 contiguous with ", n, " elements");
-    return t.data_ptr<float>();
-  };
-  const float* abp = f32(ab, 2 * N, "ab");
-  const float* rabp = (rab.has_value() && rab->defined()) ? f32(*rab, 2 * N, "rab") : nullptr;
-  const float* acp = (a_coef.has_value() && a_coef->defined()) ? f32(*a_coef, 2 * K, "a_coef") : nullptr;
   auto y = at::empty_like(res, res.options(), fmt);
   auto mask = at::empty({M * N / 8}, res.options().dtype(at::kByte));
-  const int rc = pdt_conv1x1_gemm_apply(reinterpret_cast<const uint16_t*>(a.data_ptr()),
-                                        reinterpret_cast<const uint16_t*>(b.data_ptr()),
-                                        reinterpret_cast<uint16_t*>(y.data_ptr()),
-                                        reinterpret_cast<const uint16_t*>(res.data_ptr()), abp, rabp,
-                                        mask.data_ptr<uint8_t>(), (int)M, (int)K, (int)N, acp, stream());
+  const int rc = pdt_conv1x1_gemm_apply(bf16_ptr(a), bf16_ptr(b), bf16_out(y), bf16_ptr(res),
+                                        f32_ptr(op, "ab", ab, 2 * N), opt_f32_ptr(op, "rab", rab, 2 * N),
+                                        mask.data_ptr<uint8_t>(), (int)M, (int)K, (int)N,
+                                        opt_f32_ptr(op, "a_coef", a_coef, 2 * K), stream());
   TORCH_CHECK(rc == 0, "pdt_conv1x1_gemm_apply failed: ", rc);
   return {y, mask};
 }
@@ -1365,6 +1061,8 @@ std::vector<Tensor> conv1x1_gemm_apply(Tensor a, Tensor b, Tensor res, Tensor ab
 // W^T [Ci, Co] contiguous; k = 3: the flipped transposed weights [Ci, Co, 3, 3] channels_last (= conv3x3_flip).
 void weight_prep(std::vector<Tensor> src, std::vector<Tensor> dst) {
   TORCH_CHECK(src.size() == dst.size(), "weight_prep: src / dst lists differ");
+  if (src.empty()) return;
+  const Op op("weight_prep", src[0]);
   const int cap = pdt_weight_prep_max_items();
   std::vector<const uint16_t*> sp;
   std::vector<uint16_t*> dp;
@@ -1378,8 +1076,7 @@ void weight_prep(std::vector<Tensor> src, std::vector<Tensor> dst) {
   for (size_t i = 0; i < src.size(); ++i) {
     const Tensor& w = src[i];
     const Tensor& d = dst[i];
-    check_cuda(w, "src");
-    check_cuda(d, "dst");
+    TORCH_CHECK(w.device() == op.dev && d.device() == op.dev, "weight_prep: src / dst must be on ", op.dev);
     TORCH_CHECK(w.dim() == 4 && w.scalar_type() == at::kBFloat16 && d.scalar_type() == at::kBFloat16 &&
                     w.size(2) == w.size(3) && (w.size(2) == 1 || w.size(2) == 3),
                 "weight_prep: bf16 [Co, Ci, k, k] weights, k = 1 or 3");
@@ -1393,8 +1090,8 @@ void weight_prep(std::vector<Tensor> src, std::vector<Tensor> dst) {
                       d.is_contiguous(at::MemoryFormat::ChannelsLast),
                   "weight_prep: dst [Ci, Co, 3, 3] channels_last");
     }
-    sp.push_back(reinterpret_cast<const uint16_t*>(w.data_ptr()));
-    dp.push_back(reinterpret_cast<uint16_t*>(d.data_ptr()));
+    sp.push_back(bf16_ptr(w));
+    dp.push_back(bf16_out(d));
     R.push_back((int)Co);
     C.push_back((int)Ci);
     T.push_back((int)(k * k));
@@ -1407,12 +1104,10 @@ void weight_prep(std::vector<Tensor> src, std::vector<Tensor> dst) {
 // dy[M, Co]^T x[M, Ci] from the row-major bf16 NHWC views (split-K over pixels, fixed-order fp32
 // reduction). Returns an undefined tensor for a shape the kernel does not take (caller falls back).
 Tensor conv1x1_wgrad(Tensor x, Tensor dy) {
-  check_cuda(x, "x");
-  check_cuda(dy, "dy");
-  TORCH_CHECK(x.dim() == 2 && dy.dim() == 2 && x.size(0) == dy.size(0), "conv1x1_wgrad: x [M, Ci], dy [M, Co]");
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && dy.scalar_type() == at::kBFloat16 && x.is_contiguous() &&
-                  dy.is_contiguous(),
-              "conv1x1_wgrad: contiguous bf16 operands");
+  const Op op("conv1x1_wgrad", x);
+  check_mat_bf16(op, "x", x);
+  check_mat_bf16(op, "dy", dy);
+  TORCH_CHECK(x.size(0) == dy.size(0), "conv1x1_wgrad: x [M, Ci], dy [M, Co]");
   const int64_t M = x.size(0), Ci = x.size(1), Co = dy.size(1);
   if (M * std::max(Ci, Co) >= ((int64_t)1 << 31)) return Tensor();
   int ns = 0;
@@ -1420,9 +1115,7 @@ Tensor conv1x1_wgrad(Tensor x, Tensor dy) {
   if (wsf == 0) return Tensor();
   auto ws = at::empty({wsf}, x.options().dtype(at::kFloat));
   auto dw = at::empty({Co, Ci}, x.options());
-  const int rc = pdt_conv1x1_wgrad(reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                                   reinterpret_cast<const uint16_t*>(dy.data_ptr()),
-                                   reinterpret_cast<uint16_t*>(dw.data_ptr()), ws.data_ptr<float>(), (int)M, (int)Ci,
+  const int rc = pdt_conv1x1_wgrad(bf16_ptr(x), bf16_ptr(dy), bf16_out(dw), ws.data_ptr<float>(), (int)M, (int)Ci,
                                    (int)Co, stream());
   if (rc == -1 || rc == -2) return Tensor();
   TORCH_CHECK(rc == 0, "pdt_conv1x1_wgrad failed: ", rc);
@@ -1433,11 +1126,11 @@ Tensor conv1x1_wgrad(Tensor x, Tensor dy) {
 // rows co1 + co2 (+ the ones block: column sums of x). x [M, Ci], dy1 [M, co1], dy2 [M, co2] contiguous bf16.
 // Returns an empty tensor for an unsupported shape.
 Tensor conv1x1_wgrad_seg(Tensor x, Tensor dy1, Tensor dy2) {
-  for (const Tensor* t : {&x, &dy1, &dy2}) {
-    check_cuda(*t, "conv1x1_wgrad_seg operand");
-    TORCH_CHECK(t->dim() == 2 && t->scalar_type() == at::kBFloat16 && t->is_contiguous() && t->size(0) == x.size(0),
-                "conv1x1_wgrad_seg: contiguous bf16 [M, *] operands");
-  }
+  const Op op("conv1x1_wgrad_seg", x);
+  check_mat_bf16(op, "x", x);
+  check_mat_bf16(op, "dy1", dy1);
+  check_mat_bf16(op, "dy2", dy2);
+  TORCH_CHECK(dy1.size(0) == x.size(0) && dy2.size(0) == x.size(0), "conv1x1_wgrad_seg: contiguous bf16 [M, *] operands");
   const int64_t M = x.size(0), Ci = x.size(1), co1 = dy1.size(1), co2 = dy2.size(1);
   if (M * std::max(std::max(Ci, co1), co2) >= ((int64_t)1 << 31)) return Tensor();
   int rows = 0;
@@ -1445,10 +1138,8 @@ Tensor conv1x1_wgrad_seg(Tensor x, Tensor dy1, Tensor dy2) {
   if (wsf == 0) return Tensor();
   auto ws = at::empty({wsf}, x.options().dtype(at::kFloat));
   auto out = at::empty({rows, Ci}, x.options().dtype(at::kFloat));
-  const int rc = pdt_conv1x1_wgrad_seg(reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                                       reinterpret_cast<const uint16_t*>(dy1.data_ptr()), (int)co1,
-                                       reinterpret_cast<const uint16_t*>(dy2.data_ptr()), (int)co2, out.data_ptr<float>(),
-                                       ws.data_ptr<float>(), (int)M, (int)Ci, stream());
+  const int rc = pdt_conv1x1_wgrad_seg(bf16_ptr(x), bf16_ptr(dy1), (int)co1, bf16_ptr(dy2), (int)co2,
+                                       out.data_ptr<float>(), ws.data_ptr<float>(), (int)M, (int)Ci, stream());
   if (rc == -1 || rc == -2) return Tensor();
   TORCH_CHECK(rc == 0, "pdt_conv1x1_wgrad_seg failed: ", rc);
   return out;
@@ -1459,129 +1150,94 @@ Tensor conv1x1_wgrad_seg(Tensor x, Tensor dy1, Tensor dy2) {
 c10::optional<Tensor> conv1x1_gemm_seg(Tensor a1, Tensor a2, int64_t rep2, Tensor b, Tensor out,
                                        c10::optional<Tensor> bn_x, c10::optional<Tensor> bn_mask,
                                        c10::optional<Tensor> bn_mean) {
-  for (const Tensor* t : {&a1, &a2, &b, &out}) {
-    check_cuda(*t, "conv1x1_gemm_seg operand");
-    TORCH_CHECK(t->scalar_type() == at::kBFloat16 && t->dim() == 2 && t->is_contiguous(),
-                "conv1x1_gemm_seg: operands must be 2-D contiguous bf16");
-  }
+  const Op op("conv1x1_gemm_seg", a1);
+  check_mat_bf16(op, "a1", a1);
+  check_mat_bf16(op, "a2", a2);
+  check_mat_bf16(op, "b", b);
+  check_mat_bf16(op, "out", out);
   const int64_t M = a1.size(0), k1 = a1.size(1), k2 = a2.size(1), N = b.size(0);
   TORCH_CHECK(a2.size(0) == M && out.size(0) == M && out.size(1) == N && b.size(1) == k1 + rep2 * k2 + 32 && rep2 >= 1,
               "conv1x1_gemm_seg: shape mismatch");
   TORCH_CHECK(k1 % 32 == 0 && k2 % 32 == 0 && N % 64 == 0, "conv1x1_gemm_seg: k1, k2 % 32 and N % 64 required");
   c10::optional<Tensor> part;
-  const uint16_t* bx = nullptr;
-  const uint8_t* bm = nullptr;
-  const float* bmean = nullptr;
-  if (bn_x.has_value() && bn_x->defined()) {
-    check_cuda(*bn_x, "bn_x");
-    TORCH_CHECK(bn_x->scalar_type() == at::kBFloat16 && bn_x->numel() == M * N && bn_x->is_contiguous(
-                    bn_x->dim() == 4 ? at::MemoryFormat::ChannelsLast : at::MemoryFormat::Contiguous),
-                "conv1x1_gemm_seg: bn_x must be [M, N] bf16 (channels_last when 4-D)");
-    TORCH_CHECK(bn_mean.has_value() && bn_mean->defined() && bn_mean->scalar_type() == at::kFloat &&
-                bn_mean->numel() == N && bn_mean->is_contiguous() && bn_mean->is_cuda(),
-                "conv1x1_gemm_seg: bn_mean must be fp32 [N]");
-    if (bn_mask.has_value() && bn_mask->defined()) {
-      TORCH_CHECK(bn_mask->scalar_type() == at::kByte && bn_mask->numel() == M * N / 8 && bn_mask->is_cuda(),
-                  "conv1x1_gemm_seg: bn_mask must be uint8 [M * N / 8]");
-      bm = bn_mask->data_ptr<uint8_t>();
-    }
-    bx = reinterpret_cast<const uint16_t*>(bn_x->data_ptr());
-    bmean = bn_mean->data_ptr<float>();
+  BnSide bn;
+  if (has(bn_x)) {
+    bn = bn_side(op, bn_x, bn_mask, bn_mean, M, N, false);
     const int64_t T = (M + pdt_conv1x1_tile_rows() - 1) / pdt_conv1x1_tile_rows();
     part = at::empty({2, T, N}, a1.options().dtype(at::kFloat));
   }
-  const int rc = pdt_conv1x1_gemm_seg(reinterpret_cast<const uint16_t*>(a1.data_ptr()), (int)k1,
-                                      reinterpret_cast<const uint16_t*>(a2.data_ptr()), (int)k2, (int)rep2,
-                                      reinterpret_cast<const uint16_t*>(b.data_ptr()),
-                                      reinterpret_cast<uint16_t*>(out.data_ptr()), (int)M, (int)N, bx, bm, bmean,
+  const int rc = pdt_conv1x1_gemm_seg(bf16_ptr(a1), (int)k1, bf16_ptr(a2), (int)k2, (int)rep2, bf16_ptr(b),
+                                      bf16_out(out), (int)M, (int)N, bn.x, bn.mask, bn.mean,
                                       part.has_value() ? part->data_ptr<float>() : nullptr, stream());
   TORCH_CHECK(rc == 0, "pdt_conv1x1_gemm_seg failed: ", rc);
   return part;
 }
 
+// The ALG backward's fp32 Gram workspace wg [rows, CW] (csrc/kernels/bn_alg.hip): at least min_rows rows.
+const float* alg_wg_ptr(const Op& op, const Tensor& wg, int64_t CW, int64_t min_rows) {
+  TORCH_CHECK(wg.dim() == 2 && wg.size(1) == CW && wg.size(0) >= min_rows, op.name, ": wg [>= ", min_rows, ", ", CW,
+              "] fp32");
+  return f32_ptr(op, "wg", wg, wg.numel());
+}
+
 // (bcat [CW, C4 + 2 CW + 32] bf16, dW [C4, CW] bf16) of the ALG backward (csrc/kernels/bn_alg.hip).
 std::vector<Tensor> bn_alg_assemble(Tensor w, Tensor coef, Tensor mean, Tensor G, Tensor wg, Tensor BWG, int64_t rep) {
-  for (const Tensor* t : {&w, &coef, &mean, &G, &wg, &BWG}) {
-    check_cuda(*t, "bn_alg_assemble operand");
-    TORCH_CHECK(t->is_contiguous(), "bn_alg_assemble: contiguous operands");
-  }
-  TORCH_CHECK(w.dim() == 2 && w.scalar_type() == at::kBFloat16, "bn_alg_assemble: w [C4, CW] bf16");
+  const Op op("bn_alg_assemble", w);
+  check_mat_bf16(op, "w", w);
   const int64_t C4 = w.size(0), CW = w.size(1);
-  TORCH_CHECK(coef.scalar_type() == at::kFloat && coef.numel() == 3 * C4 && mean.scalar_type() == at::kFloat &&
-                  mean.numel() == C4 && G.scalar_type() == at::kFloat && G.numel() == (C4 / 128) * CW * CW &&
-                  BWG.scalar_type() == at::kFloat && BWG.numel() == std::max<int64_t>(1, CW / 128) * C4 * CW &&
-                  wg.scalar_type() == at::kFloat &&
-                  wg.dim() == 2 && wg.size(1) == CW && wg.size(0) > C4 + CW,
-              "bn_alg_assemble: operand shapes");
   TORCH_CHECK(rep == 1 || rep == 2, "bn_alg_assemble: rep 1 or 2");
   auto bcat = at::empty({CW, C4 + rep * CW + 32}, w.options());
   auto dW = at::empty({C4, CW}, w.options());
-  const int rc = pdt_bn_alg_assemble(reinterpret_cast<const uint16_t*>(w.data_ptr()), coef.data_ptr<float>(),
-                                     mean.data_ptr<float>(), G.data_ptr<float>(), wg.data_ptr<float>(),
-                                     BWG.data_ptr<float>(), reinterpret_cast<uint16_t*>(bcat.data_ptr()),
-                                     reinterpret_cast<uint16_t*>(dW.data_ptr()), (int)C4, (int)CW, (int)rep, stream());
+  const int rc = pdt_bn_alg_assemble(bf16_ptr(w), f32_ptr(op, "coef", coef, 3 * C4), f32_ptr(op, "mean", mean, C4),
+                                     f32_ptr(op, "G", G, (C4 / 128) * CW * CW), alg_wg_ptr(op, wg, CW, C4 + CW + 1),
+                                     f32_ptr(op, "BWG", BWG, std::max<int64_t>(1, CW / 128) * C4 * CW), bf16_out(bcat),
+                                     bf16_out(dW), (int)C4, (int)CW, (int)rep, stream());
   TORCH_CHECK(rc == 0, "pdt_bn_alg_assemble failed: ", rc);
   return {bcat, dW};
 }
 
 // (G [CW, CW], BWG [C4, CW]) fp32 of the ALG backward: W^T diag(B) W and diag(B) W Gram (csrc/kernels/bn_alg.hip).
 std::vector<Tensor> bn_alg_small_gemm(Tensor w, Tensor coef, Tensor wg, c10::optional<Tensor> wt) {
-  check_cuda(w, "w");
-  check_cuda(coef, "coef");
-  check_cuda(wg, "wg");
-  TORCH_CHECK(w.dim() == 2 && w.scalar_type() == at::kBFloat16 && w.is_contiguous(), "bn_alg_small_gemm: w [C4, CW] bf16");
+  const Op op("bn_alg_small_gemm", w);
+  check_mat_bf16(op, "w", w);
   const int64_t C4 = w.size(0), CW = w.size(1);
-  TORCH_CHECK(coef.scalar_type() == at::kFloat && coef.is_contiguous() && coef.numel() == 3 * C4 &&
-                  wg.scalar_type() == at::kFloat && wg.is_contiguous() && wg.dim() == 2 && wg.size(1) == CW &&
-                  wg.size(0) >= C4 + CW && C4 % 64 == 0 && CW % 64 == 0,
-              "bn_alg_small_gemm: coef [3, C4], wg [>= C4 + CW, CW] fp32, C4 / CW % 64");
+  TORCH_CHECK(C4 % 64 == 0 && CW % 64 == 0, "bn_alg_small_gemm: coef [3, C4], wg [>= C4 + CW, CW] fp32, C4 / CW % 64");
   TORCH_CHECK(C4 % 128 == 0 && (CW == 64 || CW % 128 == 0), "bn_alg_small_gemm: C4 % 128, CW 64 or % 128");
   // split-K slices (summed by bn_alg_assemble): G [C4 / 128, CW, CW], BWG [max(1, CW / 128), C4, CW]
   auto G = at::empty({C4 / 128, CW, CW}, wg.options());
   auto BWG = at::empty({std::max<int64_t>(1, CW / 128), C4, CW}, wg.options());
   const uint16_t* wtp = nullptr;
-  if (wt.has_value() && wt->defined()) {  // W^T [CW, C4]: the matrix-core form
-    check_cuda(*wt, "wt");
-    TORCH_CHECK(wt->scalar_type() == at::kBFloat16 && wt->is_contiguous() && wt->dim() == 2 && wt->size(0) == CW &&
-                    wt->size(1) == C4, "bn_alg_small_gemm: wt [CW, C4] bf16 contiguous");
-    wtp = reinterpret_cast<const uint16_t*>(wt->data_ptr());
+  if (has(wt)) {  // W^T [CW, C4]: the matrix-core form
+    check_mat_bf16(op, "wt", *wt);
+    TORCH_CHECK(wt->size(0) == CW && wt->size(1) == C4, "bn_alg_small_gemm: wt [CW, C4] bf16 contiguous");
+    wtp = bf16_ptr(*wt);
   }
-  TORCH_CHECK(pdt_bn_alg_small_gemm(reinterpret_cast<const uint16_t*>(w.data_ptr()), wtp, coef.data_ptr<float>(),
-                                    wg.data_ptr<float>(), G.data_ptr<float>(), BWG.data_ptr<float>(), (int)C4, (int)CW,
-                                    stream()) == 0,
+  TORCH_CHECK(pdt_bn_alg_small_gemm(bf16_ptr(w), wtp, f32_ptr(op, "coef", coef, 3 * C4),
+                                    alg_wg_ptr(op, wg, CW, C4 + CW), G.data_ptr<float>(), BWG.data_ptr<float>(),
+                                    (int)C4, (int)CW, stream()) == 0,
               "pdt_bn_alg_small_gemm failed");
   return {G, BWG};
 }
 
 // Completes a sum-only producer's BatchNorm backward partials in place (csrc/kernels/bn_alg.hip).
 void bn_alg_fix_s2(Tensor part, Tensor wg, Tensor w) {
-  check_cuda(part, "part");
-  check_cuda(wg, "wg");
-  check_cuda(w, "w");
-  TORCH_CHECK(w.dim() == 2 && w.scalar_type() == at::kBFloat16 && w.is_contiguous(), "bn_alg_fix_s2: w [C4, CW] bf16");
+  const Op op("bn_alg_fix_s2", part);
+  check_mat_bf16(op, "w", w);
   const int64_t C4 = w.size(0), CW = w.size(1);
-  TORCH_CHECK(part.scalar_type() == at::kFloat && part.is_contiguous() && part.dim() == 3 && part.size(0) == 2 &&
-                  part.size(2) == C4 && wg.scalar_type() == at::kFloat && wg.is_contiguous() && wg.dim() == 2 &&
-                  wg.size(1) == CW && wg.size(0) >= C4,
-              "bn_alg_fix_s2: part [2, T, C4], wg [>= C4, CW] fp32");
-  TORCH_CHECK(pdt_bn_alg_fix_s2(part.data_ptr<float>(), (int)part.size(1), wg.data_ptr<float>(),
-                                reinterpret_cast<const uint16_t*>(w.data_ptr()), (int)C4, (int)CW, stream()) == 0,
+  TORCH_CHECK(part.dim() == 3 && part.size(0) == 2 && part.size(2) == C4, "bn_alg_fix_s2: part [2, T, C4] fp32");
+  TORCH_CHECK(pdt_bn_alg_fix_s2(f32_ptr(op, "part", part, part.numel()), (int)part.size(1),
+                                alg_wg_ptr(op, wg, CW, C4), bf16_ptr(w), (int)C4, (int)CW, stream()) == 0,
               "pdt_bn_alg_fix_s2 failed");
 }
 
 // A downsample BatchNorm's backward partials [2, 1, C4] from s1 = sum(g), its mean and the ALG pass (bn_alg.hip).
 Tensor bn_alg_ds_part(Tensor s1, Tensor mean, Tensor wg, Tensor w) {
-  for (const Tensor* t : {&s1, &mean, &wg, &w}) check_cuda(*t, "bn_alg_ds_part operand");
-  TORCH_CHECK(w.dim() == 2 && w.scalar_type() == at::kBFloat16 && w.is_contiguous(), "bn_alg_ds_part: w [C4, CW] bf16");
+  const Op op("bn_alg_ds_part", s1);
+  check_mat_bf16(op, "w", w);
   const int64_t C4 = w.size(0), CW = w.size(1);
-  TORCH_CHECK(s1.scalar_type() == at::kFloat && s1.is_contiguous() && s1.numel() == C4 && mean.scalar_type() == at::kFloat &&
-                  mean.is_contiguous() && mean.numel() == C4 && wg.scalar_type() == at::kFloat && wg.is_contiguous() &&
-                  wg.dim() == 2 && wg.size(1) == CW && wg.size(0) >= C4,
-              "bn_alg_ds_part: s1 / mean [C4] fp32, wg [>= C4, CW] fp32");
   auto part = at::empty({2, 1, C4}, s1.options());
-  TORCH_CHECK(pdt_bn_alg_ds_part(part.data_ptr<float>(), s1.data_ptr<float>(), mean.data_ptr<float>(),
-                                 wg.data_ptr<float>(), reinterpret_cast<const uint16_t*>(w.data_ptr()), (int)C4, (int)CW,
-                                 stream()) == 0,
+  TORCH_CHECK(pdt_bn_alg_ds_part(part.data_ptr<float>(), f32_ptr(op, "s1", s1, C4), f32_ptr(op, "mean", mean, C4),
+                                 alg_wg_ptr(op, wg, CW, C4), bf16_ptr(w), (int)C4, (int)CW, stream()) == 0,
               "pdt_bn_alg_ds_part failed");
   return part;
 }
@@ -1591,18 +1247,19 @@ std::vector<Tensor> bn_fwd_train_tiles(Tensor x, Tensor part, c10::optional<Tens
                                        c10::optional<Tensor> bias, c10::optional<Tensor> running_mean,
                                        c10::optional<Tensor> running_var, double momentum, double eps, bool relu,
                                        c10::optional<Tensor> res_ab, bool apply, int64_t sub) {
-  check_nhwc_bf16(x, "x");
+  const Op op("bn_fwd_train_tiles", x);
+  check_nhwc_bf16(op, "x", x);
   const int64_t C = x.size(1);
   const int64_t M = x.numel() / C;
   TORCH_CHECK(C % 64 == 0, "pdt bn: C must be a multiple of 64");
-  TORCH_CHECK(part.scalar_type() == at::kFloat && part.is_contiguous() && part.dim() == 3 && part.size(0) == 2 &&
-              part.size(2) == C, "bn_fwd_train_tiles: partials [2, T, C] fp32 expected");
+  TORCH_CHECK(part.dim() == 3 && part.size(0) == 2 && part.size(2) == C,
+              "bn_fwd_train_tiles: partials [2, T, C] fp32 expected");
   // tile height from the partials' row count: 256 (every producer) or 224 (the layer-1 row-tile 3x3,
   // used only where M / 224 >= 256, so the two never give the same T)
   const int64_t T = part.size(1);
   const int BMt = T == (M + 255) / 256 ? 256 : (M % 224 == 0 && T == M / 224 ? 224 : 0);
   TORCH_CHECK(BMt > 0, "bn_fwd_train_tiles: partials row count ", T, " matches no tile height for M = ", M);
-  const auto rab = res_ab_ptrs(res_ab, C);
+  const float* rab = opt_f32_ptr(op, "res_ab", res_ab, 2 * C);
   Tensor y;
   if (apply) y = at::empty_like(x);
   Tensor mask;
@@ -1610,14 +1267,6 @@ std::vector<Tensor> bn_fwd_train_tiles(Tensor x, Tensor part, c10::optional<Tens
   auto fopt = x.options().dtype(at::kFloat);
   auto mean = at::empty({C}, fopt), invstd = at::empty({C}, fopt);
   auto ws = at::empty({pdt_bn_tiles_ws_floats((int)T, (int)C)}, fopt);
-  const uint16_t* rp = nullptr;
-  if (res.has_value() && res->defined()) {
-    check_nhwc_bf16(*res, "residual");
-    TORCH_CHECK(res->sizes() == x.sizes() && res->strides() == x.strides(), "pdt bn: residual layout mismatch");
-    rp = reinterpret_cast<const uint16_t*>(res->data_ptr());
-  }
-  float* rm = running_mean.has_value() && running_mean->defined() ? running_mean->data_ptr<float>() : nullptr;
-  float* rv = running_var.has_value() && running_var->defined() ? running_var->data_ptr<float>() : nullptr;
   // sub >= 2: also the stride-sub subsample of y (x must be 4-D [N, C, H, W])
   Tensor ys;
   if (sub >= 2) {
@@ -1625,14 +1274,15 @@ std::vector<Tensor> bn_fwd_train_tiles(Tensor x, Tensor part, c10::optional<Tens
     ys = at::empty({x.size(0), C, (x.size(2) - 1) / sub + 1, (x.size(3) - 1) / sub + 1},
                    x.options().memory_format(at::MemoryFormat::ChannelsLast));
   }
-  const int rc = pdt_bn_fwd_train_tiles(part.data_ptr<float>(), (int)T, BMt, reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                                        rp, rab.first, rab.second, opt_fptr(weight), opt_fptr(bias), rm, rv,
-                                        (float)momentum, (float)eps, M, (int)C, relu,
-                                        apply ? reinterpret_cast<uint16_t*>(y.data_ptr()) : nullptr,
-                                        (relu && apply) ? mask.data_ptr<uint8_t>() : nullptr, mean.data_ptr<float>(),
-                                        invstd.data_ptr<float>(), ws.data_ptr<float>(), stream(),
-                                        sub >= 2 ? reinterpret_cast<uint16_t*>(ys.data_ptr()) : nullptr,
-                                        sub >= 2 ? (int)x.size(2) : 0, sub >= 2 ? (int)x.size(3) : 0, (int)sub);
+  const int rc = pdt_bn_fwd_train_tiles(f32_ptr(op, "part", part, 2 * T * C), (int)T, BMt, bf16_ptr(x),
+                                        residual_ptr(op, x, res), rab, rab ? rab + C : nullptr,
+                                        opt_f32_ptr(op, "weight", weight, C), opt_f32_ptr(op, "bias", bias, C),
+                                        opt_f32_ptr(op, "running_mean", running_mean, C),
+                                        opt_f32_ptr(op, "running_var", running_var, C), (float)momentum, (float)eps, M,
+                                        (int)C, relu, ptr_or_null<uint16_t>(y), ptr_or_null<uint8_t>(mask),
+                                        mean.data_ptr<float>(), invstd.data_ptr<float>(), ws.data_ptr<float>(),
+                                        stream(), ptr_or_null<uint16_t>(ys), sub >= 2 ? (int)x.size(2) : 0,
+                                        sub >= 2 ? (int)x.size(3) : 0, (int)sub);
   if (rc == -4) return {};  // (subsample not taken: the caller gathers)
   TORCH_CHECK(rc == 0, "pdt_bn_fwd_train_tiles failed: ", rc);
   if (!apply)  // the apply coefficients (a, b) are the workspace's last 2C floats (past the level-1 sums)
@@ -1642,18 +1292,23 @@ std::vector<Tensor> bn_fwd_train_tiles(Tensor x, Tensor part, c10::optional<Tens
 }
 
 // ----------------------------------------------------------------------------- 3x3 conv (stride 1, pad 1)
-// y = conv2d(x, w, stride=1, padding=1) for channels_last bf16 x [N,Ci,H,W] and w [Co,Ci,3,3]
-// (w's channels_last storage is [Co][3][3][Ci], the kernel's layout).
+// A 3x3 conv weight [*, Ci, 3, 3] bf16 on the op's device, returned channels_last (storage [*][3][3][Ci], the
+// kernels' layout).
+Tensor check_w3x3(const Op& op, const Tensor& w, int64_t Ci) {
+  TORCH_CHECK(w.dim() == 4 && w.size(2) == 3 && w.size(3) == 3 && w.size(1) == Ci &&
+                  w.scalar_type() == at::kBFloat16 && w.device() == op.dev,
+              op.name, ": weight [Co, ", Ci, ", 3, 3] bf16 on ", op.dev);
+  return w.contiguous(at::MemoryFormat::ChannelsLast);
+}
+
+// y = conv2d(x, w, stride=1, padding=1) for channels_last bf16 x [N,Ci,H,W] and w [Co,Ci,3,3].
 Tensor conv3x3s1_fwd(Tensor x, Tensor w) {
-  check_nhwc_bf16(x, "x");
-  TORCH_CHECK(w.dim() == 4 && w.size(2) == 3 && w.size(3) == 3 && w.size(1) == x.size(1) &&
-              w.scalar_type() == at::kBFloat16, "conv3x3: weight [Co, Ci, 3, 3] bf16");
-  w = w.contiguous(at::MemoryFormat::ChannelsLast);
+  const Op op("conv3x3s1_fwd", x);
+  check_nhwc_bf16(op, "x", x);
+  w = check_w3x3(op, w, x.size(1));
   const int64_t N = x.size(0), Ci = x.size(1), H = x.size(2), W = x.size(3), Co = w.size(0);
   auto y = at::empty({N, Co, H, W}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  const int rc = pdt_conv3x3s1_fwd(reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                                   reinterpret_cast<const uint16_t*>(w.data_ptr()),
-                                   reinterpret_cast<uint16_t*>(y.data_ptr()), (int)N, (int)H, (int)W, (int)Ci, (int)Co,
+  const int rc = pdt_conv3x3s1_fwd(bf16_ptr(x), bf16_ptr(w), bf16_out(y), (int)N, (int)H, (int)W, (int)Ci, (int)Co,
                                    stream());
   TORCH_CHECK(rc == 0, "pdt_conv3x3s1_fwd failed: ", rc);
   return y;
@@ -1662,19 +1317,16 @@ Tensor conv3x3s1_fwd(Tensor x, Tensor w) {
 // conv3x3s1_fwd + the per-tile BatchNorm statistics of y (tile_stats.h): {y, part [2, T, Co]}, or
 // {y} alone when the shape runs on a kernel without the statistics epilogue.
 std::vector<Tensor> conv3x3s1_fwd_stats(Tensor x, Tensor w) {
-  check_nhwc_bf16(x, "x");
-  TORCH_CHECK(w.dim() == 4 && w.size(2) == 3 && w.size(3) == 3 && w.size(1) == x.size(1) &&
-              w.scalar_type() == at::kBFloat16, "conv3x3: weight [Co, Ci, 3, 3] bf16");
-  w = w.contiguous(at::MemoryFormat::ChannelsLast);
+  const Op op("conv3x3s1_fwd_stats", x);
+  check_nhwc_bf16(op, "x", x);
+  w = check_w3x3(op, w, x.size(1));
   const int64_t N = x.size(0), Ci = x.size(1), H = x.size(2), W = x.size(3), Co = w.size(0);
   auto y = at::empty({N, Co, H, W}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
   const int64_t rows = pdt_conv3x3s1_stats_tile_rows((int)N, (int)H, (int)W, (int)Ci, (int)Co);
   const int64_t T = (N * H * W + rows - 1) / rows;
   auto part = at::empty({2, T, Co}, x.options().dtype(at::kFloat));
-  const int rc = pdt_conv3x3s1_fwd_stats(reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                                         reinterpret_cast<const uint16_t*>(w.data_ptr()),
-                                         reinterpret_cast<uint16_t*>(y.data_ptr()), part.data_ptr<float>(), (int)N,
-                                         (int)H, (int)W, (int)Ci, (int)Co, stream());
+  const int rc = pdt_conv3x3s1_fwd_stats(bf16_ptr(x), bf16_ptr(w), bf16_out(y), part.data_ptr<float>(), (int)N, (int)H,
+                                         (int)W, (int)Ci, (int)Co, stream());
   if (rc == -5) return {conv3x3s1_fwd(x, w)};
   TORCH_CHECK(rc == 0, "pdt_conv3x3s1_fwd_stats failed: ", rc);
   return {y, part};
@@ -1685,32 +1337,19 @@ std::vector<Tensor> conv3x3s1_fwd_stats(Tensor x, Tensor w) {
 // [2, T, Co]} of the BN's backward reduction, or {y} where only a kernel without the epilogue applies.
 std::vector<Tensor> conv3x3s1_fwd_bnbwd(Tensor x, Tensor w, Tensor bn_x, c10::optional<Tensor> bn_mask,
                                         Tensor bn_mean) {
-  check_nhwc_bf16(x, "x");
-  check_nhwc_bf16(bn_x, "bn_x");
-  TORCH_CHECK(w.dim() == 4 && w.size(2) == 3 && w.size(3) == 3 && w.size(1) == x.size(1) &&
-              w.scalar_type() == at::kBFloat16, "conv3x3: weight [Co, Ci, 3, 3] bf16");
-  w = w.contiguous(at::MemoryFormat::ChannelsLast);
+  const Op op("conv3x3s1_fwd_bnbwd", x);
+  check_nhwc_bf16(op, "x", x);
+  w = check_w3x3(op, w, x.size(1));
   const int64_t N = x.size(0), Ci = x.size(1), H = x.size(2), W = x.size(3), Co = w.size(0);
-  TORCH_CHECK(bn_x.size(0) == N && bn_x.size(1) == Co && bn_x.size(2) == H && bn_x.size(3) == W,
+  const BnSide bn = bn_side(op, bn_x, bn_mask, bn_mean, N * H * W, Co, false);
+  TORCH_CHECK(bn_x.dim() == 4 && bn_x.size(0) == N && bn_x.size(1) == Co && bn_x.size(2) == H && bn_x.size(3) == W,
               "conv3x3s1_fwd_bnbwd: bn_x must have the output's shape");
-  TORCH_CHECK(bn_mean.scalar_type() == at::kFloat && bn_mean.numel() == Co && bn_mean.is_contiguous() &&
-              bn_mean.is_cuda(), "conv3x3s1_fwd_bnbwd: bn_mean fp32 [Co]");
-  const uint8_t* mp = nullptr;
-  if (bn_mask.has_value() && bn_mask->defined()) {
-    TORCH_CHECK(bn_mask->scalar_type() == at::kByte && bn_mask->numel() == N * H * W * Co / 8 && bn_mask->is_cuda(),
-                "conv3x3s1_fwd_bnbwd: bn_mask uint8 [M * Co / 8]");
-    mp = bn_mask->data_ptr<uint8_t>();
-  }
   auto y = at::empty({N, Co, H, W}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
   const int64_t rows = pdt_conv3x3s1_bnbwd_tile_rows((int)N, (int)H, (int)W, (int)Ci, (int)Co);
   const int64_t T = (N * H * W + rows - 1) / rows;
   auto part = at::empty({2, T, Co}, x.options().dtype(at::kFloat));
-  const int rc = pdt_conv3x3s1_fwd_bnbwd(reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                                         reinterpret_cast<const uint16_t*>(w.data_ptr()),
-                                         reinterpret_cast<uint16_t*>(y.data_ptr()),
-                                         reinterpret_cast<const uint16_t*>(bn_x.data_ptr()), mp,
-                                         bn_mean.data_ptr<float>(), part.data_ptr<float>(), (int)N, (int)H, (int)W,
-                                         (int)Ci, (int)Co, stream());
+  const int rc = pdt_conv3x3s1_fwd_bnbwd(bf16_ptr(x), bf16_ptr(w), bf16_out(y), bn.x, bn.mask, bn.mean,
+                                         part.data_ptr<float>(), (int)N, (int)H, (int)W, (int)Ci, (int)Co, stream());
   if (rc == -5) return {conv3x3s1_fwd(x, w)};
   TORCH_CHECK(rc == 0, "pdt_conv3x3s1_fwd_bnbwd failed: ", rc);
   return {y, part};
@@ -1721,19 +1360,16 @@ std::vector<Tensor> conv3x3s1_fwd_bnbwd(Tensor x, Tensor w, Tensor bn_x, c10::op
 // the per-tile BatchNorm statistics of y -> {y, part [2, T, Co]}. Ci % 64, Co % 128 == 0 (returns {} for
 // a shape the kernel does not take).
 std::vector<Tensor> conv3x3s2_fwd(Tensor x, Tensor w, bool stats) {
-  check_nhwc_bf16(x, "x");
-  TORCH_CHECK(w.dim() == 4 && w.size(2) == 3 && w.size(3) == 3 && w.size(1) == x.size(1) &&
-              w.scalar_type() == at::kBFloat16, "conv3x3s2: weight [Co, Ci, 3, 3] bf16");
-  w = w.contiguous(at::MemoryFormat::ChannelsLast);
+  const Op op("conv3x3s2_fwd", x);
+  check_nhwc_bf16(op, "x", x);
+  w = check_w3x3(op, w, x.size(1));
   const int64_t N = x.size(0), Ci = x.size(1), H = x.size(2), W = x.size(3), Co = w.size(0);
   const int64_t Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   auto y = at::empty({N, Co, Ho, Wo}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
   Tensor part;
   if (stats) part = at::empty({2, (N * Ho * Wo + 255) / 256, Co}, x.options().dtype(at::kFloat));
-  const int rc = pdt_conv3x3s2_fwd(reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                                   reinterpret_cast<const uint16_t*>(w.data_ptr()),
-                                   reinterpret_cast<uint16_t*>(y.data_ptr()), stats ? part.data_ptr<float>() : nullptr,
-                                   (int)N, (int)H, (int)W, (int)Ci, (int)Co, stream());
+  const int rc = pdt_conv3x3s2_fwd(bf16_ptr(x), bf16_ptr(w), bf16_out(y), ptr_or_null<float>(part), (int)N, (int)H,
+                                   (int)W, (int)Ci, (int)Co, stream());
   if (rc == -1 || rc == -2) return {};
   TORCH_CHECK(rc == 0, "pdt_conv3x3s2_fwd failed: ", rc);
   if (stats) return {y, part};
@@ -1745,50 +1381,34 @@ std::vector<Tensor> conv3x3s2_fwd(Tensor x, Tensor w, bool stats) {
 // backward reduction (T = 4 phases of tiles). Returns {} for a shape the kernel does not take.
 std::vector<Tensor> conv3x3s2_dgrad(Tensor dy, Tensor wf, int64_t H, int64_t W, c10::optional<Tensor> bn_x,
                                     c10::optional<Tensor> bn_mask, c10::optional<Tensor> bn_mean) {
-  check_nhwc_bf16(dy, "dy");
-  TORCH_CHECK(wf.dim() == 4 && wf.size(2) == 3 && wf.size(3) == 3 && wf.size(1) == dy.size(1) &&
-              wf.scalar_type() == at::kBFloat16, "conv3x3s2_dgrad: flipped weight [Ci, Co, 3, 3] bf16");
-  wf = wf.contiguous(at::MemoryFormat::ChannelsLast);
+  const Op op("conv3x3s2_dgrad", dy);
+  check_nhwc_bf16(op, "dy", dy);
+  wf = check_w3x3(op, wf, dy.size(1));  // the flipped weight [Ci, Co, 3, 3]
   const int64_t N = dy.size(0), Co = dy.size(1), Ci = wf.size(0);
   TORCH_CHECK(dy.size(2) == (H - 1) / 2 + 1 && dy.size(3) == (W - 1) / 2 + 1, "conv3x3s2_dgrad: dy spatial size");
   auto dx = at::empty({N, Ci, H, W}, dy.options().memory_format(at::MemoryFormat::ChannelsLast));
-  const bool bst = bn_x.has_value() && bn_x->defined();
-  const uint16_t* bx = nullptr;
-  const uint8_t* bm = nullptr;
-  const float* bmean = nullptr;
+  BnSide bn;
   Tensor part;
-  if (bst) {
-    check_nhwc_bf16(*bn_x, "bn_x");
+  if (has(bn_x)) {
+    bn = bn_side(op, bn_x, bn_mask, bn_mean, N * H * W, Ci, false);
     TORCH_CHECK(bn_x->sizes() == dx.sizes(), "conv3x3s2_dgrad: bn_x must have dx's shape");
-    TORCH_CHECK(bn_mean.has_value() && bn_mean->defined() && bn_mean->scalar_type() == at::kFloat &&
-                bn_mean->numel() == Ci && bn_mean->is_contiguous() && bn_mean->is_cuda(),
-                "conv3x3s2_dgrad: bn_mean fp32 [Ci]");
-    if (bn_mask.has_value() && bn_mask->defined()) {
-      TORCH_CHECK(bn_mask->scalar_type() == at::kByte && bn_mask->numel() == N * H * W * Ci / 8 && bn_mask->is_cuda(),
-                  "conv3x3s2_dgrad: bn_mask uint8 [M * Ci / 8]");
-      bm = bn_mask->data_ptr<uint8_t>();
-    }
-    bx = reinterpret_cast<const uint16_t*>(bn_x->data_ptr());
-    bmean = bn_mean->data_ptr<float>();
     part = at::empty({2, (int64_t)pdt_conv3x3s2_dgrad_tiles((int)N, (int)H, (int)W), Ci},
                      dy.options().dtype(at::kFloat));
   }
-  const int rc = pdt_conv3x3s2_dgrad(reinterpret_cast<const uint16_t*>(dy.data_ptr()),
-                                     reinterpret_cast<const uint16_t*>(wf.data_ptr()),
-                                     reinterpret_cast<uint16_t*>(dx.data_ptr()), bx, bm, bmean,
-                                     bst ? part.data_ptr<float>() : nullptr, (int)N, (int)H, (int)W, (int)Ci, (int)Co,
-                                     stream());
+  const int rc = pdt_conv3x3s2_dgrad(bf16_ptr(dy), bf16_ptr(wf), bf16_out(dx), bn.x, bn.mask, bn.mean,
+                                     ptr_or_null<float>(part), (int)N, (int)H, (int)W, (int)Ci, (int)Co, stream());
   if (rc == -1 || rc == -2) return {};
   TORCH_CHECK(rc == 0, "pdt_conv3x3s2_dgrad failed: ", rc);
-  if (bst) return {dx, part};
+  if (has(bn_x)) return {dx, part};
   return {dx};
 }
 
 // Weight gradient of the stride-2 pad-1 3x3 conv (conv3x3_wgrad.hip, S = 2): dw [Co, Ci, 3, 3]
 // channels_last bf16 from x [N, Ci, H, W] and dy [N, Co, Ho, Wo]; undefined for an unsupported shape.
 Tensor conv3x3s2_wgrad(Tensor x, Tensor dy) {
-  check_nhwc_bf16(x, "x");
-  check_nhwc_bf16(dy, "dy");
+  const Op op("conv3x3s2_wgrad", x);
+  check_nhwc_bf16(op, "x", x);
+  check_nhwc_bf16(op, "dy", dy);
   const int64_t N = x.size(0), Ci = x.size(1), H = x.size(2), W = x.size(3), Co = dy.size(1);
   TORCH_CHECK(dy.size(0) == N && dy.size(2) == (H - 1) / 2 + 1 && dy.size(3) == (W - 1) / 2 + 1,
               "conv3x3s2_wgrad: dy [N, Co, Ho, Wo]");
@@ -1797,22 +1417,20 @@ Tensor conv3x3s2_wgrad(Tensor x, Tensor dy) {
   if (wsf == 0 || N * H * W * std::max(Ci, Co) >= ((int64_t)1 << 31)) return Tensor();
   auto ws = at::empty({wsf}, x.options().dtype(at::kFloat));
   auto dw = at::empty({Co, Ci, 3, 3}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  const int rc = pdt_conv3x3s2_wgrad(reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                                     reinterpret_cast<const uint16_t*>(dy.data_ptr()),
-                                     reinterpret_cast<uint16_t*>(dw.data_ptr()), ws.data_ptr<float>(), (int)N, (int)H,
+  const int rc = pdt_conv3x3s2_wgrad(bf16_ptr(x), bf16_ptr(dy), bf16_out(dw), ws.data_ptr<float>(), (int)N, (int)H,
                                      (int)W, (int)Ci, (int)Co, stream());
   if (rc == -4 || rc == -1 || rc == -2) return Tensor();
   TORCH_CHECK(rc == 0, "pdt_conv3x3s2_wgrad failed: ", rc);
   return dw;
 }
 
-// Data-gradient weights: wf [Ci, Co, 3, 3] (channels_last storage [Ci][3][3][Co]) with
 // Weight gradient of the stride-1 pad-1 3x3 conv (csrc/kernels/conv3x3_wgrad.hip): dw [Co, Ci, 3, 3]
 // channels_last bf16 from channels_last bf16 x [N, Ci, H, W] and dy [N, Co, H, W]. Returns an
 // undefined tensor for a shape the kernel does not take (caller falls back).
 Tensor conv3x3s1_wgrad(Tensor x, Tensor dy) {
-  check_nhwc_bf16(x, "x");
-  check_nhwc_bf16(dy, "dy");
+  const Op op("conv3x3s1_wgrad", x);
+  check_nhwc_bf16(op, "x", x);
+  check_nhwc_bf16(op, "dy", dy);
   const int64_t N = x.size(0), Ci = x.size(1), H = x.size(2), W = x.size(3), Co = dy.size(1);
   TORCH_CHECK(dy.size(0) == N && dy.size(2) == H && dy.size(3) == W, "conv3x3s1_wgrad: dy [N, Co, H, W]");
   int ns = 0;
@@ -1820,44 +1438,47 @@ Tensor conv3x3s1_wgrad(Tensor x, Tensor dy) {
   if (wsf == 0 || N * H * W * std::max(Ci, Co) >= ((int64_t)1 << 31)) return Tensor();
   auto ws = at::empty({wsf}, x.options().dtype(at::kFloat));
   auto dw = at::empty({Co, Ci, 3, 3}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  const int rc = pdt_conv3x3s1_wgrad(reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                                     reinterpret_cast<const uint16_t*>(dy.data_ptr()),
-                                     reinterpret_cast<uint16_t*>(dw.data_ptr()), ws.data_ptr<float>(), (int)N, (int)H,
+  const int rc = pdt_conv3x3s1_wgrad(bf16_ptr(x), bf16_ptr(dy), bf16_out(dw), ws.data_ptr<float>(), (int)N, (int)H,
                                      (int)W, (int)Ci, (int)Co, stream());
   if (rc == -4) return Tensor();
   TORCH_CHECK(rc == 0, "pdt_conv3x3s1_wgrad failed: ", rc);
   return dw;
 }
 
+// Data-gradient weights: wf [Ci, Co, 3, 3] (channels_last storage [Ci][3][3][Co]) with
 // wf[ci, co, kh, kw] = w[co, ci, 2 - kh, 2 - kw], so dx = conv3x3s1_fwd(dy, wf).
 Tensor conv3x3_flip(Tensor w) {
-  check_cuda(w, "w");
-  TORCH_CHECK(w.dim() == 4 && w.size(2) == 3 && w.size(3) == 3 && w.scalar_type() == at::kBFloat16,
-              "conv3x3_flip: weight [Co, Ci, 3, 3] bf16");
-  w = w.contiguous(at::MemoryFormat::ChannelsLast);
+  const Op op("conv3x3_flip", w);
+  w = check_w3x3(op, w, w.dim() == 4 ? w.size(1) : 0);
   const int64_t Co = w.size(0), Ci = w.size(1);
   auto wf = at::empty({Ci, Co, 3, 3}, w.options().memory_format(at::MemoryFormat::ChannelsLast));
-  TORCH_CHECK(pdt_conv3x3_flip_weights(reinterpret_cast<const uint16_t*>(w.data_ptr()),
-                                       reinterpret_cast<uint16_t*>(wf.data_ptr()), (int)Co, (int)Ci, stream()) == 0,
+  TORCH_CHECK(pdt_conv3x3_flip_weights(bf16_ptr(w), bf16_out(wf), (int)Co, (int)Ci, stream()) == 0,
               "pdt_conv3x3_flip_weights failed");
   return wf;
 }
 
 // ----------------------------------------------------------------------------- 7x7/s2 stem conv (3 -> 64)
+// The stem's input x [N, 3, H, W] (W % 32 == 0; the weight gradients also need W <= 224) and weight [64, 3, 7, 7].
+void check_stem_x(const Op& op, const Tensor& x) {
+  check_nhwc_bf16(op, "x", x);
+  TORCH_CHECK(x.dim() == 4 && x.size(1) == 3 && x.size(3) % 32 == 0, op.name, ": x [N, 3, H, W] with W % 32 == 0");
+}
+Tensor check_stem_w(const Op& op, const Tensor& w) {
+  TORCH_CHECK(w.dim() == 4 && w.size(0) == 64 && w.size(1) == 3 && w.size(2) == 7 && w.size(3) == 7 &&
+                  w.scalar_type() == at::kBFloat16 && w.device() == op.dev, op.name, ": weight [64, 3, 7, 7] bf16");
+  return w.contiguous(at::MemoryFormat::ChannelsLast);
+}
+
 // y = conv2d(x, w, stride=2, padding=3) for channels_last bf16 x [N,3,H,W] (W % 32 == 0) and w [64,3,7,7].
 Tensor stem_conv_fwd(Tensor x, Tensor w) {
-  check_nhwc_bf16(x, "x");
-  TORCH_CHECK(x.size(1) == 3 && x.size(3) % 32 == 0, "stem_conv: x [N, 3, H, W] with W % 32 == 0");
-  TORCH_CHECK(w.dim() == 4 && w.size(0) == 64 && w.size(1) == 3 && w.size(2) == 7 && w.size(3) == 7 &&
-              w.scalar_type() == at::kBFloat16, "stem_conv: weight [64, 3, 7, 7] bf16");
-  w = w.contiguous(at::MemoryFormat::ChannelsLast);
+  const Op op("stem_conv_fwd", x);
+  check_stem_x(op, x);
+  w = check_stem_w(op, w);
   const int64_t N = x.size(0), H = x.size(2), W = x.size(3), OH = (H - 1) / 2 + 1, OW = W / 2;
   auto wp = at::empty({pdt_stem_conv_wprep_elems()}, w.options());
   auto y = at::empty({N, 64, OH, OW}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  const int rc = pdt_stem_conv_fwd(reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                                   reinterpret_cast<const uint16_t*>(w.data_ptr()),
-                                   reinterpret_cast<uint16_t*>(wp.data_ptr()), reinterpret_cast<uint16_t*>(y.data_ptr()),
-                                   (int)N, (int)H, (int)W, stream());
+  const int rc = pdt_stem_conv_fwd(bf16_ptr(x), bf16_ptr(w), bf16_out(wp), bf16_out(y), (int)N, (int)H, (int)W,
+                                   stream());
   TORCH_CHECK(rc == 0, "pdt_stem_conv_fwd failed: ", rc);
   return y;
 }
@@ -1865,22 +1486,17 @@ Tensor stem_conv_fwd(Tensor x, Tensor w) {
 // stem_conv_fwd plus the output's BatchNorm statistics -> {y, part} (part: P (2 * 64 + 1) floats, the
 // input of bn_relu_maxpool_fwd_parts); {} when it does not apply (W != 224).
 std::vector<Tensor> stem_conv_fwd_stats(Tensor x, Tensor w) {
-  check_nhwc_bf16(x, "x");
-  TORCH_CHECK(x.size(1) == 3 && x.size(3) % 32 == 0, "stem_conv: x [N, 3, H, W] with W % 32 == 0");
-  TORCH_CHECK(w.dim() == 4 && w.size(0) == 64 && w.size(1) == 3 && w.size(2) == 7 && w.size(3) == 7 &&
-              w.scalar_type() == at::kBFloat16, "stem_conv: weight [64, 3, 7, 7] bf16");
+  const Op op("stem_conv_fwd_stats", x);
+  check_stem_x(op, x);
   const int64_t N = x.size(0), H = x.size(2), W = x.size(3), OH = (H - 1) / 2 + 1, OW = W / 2;
   const int64_t P = pdt_stem_stats_parts((int)N, (int)H, (int)W);
+  w = check_stem_w(op, w);
   if (P == 0) return {};
-  w = w.contiguous(at::MemoryFormat::ChannelsLast);
   auto wp = at::empty({pdt_stem_conv_wprep_elems()}, w.options());
   auto y = at::empty({N, 64, OH, OW}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
   auto part = at::empty({P * (2 * 64 + 1)}, x.options().dtype(at::kFloat));
-  const int rc = pdt_stem_conv_fwd_stats(reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                                         reinterpret_cast<const uint16_t*>(w.data_ptr()),
-                                         reinterpret_cast<uint16_t*>(wp.data_ptr()),
-                                         reinterpret_cast<uint16_t*>(y.data_ptr()), part.data_ptr<float>(), (int)N,
-                                         (int)H, (int)W, stream());
+  const int rc = pdt_stem_conv_fwd_stats(bf16_ptr(x), bf16_ptr(w), bf16_out(wp), bf16_out(y), part.data_ptr<float>(),
+                                         (int)N, (int)H, (int)W, stream());
   TORCH_CHECK(rc == 0, "pdt_stem_conv_fwd_stats failed: ", rc);
   return {y, part};
 }
@@ -1888,17 +1504,16 @@ std::vector<Tensor> stem_conv_fwd_stats(Tensor x, Tensor w) {
 // Weight gradient of stem_conv_fwd: dw [64, 3, 7, 7] (channels_last) from x and dy [N, 64, OH, OW]
 // (channels_last); W % 32 == 0 and W <= 224.
 Tensor stem_conv_wgrad(Tensor x, Tensor dy) {
-  check_nhwc_bf16(x, "x");
-  check_nhwc_bf16(dy, "dy");
+  const Op op("stem_conv_wgrad", x);
+  check_stem_x(op, x);
+  TORCH_CHECK(x.size(3) <= 224, op.name, ": W <= 224");
+  check_nhwc_bf16(op, "dy", dy);
   const int64_t N = x.size(0), H = x.size(2), W = x.size(3);
-  TORCH_CHECK(x.size(1) == 3 && W % 32 == 0 && W <= 224, "stem_conv_wgrad: x [N, 3, H, W], W % 32 == 0, W <= 224");
   TORCH_CHECK(dy.size(0) == N && dy.size(1) == 64 && dy.size(2) == (H - 1) / 2 + 1 && dy.size(3) == W / 2,
               "stem_conv_wgrad: dy [N, 64, OH, OW]");
   auto ws = at::empty({pdt_stem_wgrad_ws_floats()}, x.options().dtype(at::kFloat));
   auto dw = at::empty({64, 3, 7, 7}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  const int rc = pdt_stem_conv_wgrad(reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                                     reinterpret_cast<const uint16_t*>(dy.data_ptr()),
-                                     reinterpret_cast<uint16_t*>(dw.data_ptr()), ws.data_ptr<float>(), (int)N, (int)H,
+  const int rc = pdt_stem_conv_wgrad(bf16_ptr(x), bf16_ptr(dy), bf16_out(dw), ws.data_ptr<float>(), (int)N, (int)H,
                                      (int)W, stream());
   TORCH_CHECK(rc == 0, "pdt_stem_conv_wgrad failed: ", rc);
   return dw;
@@ -1908,24 +1523,20 @@ Tensor stem_conv_wgrad(Tensor x, Tensor dy) {
 // output gradient is A dz + B (xb - mean) + D (coef [3, 64] = A, B, D from maxpool3s2_bwd_bn_coef;
 // xb: the BN input = the stem conv output, dz: the gradient at the BN output, both [N, 64, OH, OW]).
 Tensor stem_conv_wgrad_bn(Tensor x, Tensor dz, Tensor xb, Tensor coef, Tensor mean) {
-  check_nhwc_bf16(x, "x");
-  check_nhwc_bf16(dz, "dz");
-  check_nhwc_bf16(xb, "xb");
+  const Op op("stem_conv_wgrad_bn", x);
+  check_stem_x(op, x);
+  TORCH_CHECK(x.size(3) <= 224, op.name, ": W <= 224");
+  check_nhwc_bf16(op, "dz", dz);
+  check_nhwc_bf16(op, "xb", xb);
   const int64_t N = x.size(0), H = x.size(2), W = x.size(3);
-  TORCH_CHECK(x.size(1) == 3 && W % 32 == 0 && W <= 224, "stem_conv_wgrad_bn: x [N, 3, H, W], W % 32 == 0, W <= 224");
   TORCH_CHECK(dz.size(0) == N && dz.size(1) == 64 && dz.size(2) == (H - 1) / 2 + 1 && dz.size(3) == W / 2,
               "stem_conv_wgrad_bn: dz [N, 64, OH, OW]");
   TORCH_CHECK(xb.sizes() == dz.sizes(), "stem_conv_wgrad_bn: xb shape");
-  TORCH_CHECK(coef.is_cuda() && coef.scalar_type() == at::kFloat && coef.is_contiguous() && coef.numel() == 3 * 64,
-              "stem_conv_wgrad_bn: coef [3, 64] f32");
-  TORCH_CHECK(mean.is_cuda() && mean.scalar_type() == at::kFloat && mean.is_contiguous() && mean.numel() == 64,
-              "stem_conv_wgrad_bn: mean [64] f32");
   auto ws = at::empty({pdt_stem_wgrad_ws_floats()}, x.options().dtype(at::kFloat));
   auto dw = at::empty({64, 3, 7, 7}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  const int rc = pdt_stem_conv_wgrad_bn(
-      reinterpret_cast<const uint16_t*>(x.data_ptr()), reinterpret_cast<const uint16_t*>(dz.data_ptr()),
-      reinterpret_cast<const uint16_t*>(xb.data_ptr()), coef.data_ptr<float>(), mean.data_ptr<float>(),
-      reinterpret_cast<uint16_t*>(dw.data_ptr()), ws.data_ptr<float>(), (int)N, (int)H, (int)W, stream());
+  const int rc = pdt_stem_conv_wgrad_bn(bf16_ptr(x), bf16_ptr(dz), bf16_ptr(xb), f32_ptr(op, "coef", coef, 3 * 64),
+                                        f32_ptr(op, "mean", mean, 64), bf16_out(dw), ws.data_ptr<float>(), (int)N,
+                                        (int)H, (int)W, stream());
   TORCH_CHECK(rc == 0, "pdt_stem_conv_wgrad_bn failed: ", rc);
   return dw;
 }
@@ -1933,29 +1544,23 @@ Tensor stem_conv_wgrad_bn(Tensor x, Tensor dz, Tensor xb, Tensor coef, Tensor me
 // The same weight gradient from the gradient at the max-pool OUTPUT (dyp [N, 64, PH, PW]) and the pool's
 // winner codes: the pool's input gradient dz is formed per tile inside the kernel, never in HBM.
 Tensor stem_conv_wgrad_bn_pool(Tensor x, Tensor dyp, Tensor code, Tensor xb, Tensor coef, Tensor mean) {
-  check_nhwc_bf16(x, "x");
-  check_nhwc_bf16(dyp, "dyp");
-  check_nhwc_bf16(xb, "xb");
+  const Op op("stem_conv_wgrad_bn_pool", x);
+  check_stem_x(op, x);
+  TORCH_CHECK(x.size(3) <= 224, op.name, ": W <= 224");
+  check_nhwc_bf16(op, "dyp", dyp);
+  check_nhwc_bf16(op, "xb", xb);
   const int64_t N = x.size(0), H = x.size(2), W = x.size(3);
-  TORCH_CHECK(x.size(1) == 3 && W % 32 == 0 && W <= 224, "stem_conv_wgrad_bn_pool: x [N, 3, H, W], W % 32 == 0, W <= 224");
   const int64_t OH = (H - 1) / 2 + 1, OW = W / 2;
   TORCH_CHECK(xb.size(0) == N && xb.size(1) == 64 && xb.size(2) == OH && xb.size(3) == OW,
               "stem_conv_wgrad_bn_pool: xb [N, 64, OH, OW]");
   TORCH_CHECK(dyp.size(0) == N && dyp.size(1) == 64 && dyp.size(2) == (OH - 1) / 2 + 1 && dyp.size(3) == (OW - 1) / 2 + 1,
               "stem_conv_wgrad_bn_pool: dyp [N, 64, PH, PW]");
-  TORCH_CHECK(code.is_cuda() && code.scalar_type() == at::kByte && code.numel() == dyp.numel() && code.is_contiguous(),
-              "stem_conv_wgrad_bn_pool: code uint8, one per dyp element");
-  TORCH_CHECK(coef.is_cuda() && coef.scalar_type() == at::kFloat && coef.is_contiguous() && coef.numel() == 3 * 64,
-              "stem_conv_wgrad_bn_pool: coef [3, 64] f32");
-  TORCH_CHECK(mean.is_cuda() && mean.scalar_type() == at::kFloat && mean.is_contiguous() && mean.numel() == 64,
-              "stem_conv_wgrad_bn_pool: mean [64] f32");
   auto ws = at::empty({pdt_stem_wgrad_ws_floats()}, x.options().dtype(at::kFloat));
   auto dw = at::empty({64, 3, 7, 7}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  const int rc = pdt_stem_conv_wgrad_bn_pool(
-      reinterpret_cast<const uint16_t*>(x.data_ptr()), reinterpret_cast<const uint16_t*>(dyp.data_ptr()),
-      code.data_ptr<uint8_t>(), reinterpret_cast<const uint16_t*>(xb.data_ptr()), coef.data_ptr<float>(),
-      mean.data_ptr<float>(), reinterpret_cast<uint16_t*>(dw.data_ptr()), ws.data_ptr<float>(), (int)N, (int)H, (int)W,
-      stream());
+  const int rc = pdt_stem_conv_wgrad_bn_pool(bf16_ptr(x), bf16_ptr(dyp), u8_ptr(op, "code", code, dyp.numel()),
+                                             bf16_ptr(xb), f32_ptr(op, "coef", coef, 3 * 64),
+                                             f32_ptr(op, "mean", mean, 64), bf16_out(dw), ws.data_ptr<float>(), (int)N,
+                                             (int)H, (int)W, stream());
   TORCH_CHECK(rc == 0, "pdt_stem_conv_wgrad_bn_pool failed: ", rc);
   return dw;
 }
@@ -1964,8 +1569,9 @@ Tensor stem_conv_wgrad_bn_pool(Tensor x, Tensor dyp, Tensor code, Tensor xb, Ten
 std::vector<Tensor> ce_fwd(Tensor logits, Tensor target, double smoothing, int64_t ignore_index) {
   check_cuda(logits, "logits");
   TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), "ce: logits must be contiguous [N, V]");
-  TORCH_CHECK(target.scalar_type() == at::kLong && target.is_contiguous(), "ce: target must be int64");
   const int64_t N = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(target.scalar_type() == at::kLong && target.is_contiguous() && target.numel() == N &&
+                  target.device() == logits.device(), "ce: target must be int64 [N] on the logits' device");
   auto fopt = logits.options().dtype(at::kFloat);
   auto loss = at::empty({N}, fopt), lse = at::empty({N}, fopt);
   pdt_ce_fwd(logits.data_ptr(), dcode(logits), target.data_ptr<int64_t>(), N, V, (float)smoothing, ignore_index,
@@ -1975,16 +1581,20 @@ std::vector<Tensor> ce_fwd(Tensor logits, Tensor target, double smoothing, int64
 
 Tensor ce_bwd(Tensor logits, Tensor target, Tensor lse, c10::optional<Tensor> dloss, double dloss_scale,
               double smoothing, int64_t ignore_index) {
+  const Op op("ce_bwd", logits);
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), "ce: logits must be contiguous [N, V]");
   const int64_t N = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(target.scalar_type() == at::kLong && target.is_contiguous() && target.numel() == N &&
+                  target.device() == op.dev, "ce: target must be int64 [N] on the logits' device");
   auto dl = at::empty_like(logits);
   const float* dp = nullptr;
   Tensor dloss_c;
-  if (dloss.has_value() && dloss->defined()) {
+  if (has(dloss)) {
     dloss_c = dloss->to(at::kFloat).contiguous();
     if (dloss_c.numel() == 1) dloss_c = dloss_c.expand({N}).contiguous();
-    dp = dloss_c.data_ptr<float>();
+    dp = f32_ptr(op, "dloss", dloss_c, N);
   }
-  pdt_ce_bwd(logits.data_ptr(), dcode(logits), target.data_ptr<int64_t>(), lse.data_ptr<float>(), dp,
+  pdt_ce_bwd(logits.data_ptr(), dcode(logits), target.data_ptr<int64_t>(), f32_ptr(op, "lse", lse, N), dp,
              (float)dloss_scale, N, V, (float)smoothing, ignore_index, dl.data_ptr(), stream());
   return dl;
 }
@@ -1992,11 +1602,10 @@ Tensor ce_bwd(Tensor logits, Tensor target, Tensor lse, c10::optional<Tensor> dl
 // ----------------------------------------------------------------------------- layernorm
 // res: optional residual branch; then the sum s = x + res is returned as a 4th output and normalised.
 std::vector<Tensor> ln_fwd(Tensor x, Tensor w, Tensor b, double eps, c10::optional<Tensor> res) {
-  check_cuda(x, "x");
+  const Op op("ln_fwd", x);
   TORCH_CHECK(x.is_contiguous(), "ln: x must be contiguous");
   const int64_t D = x.size(-1), N = x.numel() / D;
-  TORCH_CHECK(w.scalar_type() == at::kFloat && b.scalar_type() == at::kFloat, "ln: weight/bias must be fp32");
-  const bool hr = res.has_value() && res->defined();
+  const bool hr = has(res);
   if (hr)
     TORCH_CHECK(res->is_contiguous() && res->sizes() == x.sizes() && res->scalar_type() == x.scalar_type(),
                 "ln: residual must match x (contiguous, same shape/dtype)");
@@ -2005,8 +1614,8 @@ std::vector<Tensor> ln_fwd(Tensor x, Tensor w, Tensor b, double eps, c10::option
   if (hr) sum = at::empty_like(x);
   auto fopt = x.options().dtype(at::kFloat);
   auto mean = at::empty({N}, fopt), rstd = at::empty({N}, fopt);
-  int rc = pdt_ln_fwd(x.data_ptr(), hr ? res->data_ptr() : nullptr, dcode(x), w.data_ptr<float>(),
-                      b.data_ptr<float>(), y.data_ptr(), hr ? sum.data_ptr() : nullptr, mean.data_ptr<float>(),
+  int rc = pdt_ln_fwd(x.data_ptr(), hr ? res->data_ptr() : nullptr, dcode(x), f32_ptr(op, "w", w, D),
+                      f32_ptr(op, "b", b, D), y.data_ptr(), hr ? sum.data_ptr() : nullptr, mean.data_ptr<float>(),
                       rstd.data_ptr<float>(), N, (int)D, (float)eps, stream());
   TORCH_CHECK(rc == 0, "pdt_ln_fwd: unsupported D=", D);
   return {y, mean, rstd, sum};
@@ -2016,13 +1625,12 @@ std::vector<Tensor> ln_fwd(Tensor x, Tensor w, Tensor b, double eps, c10::option
 // (+ res: s = x + res stored). Returns {yq [N, D], yq^T [D, N], mean, rstd, s}; state_row is the
 // consuming GEMM's input-operand row (amax, scale, ...).
 std::vector<Tensor> ln_fwd_fp8(Tensor x, Tensor w, Tensor b, double eps, c10::optional<Tensor> res, Tensor state_row) {
-  check_cuda(x, "x");
+  const Op op("ln_fwd_fp8", x);
   TORCH_CHECK(x.is_contiguous() && x.scalar_type() == at::kBFloat16, "ln_fp8: x must be contiguous bf16");
   const int64_t D = x.size(-1), N = x.numel() / D;
-  TORCH_CHECK(w.scalar_type() == at::kFloat && b.scalar_type() == at::kFloat, "ln_fp8: weight/bias must be fp32");
   TORCH_CHECK(state_row.scalar_type() == at::kFloat && state_row.numel() >= 3 && state_row.is_contiguous(),
               "ln_fp8: fp32 state row");
-  const bool hr = res.has_value() && res->defined();
+  const bool hr = has(res);
   if (hr)
     TORCH_CHECK(res->is_contiguous() && res->sizes() == x.sizes() && res->scalar_type() == x.scalar_type(),
                 "ln_fp8: residual must match x (contiguous, same shape/dtype)");
@@ -2033,21 +1641,19 @@ std::vector<Tensor> ln_fwd_fp8(Tensor x, Tensor w, Tensor b, double eps, c10::op
   auto fopt = x.options().dtype(at::kFloat);
   auto mean = at::empty({N}, fopt), rstd = at::empty({N}, fopt);
   float* st = state_row.data_ptr<float>();
-  int rc = pdt_ln_fwd_fp8(reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                          hr ? reinterpret_cast<const uint16_t*>(res->data_ptr()) : nullptr, w.data_ptr<float>(),
-                          b.data_ptr<float>(), hr ? reinterpret_cast<uint16_t*>(sum.data_ptr()) : nullptr,
-                          reinterpret_cast<uint8_t*>(yq.data_ptr()), reinterpret_cast<uint8_t*>(yqt.data_ptr()),
-                          mean.data_ptr<float>(), rstd.data_ptr<float>(), N, (int)D, (float)eps, st + 1, st,
-                          fp8_striped(state_row), stream());
+  int rc = pdt_ln_fwd_fp8(bf16_ptr(x), hr ? bf16_ptr(*res) : nullptr, f32_ptr(op, "w", w, D), f32_ptr(op, "b", b, D),
+                          ptr_or_null<uint16_t>(sum), byte_ptr(yq), byte_ptr(yqt), mean.data_ptr<float>(),
+                          rstd.data_ptr<float>(), N, (int)D, (float)eps, st + 1, st, fp8_striped(state_row), stream());
   TORCH_CHECK(rc == 0, "pdt_ln_fwd_fp8: unsupported N=", N, " D=", D);
   return {yq, yqt, mean, rstd, sum};
 }
 
 // dres: optional gradient added into dx (the residual stream's own gradient).
 std::vector<Tensor> ln_bwd(Tensor dy, Tensor x, Tensor w, Tensor mean, Tensor rstd, c10::optional<Tensor> dres) {
+  const Op op("ln_bwd", x);
   TORCH_CHECK(dy.is_contiguous() && x.is_contiguous(), "ln bwd: contiguous inputs required");
   const int64_t D = x.size(-1), N = x.numel() / D;
-  const bool hr = dres.has_value() && dres->defined();
+  const bool hr = has(dres);
   if (hr)
     TORCH_CHECK(dres->is_contiguous() && dres->sizes() == x.sizes() && dres->scalar_type() == x.scalar_type(),
                 "ln bwd: dres must match x (contiguous, same shape/dtype)");
@@ -2055,8 +1661,8 @@ std::vector<Tensor> ln_bwd(Tensor dy, Tensor x, Tensor w, Tensor mean, Tensor rs
   auto fopt = x.options().dtype(at::kFloat);
   auto dw = at::empty({D}, fopt), db = at::empty({D}, fopt);
   auto ws = at::empty({std::max<int64_t>(pdt_ln_workspace_floats(N, (int)D), 1)}, fopt);
-  int rc = pdt_ln_bwd(dy.data_ptr(), x.data_ptr(), hr ? dres->data_ptr() : nullptr, dcode(x), w.data_ptr<float>(),
-                      mean.data_ptr<float>(), rstd.data_ptr<float>(), dx.data_ptr(), dw.data_ptr<float>(),
+  int rc = pdt_ln_bwd(dy.data_ptr(), x.data_ptr(), hr ? dres->data_ptr() : nullptr, dcode(x), f32_ptr(op, "w", w, D),
+                      f32_ptr(op, "mean", mean, N), f32_ptr(op, "rstd", rstd, N), dx.data_ptr(), dw.data_ptr<float>(),
                       db.data_ptr<float>(), N, (int)D, ws.data_ptr<float>(), stream());
   TORCH_CHECK(rc == 0, "pdt_ln_bwd: unsupported D=", D);
   return {dx, dw, db};
@@ -2102,12 +1708,10 @@ Tensor dropout_mask(Tensor ticket, int64_t dstream, std::vector<int64_t> shape, 
   const int64_t* tp = ticket_ptr(ticket, out);
   int rc;
   if (kind == "flat") {
-    rc = pdt_dropout_mask_flat(reinterpret_cast<uint8_t*>(out.data_ptr()), out.numel(), tp, (int)dstream, (int)thr,
-                               stream());
+    rc = pdt_dropout_mask_flat(byte_ptr(out), out.numel(), tp, (int)dstream, (int)thr, stream());
   } else {
     TORCH_CHECK(kind == "attn" && shape.size() == 4 && shape[2] == shape[3], "dropout_mask: attn wants [B, H, T, T]");
-    rc = pdt_dropout_mask_attn(reinterpret_cast<uint8_t*>(out.data_ptr()), shape[0] * shape[1], (int)shape[2], tp,
-                               (int)dstream, (int)thr, stream());
+    rc = pdt_dropout_mask_attn(byte_ptr(out), shape[0] * shape[1], (int)shape[2], tp, (int)dstream, (int)thr, stream());
   }
   TORCH_CHECK(rc == 0, "pdt_dropout_mask failed: ", rc);
   return out;
@@ -2116,16 +1720,15 @@ Tensor dropout_mask(Tensor ticket, int64_t dstream, std::vector<int64_t> shape, 
 // s = x + dropout(res), y = LN(s): {y, mean, rstd, s}
 std::vector<Tensor> ln_fwd_drop(Tensor x, Tensor w, Tensor b, double eps, Tensor res, Tensor ticket, int64_t dstream,
                                 int64_t thr) {
-  check_cuda(x, "x");
+  const Op op("ln_fwd_drop", x);
   TORCH_CHECK(x.is_contiguous(), "ln: x must be contiguous");
   const int64_t D = x.size(-1), N = x.numel() / D;
-  TORCH_CHECK(w.scalar_type() == at::kFloat && b.scalar_type() == at::kFloat, "ln: weight/bias must be fp32");
   TORCH_CHECK(res.is_contiguous() && res.sizes() == x.sizes() && res.scalar_type() == x.scalar_type(),
               "ln: residual must match x (contiguous, same shape/dtype)");
   auto y = at::empty_like(x), sum = at::empty_like(x);
   auto fopt = x.options().dtype(at::kFloat);
   auto mean = at::empty({N}, fopt), rstd = at::empty({N}, fopt);
-  int rc = pdt_ln_fwd_drop(x.data_ptr(), res.data_ptr(), dcode(x), w.data_ptr<float>(), b.data_ptr<float>(),
+  int rc = pdt_ln_fwd_drop(x.data_ptr(), res.data_ptr(), dcode(x), f32_ptr(op, "w", w, D), f32_ptr(op, "b", b, D),
                            y.data_ptr(), sum.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(), N, (int)D,
                            (float)eps, ticket_ptr(ticket, x), (int)dstream, check_thr(thr), stream());
   TORCH_CHECK(rc == 0, "pdt_ln_fwd_drop: unsupported D=", D);
@@ -2135,9 +1738,10 @@ std::vector<Tensor> ln_fwd_drop(Tensor x, Tensor w, Tensor b, double eps, Tensor
 // {dx, dh, dw, db}: dx as ln_bwd, dh = the dropout backward of dx (the dropped branch's gradient)
 std::vector<Tensor> ln_bwd_drop(Tensor dy, Tensor x, Tensor w, Tensor mean, Tensor rstd, c10::optional<Tensor> dres,
                                 Tensor ticket, int64_t dstream, int64_t thr) {
+  const Op op("ln_bwd_drop", x);
   TORCH_CHECK(dy.is_contiguous() && x.is_contiguous(), "ln bwd: contiguous inputs required");
   const int64_t D = x.size(-1), N = x.numel() / D;
-  const bool hr = dres.has_value() && dres->defined();
+  const bool hr = has(dres);
   if (hr)
     TORCH_CHECK(dres->is_contiguous() && dres->sizes() == x.sizes() && dres->scalar_type() == x.scalar_type(),
                 "ln bwd: dres must match x (contiguous, same shape/dtype)");
@@ -2146,9 +1750,9 @@ std::vector<Tensor> ln_bwd_drop(Tensor dy, Tensor x, Tensor w, Tensor mean, Tens
   auto dw = at::empty({D}, fopt), db = at::empty({D}, fopt);
   auto ws = at::empty({std::max<int64_t>(pdt_ln_workspace_floats(N, (int)D), 1)}, fopt);
   int rc = pdt_ln_bwd_drop(dy.data_ptr(), x.data_ptr(), hr ? dres->data_ptr() : nullptr, dcode(x),
-                           w.data_ptr<float>(), mean.data_ptr<float>(), rstd.data_ptr<float>(), dx.data_ptr(),
-                           dh.data_ptr(), dw.data_ptr<float>(), db.data_ptr<float>(), N, (int)D, ws.data_ptr<float>(),
-                           ticket_ptr(ticket, x), (int)dstream, check_thr(thr), stream());
+                           f32_ptr(op, "w", w, D), f32_ptr(op, "mean", mean, N), f32_ptr(op, "rstd", rstd, N),
+                           dx.data_ptr(), dh.data_ptr(), dw.data_ptr<float>(), db.data_ptr<float>(), N, (int)D,
+                           ws.data_ptr<float>(), ticket_ptr(ticket, x), (int)dstream, check_thr(thr), stream());
   TORCH_CHECK(rc == 0, "pdt_ln_bwd_drop: unsupported D=", D);
   return {dx, dh, dw, db};
 }
@@ -2158,7 +1762,7 @@ Tensor bias_gelu_fwd(Tensor x, c10::optional<Tensor> bias, bool tanh_form) {
   TORCH_CHECK(x.is_contiguous(), "gelu: x must be contiguous");
   const int64_t D = x.size(-1), N = x.numel() / D;
   auto y = at::empty_like(x);
-  const bool hb = bias.has_value() && bias->defined();
+  const bool hb = has(bias);
   const bool bb = hb && bias->scalar_type() == at::kBFloat16;  // a bf16 model's bias, read as is
   if (hb) {
     check_cuda(*bias, "bias");
@@ -2176,7 +1780,7 @@ std::vector<Tensor> bias_gelu_bwd(Tensor dy, Tensor x, c10::optional<Tensor> bia
   const int64_t D = x.size(-1), N = x.numel() / D;
   auto dx = at::empty_like(x);
   auto fopt = x.options().dtype(at::kFloat);
-  const bool hb = bias.has_value() && bias->defined();
+  const bool hb = has(bias);
   const bool bb = hb && bias->scalar_type() == at::kBFloat16;
   Tensor db, ws;
   if (hb) {
@@ -2185,7 +1789,7 @@ std::vector<Tensor> bias_gelu_bwd(Tensor dy, Tensor x, c10::optional<Tensor> bia
   }
   int rc = pdt_bias_gelu_bwd(dy.data_ptr(), x.data_ptr(), dcode(x), hb ? bias->data_ptr() : nullptr, dx.data_ptr(),
                              hb ? db.data_ptr() : nullptr, N, (int)D, tanh_form,
-                             hb ? ws.data_ptr<float>() : nullptr, stream(), bb ? 1 : 0);
+                             ptr_or_null<float>(ws), stream(), bb ? 1 : 0);
   TORCH_CHECK(rc == 0, "pdt_bias_gelu_bwd failed");
   return {dx, db};
 }
@@ -2210,10 +1814,8 @@ void attn_fwd_out(Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causa
   TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() && lse.numel() == q.size(0) * q.size(1) * q.size(2),
               "attn: lse must be fp32 [B,H,T]");
   const int B = q.size(0), H = q.size(1), T = q.size(2), Dh = q.size(3);
-  int rc = pdt_attn_fwd(reinterpret_cast<const uint16_t*>(q.data_ptr()), qs.v, reinterpret_cast<const uint16_t*>(k.data_ptr()),
-                        ks.v, reinterpret_cast<const uint16_t*>(v.data_ptr()), vs.v,
-                        reinterpret_cast<uint16_t*>(o.data_ptr()), os.v, lse.data_ptr<float>(), B, H, T, Dh, causal,
-                        (float)scale, stream());
+  int rc = pdt_attn_fwd(bf16_ptr(q), qs.v, bf16_ptr(k), ks.v, bf16_ptr(v), vs.v, bf16_out(o), os.v,
+                        lse.data_ptr<float>(), B, H, T, Dh, causal, (float)scale, stream());
   TORCH_CHECK(rc == 0, "pdt_attn_fwd: unsupported head dim ", Dh);
 }
 
@@ -2225,13 +1827,9 @@ void attn_bwd_out(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor ls
               gs.v[1] == gv.v[1] && gs.v[2] == gv.v[2], "attn bwd: dq/dk/dv must share strides");
   const int B = q.size(0), H = q.size(1), T = q.size(2), Dh = q.size(3);
   auto delta = at::empty({(int64_t)B * H * T}, q.options().dtype(at::kFloat));
-  int rc = pdt_attn_bwd(reinterpret_cast<const uint16_t*>(dout.data_ptr()), dos.v,
-                        reinterpret_cast<const uint16_t*>(q.data_ptr()), qs.v, reinterpret_cast<const uint16_t*>(k.data_ptr()),
-                        ks.v, reinterpret_cast<const uint16_t*>(v.data_ptr()), vs.v,
-                        reinterpret_cast<const uint16_t*>(o.data_ptr()), os.v, lse.data_ptr<float>(),
-                        delta.data_ptr<float>(), reinterpret_cast<uint16_t*>(dq.data_ptr()),
-                        reinterpret_cast<uint16_t*>(dk.data_ptr()), reinterpret_cast<uint16_t*>(dv.data_ptr()), gs.v, B,
-                        H, T, Dh, causal, (float)scale, stream());
+  int rc = pdt_attn_bwd(bf16_ptr(dout), dos.v, bf16_ptr(q), qs.v, bf16_ptr(k), ks.v, bf16_ptr(v), vs.v, bf16_ptr(o),
+                        os.v, lse.data_ptr<float>(), delta.data_ptr<float>(), bf16_out(dq), bf16_out(dk), bf16_out(dv),
+                        gs.v, B, H, T, Dh, causal, (float)scale, stream());
   TORCH_CHECK(rc == 0, "pdt_attn_bwd: unsupported head dim ", Dh);
 }
 
@@ -2243,11 +1841,9 @@ void attn_fwd_drop_out(Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool 
   TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() && lse.numel() == q.size(0) * q.size(1) * q.size(2),
               "attn: lse must be fp32 [B,H,T]");
   const int B = q.size(0), H = q.size(1), T = q.size(2), Dh = q.size(3);
-  int rc = pdt_attn_fwd_drop(reinterpret_cast<const uint16_t*>(q.data_ptr()), qs.v,
-                             reinterpret_cast<const uint16_t*>(k.data_ptr()), ks.v,
-                             reinterpret_cast<const uint16_t*>(v.data_ptr()), vs.v,
-                             reinterpret_cast<uint16_t*>(o.data_ptr()), os.v, lse.data_ptr<float>(), B, H, T, Dh, causal,
-                             (float)scale, ticket_ptr(ticket, q), (int)dstream, check_thr(thr), stream());
+  int rc = pdt_attn_fwd_drop(bf16_ptr(q), qs.v, bf16_ptr(k), ks.v, bf16_ptr(v), vs.v, bf16_out(o), os.v,
+                             lse.data_ptr<float>(), B, H, T, Dh, causal, (float)scale, ticket_ptr(ticket, q),
+                             (int)dstream, check_thr(thr), stream());
   TORCH_CHECK(rc == 0, "pdt_attn_fwd_drop: unsupported head dim ", Dh);
 }
 
@@ -2263,42 +1859,36 @@ void attn_bwd_drop_out(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tens
   TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() && lse.numel() == (int64_t)B * H * T,
               "attn bwd: lse must be fp32 [B,H,T]");
   auto delta = at::empty({(int64_t)B * H * T}, q.options().dtype(at::kFloat));
-  int rc = pdt_attn_bwd_drop(reinterpret_cast<const uint16_t*>(dout.data_ptr()), dos.v,
-                             reinterpret_cast<const uint16_t*>(q.data_ptr()), qs.v,
-                             reinterpret_cast<const uint16_t*>(k.data_ptr()), ks.v,
-                             reinterpret_cast<const uint16_t*>(v.data_ptr()), vs.v,
-                             reinterpret_cast<const uint16_t*>(o.data_ptr()), os.v, lse.data_ptr<float>(),
-                             delta.data_ptr<float>(), reinterpret_cast<uint16_t*>(dq.data_ptr()),
-                             reinterpret_cast<uint16_t*>(dk.data_ptr()), reinterpret_cast<uint16_t*>(dv.data_ptr()), gs.v, B,
-                             H, T, Dh, causal, (float)scale, ticket_ptr(ticket, q), (int)dstream, check_thr(thr),
-                             stream());
+  int rc = pdt_attn_bwd_drop(bf16_ptr(dout), dos.v, bf16_ptr(q), qs.v, bf16_ptr(k), ks.v, bf16_ptr(v), vs.v,
+                             bf16_ptr(o), os.v, lse.data_ptr<float>(), delta.data_ptr<float>(), bf16_out(dq),
+                             bf16_out(dk), bf16_out(dv), gs.v, B, H, T, Dh, causal, (float)scale, ticket_ptr(ticket, q),
+                             (int)dstream, check_thr(thr), stream());
   TORCH_CHECK(rc == 0, "pdt_attn_bwd_drop: unsupported head dim ", Dh);
 }
 
 // bias gradient of a Linear layer: column sum of dy [*, D] -> [D] in out_dtype (fp32 / bf16)
 // xs = x[:, :, ::s, ::s] for a channels_last bf16 [N, C, H, W] tensor (C % 8 == 0), channels_last out.
 Tensor subsample_gather(Tensor x, int64_t s) {
-  check_nhwc_bf16(x, "x");
+  const Op op("subsample_gather", x);
+  check_nhwc_bf16(op, "x", x);
   const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   TORCH_CHECK(C % 8 == 0 && s >= 1, "subsample_gather: C % 8 == 0, s >= 1");
   auto xs = at::empty({N, C, (H - 1) / s + 1, (W - 1) / s + 1}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  const int rc = pdt_subsample_gather(reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                                      reinterpret_cast<uint16_t*>(xs.data_ptr()), (int)N, (int)H, (int)W, (int)C,
-                                      (int)s, stream());
+  const int rc = pdt_subsample_gather(bf16_ptr(x), bf16_out(xs), (int)N, (int)H, (int)W, (int)C, (int)s, stream());
   TORCH_CHECK(rc == 0, "pdt_subsample_gather failed: ", rc);
   return xs;
 }
 
 // full[:, :, ::s, ::s] += t (in place; both channels_last bf16).
 void subsample_scatter_add(Tensor t, Tensor full, int64_t s) {
-  check_nhwc_bf16(t, "t");
-  check_nhwc_bf16(full, "full");
+  const Op op("subsample_scatter_add", t);
+  check_nhwc_bf16(op, "t", t);
+  check_nhwc_bf16(op, "full", full);
   const int64_t N = full.size(0), C = full.size(1), H = full.size(2), W = full.size(3);
   TORCH_CHECK(t.size(0) == N && t.size(1) == C && t.size(2) == (H - 1) / s + 1 && t.size(3) == (W - 1) / s + 1 &&
               C % 8 == 0, "subsample_scatter_add: shape");
-  const int rc = pdt_subsample_scatter_add(reinterpret_cast<const uint16_t*>(t.data_ptr()),
-                                           reinterpret_cast<uint16_t*>(full.data_ptr()), (int)N, (int)H, (int)W,
-                                           (int)C, (int)s, stream());
+  const int rc = pdt_subsample_scatter_add(bf16_ptr(t), bf16_out(full), (int)N, (int)H, (int)W, (int)C, (int)s,
+                                           stream());
   TORCH_CHECK(rc == 0, "pdt_subsample_scatter_add failed: ", rc);
 }
 
@@ -2308,8 +1898,7 @@ Tensor slice_sum(Tensor x) {
   TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.is_contiguous() && x.dim() >= 2, "slice_sum: contiguous bf16 [S, ...]");
   const int64_t S = x.size(0), n = x.numel() / S;
   auto out = at::empty(x.sizes().slice(1), x.options());
-  const int rc = pdt_slice_sum_bf16(reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                                    reinterpret_cast<uint16_t*>(out.data_ptr()), (int)S, n, stream());
+  const int rc = pdt_slice_sum_bf16(bf16_ptr(x), bf16_out(out), (int)S, n, stream());
   TORCH_CHECK(rc == 0, "pdt_slice_sum_bf16 failed: ", rc);
   return out;
 }
@@ -2341,9 +1930,7 @@ std::vector<Tensor> fp8_cast_transpose(Tensor x, Tensor state_row, bool transpos
   Tensor out_t;
   if (transpose) out_t = at::empty({K, M}, o8);
   float* st = state_row.data_ptr<float>();
-  int rc = pdt_fp8_cast_transpose(reinterpret_cast<const uint16_t*>(x.data_ptr()), M, K, st + 1,
-                                  reinterpret_cast<uint8_t*>(out.data_ptr()),
-                                  transpose ? reinterpret_cast<uint8_t*>(out_t.data_ptr()) : nullptr, st,
+  int rc = pdt_fp8_cast_transpose(bf16_ptr(x), M, K, st + 1, byte_ptr(out), transpose ? byte_ptr(out_t) : nullptr, st,
                                   fp8_striped(state_row), stream());
   TORCH_CHECK(rc == 0, "pdt_fp8_cast_transpose failed");
   return {out, out_t};
@@ -2361,11 +1948,11 @@ std::vector<Tensor> fp8_gelu_cast(Tensor h, c10::optional<Tensor> dg, c10::optio
               "fp8_gelu_cast: fp32 state row");
   const int64_t M = h.size(0), D = h.size(1);
   TORCH_CHECK(M % 16 == 0 && D % 64 == 0 && M > 0, "fp8_gelu_cast: M % 16 == 0 and D % 64 == 0");
-  const bool bwd = dg.has_value() && dg->defined();
+  const bool bwd = has(dg);
   if (bwd)
     TORCH_CHECK(dg->scalar_type() == at::kBFloat16 && dg->sizes() == h.sizes() && dg->is_contiguous(),
                 "fp8_gelu_cast: dg like h");
-  const bool hb = bias.has_value() && bias->defined();
+  const bool hb = has(bias);
   if (hb)
     TORCH_CHECK(bias->scalar_type() == at::kFloat && bias->is_contiguous() && bias->numel() == D,
                 "fp8_gelu_cast: fp32 bias [D]");
@@ -2374,12 +1961,10 @@ std::vector<Tensor> fp8_gelu_cast(Tensor h, c10::optional<Tensor> dg, c10::optio
   Tensor part, db;
   if (bwd) part = at::empty({pdt_fp8_gelu_cast_workspace_floats(M, (int)D)}, h.options().dtype(at::kFloat));
   float* st = state_row.data_ptr<float>();
-  const int nchunk = pdt_fp8_gelu_cast(reinterpret_cast<const uint16_t*>(h.data_ptr()),
-                                       bwd ? reinterpret_cast<const uint16_t*>(dg->data_ptr()) : nullptr,
+  const int nchunk = pdt_fp8_gelu_cast(bf16_ptr(h), bwd ? bf16_ptr(*dg) : nullptr,
                                        hb ? bias->data_ptr<float>() : nullptr, M, (int)D, tanh_form, st + 1,
-                                       reinterpret_cast<uint8_t*>(out.data_ptr()),
-                                       reinterpret_cast<uint8_t*>(out_t.data_ptr()), st,
-                                       bwd ? part.data_ptr<float>() : nullptr, fp8_striped(state_row), stream());
+                                       byte_ptr(out), byte_ptr(out_t), st, ptr_or_null<float>(part),
+                                       fp8_striped(state_row), stream());
   TORCH_CHECK(nchunk > 0, "pdt_fp8_gelu_cast failed: ", nchunk);
   if (bwd && hb) {
     TORCH_CHECK(db_dtype == at::kFloat || db_dtype == at::kBFloat16, "fp8_gelu_cast: db dtype fp32 / bf16");
@@ -2405,10 +1990,8 @@ std::vector<Tensor> fp8_cast_colsum(Tensor x, Tensor state_row, at::ScalarType d
   auto part = at::empty({pdt_fp8_gelu_cast_workspace_floats(M, (int)D)}, x.options().dtype(at::kFloat));
   auto db = at::empty({D}, x.options().dtype(db_dtype));
   float* st = state_row.data_ptr<float>();
-  const int nchunk = pdt_fp8_cast_colsum(reinterpret_cast<const uint16_t*>(x.data_ptr()), M, (int)D, st + 1,
-                                         reinterpret_cast<uint8_t*>(out.data_ptr()),
-                                         reinterpret_cast<uint8_t*>(out_t.data_ptr()), st, part.data_ptr<float>(),
-                                         fp8_striped(state_row), stream());
+  const int nchunk = pdt_fp8_cast_colsum(bf16_ptr(x), M, (int)D, st + 1, byte_ptr(out), byte_ptr(out_t), st,
+                                         part.data_ptr<float>(), fp8_striped(state_row), stream());
   TORCH_CHECK(nchunk > 0, "pdt_fp8_cast_colsum failed: ", nchunk);
   pdt_colsum_finalize(part.data_ptr<float>(), nchunk, (int)D, db.data_ptr(), db_dtype == at::kFloat ? 0 : 1, stream());
   return {out, out_t, db};
@@ -2437,13 +2020,13 @@ std::vector<Tensor> fp8_cast_multi(std::vector<Tensor> xs, std::vector<Tensor> r
       auto o8 = x.options().dtype(at::kFloat8_e4m3fn);
       res.push_back(at::empty({M, K}, o8));
       res.push_back(at::empty({K, M}, o8));
-      px[i] = reinterpret_cast<const uint16_t*>(x.data_ptr());
+      px[i] = bf16_ptr(x);
       pm[i] = (int)M;
       pk[i] = (int)K;
       ps[i] = r.data_ptr<float>();
       pst[i] = fp8_striped(r);
-      po[i] = reinterpret_cast<uint8_t*>(res[res.size() - 2].data_ptr());
-      pt[i] = reinterpret_cast<uint8_t*>(res.back().data_ptr());
+      po[i] = byte_ptr(res[res.size() - 2]);
+      pt[i] = byte_ptr(res.back());
     }
     const int rc = pdt_fp8_cast_multi(n, px.data(), pm.data(), pk.data(), ps.data(), pst.data(), po.data(), pt.data(),
                                       stream());
@@ -2454,7 +2037,7 @@ std::vector<Tensor> fp8_cast_multi(std::vector<Tensor> xs, std::vector<Tensor> r
 
 void fp8_update_scales(Tensor state, int64_t history, double margin) {
   check_cuda(state, "state");
-  const bool striped = state.dim() == 2 && state.size(1) == kFp8StripedRow - 1 + history;
+  const bool striped = state.dim() == 2 && state.size(1) == pdt::kAmaxHist + history;
   TORCH_CHECK(state.scalar_type() == at::kFloat && state.is_contiguous() && state.dim() == 2 &&
                   (state.size(1) == 3 + history || striped),
               "fp8_update_scales: state [n, 3 + L] or striped [n, 260 + L] fp32");
@@ -2589,10 +2172,8 @@ Tensor embedding_fwd(Tensor idx, Tensor wte, Tensor wpe) {
   const int64_t B = idx.size(0), T = idx.size(1), D = wte.size(1);
   TORCH_CHECK(T <= wpe.size(0) && D % 8 == 0, "embedding: T <= P, D % 8 == 0");
   auto out = at::empty({B, T, D}, wte.options());
-  TORCH_CHECK(pdt_embedding_fwd(idx.data_ptr<int64_t>(), reinterpret_cast<const uint16_t*>(wte.data_ptr()),
-                                reinterpret_cast<const uint16_t*>(wpe.data_ptr()),
-                                reinterpret_cast<uint16_t*>(out.data_ptr()), B * T, (int)T, (int)D, (int)wte.size(0),
-                                embedding_err(idx).data_ptr<int>(), stream()) == 0,
+  TORCH_CHECK(pdt_embedding_fwd(idx.data_ptr<int64_t>(), bf16_ptr(wte), bf16_ptr(wpe), bf16_out(out), B * T, (int)T,
+                                (int)D, (int)wte.size(0), embedding_err(idx).data_ptr<int>(), stream()) == 0,
               "pdt_embedding_fwd failed");
   return out;
 }
@@ -2608,8 +2189,7 @@ std::vector<Tensor> embedding_bwd(Tensor idx, Tensor dout, int64_t V, int64_t P)
   auto ws = at::zeros({pdt_embedding_bwd_ws_ints(n, (int)V)}, idx.options().dtype(at::kInt));
   auto dwte = at::empty({V, D}, dout.options());
   auto dwpe = T == P ? at::empty({P, D}, dout.options()) : at::zeros({P, D}, dout.options());
-  TORCH_CHECK(pdt_embedding_bwd(idx.data_ptr<int64_t>(), reinterpret_cast<const uint16_t*>(dout.data_ptr()),
-                                reinterpret_cast<uint16_t*>(dwte.data_ptr()), reinterpret_cast<uint16_t*>(dwpe.data_ptr()),
+  TORCH_CHECK(pdt_embedding_bwd(idx.data_ptr<int64_t>(), bf16_ptr(dout), bf16_out(dwte), bf16_out(dwpe),
                                 ws.data_ptr<int>(), n, (int)B, (int)T, (int)V, (int)D,
                                 embedding_err(idx).data_ptr<int>(), stream()) == 0,
               "pdt_embedding_bwd failed");
@@ -2628,7 +2208,7 @@ std::vector<Tensor> gemm_nt(Tensor a, Tensor b, c10::optional<Tensor> bias, int6
   const int64_t M = a.size(0), K = a.size(1), N = b.size(0);
   const void* bp = nullptr;
   int bf32 = 0;
-  if (bias.has_value() && bias->defined()) {
+  if (has(bias)) {
     TORCH_CHECK(bias->is_contiguous() && bias->numel() == N &&
                     (bias->scalar_type() == at::kFloat || bias->scalar_type() == at::kBFloat16),
                 "gemm_nt: bias [N] fp32 or bf16");
@@ -2637,9 +2217,7 @@ std::vector<Tensor> gemm_nt(Tensor a, Tensor b, c10::optional<Tensor> bias, int6
   }
   auto c = at::empty({M, N}, a.options());
   Tensor g = epi == 2 ? at::empty({M, N}, a.options()) : Tensor();
-  const int rc = pdt_gemm_nt(reinterpret_cast<const uint16_t*>(a.data_ptr()), reinterpret_cast<const uint16_t*>(b.data_ptr()),
-                             reinterpret_cast<uint16_t*>(c.data_ptr()),
-                             epi == 2 ? reinterpret_cast<uint16_t*>(g.data_ptr()) : nullptr, bp, bf32, (int)epi,
+  const int rc = pdt_gemm_nt(bf16_ptr(a), bf16_ptr(b), bf16_out(c), ptr_or_null<uint16_t>(g), bp, bf32, (int)epi,
                              tanh_form ? 1 : 0, (int)M, (int)N, (int)K, stream());
   TORCH_CHECK(rc == 0, "pdt_gemm_nt failed (", rc, ") for M=", M, " N=", N, " K=", K);
   if (epi == 2) return {c, g};
@@ -2660,7 +2238,7 @@ Tensor gemm_nt_fp8(Tensor a, Tensor b, Tensor sa, Tensor sb, c10::optional<Tenso
   const int64_t M = a.size(0), K = a.size(1), N = b.size(0);
   const void* bp = nullptr;
   int bf32 = 0;
-  if (bias.has_value() && bias->defined()) {
+  if (has(bias)) {
     TORCH_CHECK(bias->is_contiguous() && bias->numel() == N &&
                     (bias->scalar_type() == at::kFloat || bias->scalar_type() == at::kBFloat16),
                 "gemm_nt_fp8: bias [N] fp32 or bf16");
@@ -2672,10 +2250,8 @@ Tensor gemm_nt_fp8(Tensor a, Tensor b, Tensor sa, Tensor sb, c10::optional<Tenso
   const int ks = bp ? 1 : pdt_gemm_nt_fp8_ksplit((int)M, (int)N, (int)K);
   Tensor ws;
   if (ks > 1) ws = at::empty({(int64_t)ks * M * N}, a.options().dtype(at::kFloat));
-  const int rc = pdt_gemm_nt_fp8(reinterpret_cast<const uint8_t*>(a.data_ptr()), reinterpret_cast<const uint8_t*>(b.data_ptr()),
-                                 reinterpret_cast<uint16_t*>(c.data_ptr()), sa.data_ptr<float>(), sb.data_ptr<float>(), bp,
-                                 bf32, bp ? 1 : 0, (int)M, (int)N, (int)K, ks > 1 ? ws.data_ptr<float>() : nullptr, ks,
-                                 stream());
+  const int rc = pdt_gemm_nt_fp8(byte_ptr(a), byte_ptr(b), bf16_out(c), sa.data_ptr<float>(), sb.data_ptr<float>(), bp,
+                                 bf32, bp ? 1 : 0, (int)M, (int)N, (int)K, ptr_or_null<float>(ws), ks, stream());
   TORCH_CHECK(rc == 0, "pdt_gemm_nt_fp8 failed (", rc, ") for M=", M, " N=", N, " K=", K);
   return c;
 }
@@ -2747,13 +2323,13 @@ std::vector<Tensor> softmax_nll_small(Tensor logits, Tensor target, int64_t mode
   if (want_loss) loss = at::empty({N}, logits.options().dtype(at::kFloat));
   if (want_grad) dl = at::empty_like(logits);
   double* ap = nullptr;
-  if (acc.has_value() && acc->defined()) {
+  if (has(acc)) {
     TORCH_CHECK(acc->scalar_type() == at::kDouble && acc->numel() >= 3, "softmax_nll_small: acc fp64 [3]");
     ap = acc->data_ptr<double>();
   }
   int rc = pdt_softmax_nll_small(logits.data_ptr(), dcode(logits), target.data_ptr<int64_t>(), N,
                                  (int)logits.size(1), (int)mode, (float)smoothing,
-                                 want_loss ? loss.data_ptr<float>() : nullptr, want_grad ? dl.data_ptr() : nullptr,
+                                 ptr_or_null<float>(loss), want_grad ? dl.data_ptr() : nullptr,
                                  (float)dscale, ap, stream());
   TORCH_CHECK(rc == 0, "pdt_softmax_nll_small failed");
   if (mean_scale > 0.0 && want_loss) {

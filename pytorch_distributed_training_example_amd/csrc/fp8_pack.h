@@ -1,6 +1,8 @@
 // OCP e4m3fn (gfx950 fp8) packing shared by the cast kernels (kernels/fp8.hip) and the producers
 // that emit fp8 directly (kernels/layernorm.hip).
 #pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
 
 namespace pdt {
 

@@ -12,6 +12,7 @@
 //  * pdt_mt_copy       : dst = src * scale with dtype conversion (bucket flatten/unflatten,
 //                        fp32 <-> bf16 reduction buffers), 1/world folded in.
 #include "../multi_tensor.h"
+#include "../launchers.h"
 
 using namespace pdt;
 

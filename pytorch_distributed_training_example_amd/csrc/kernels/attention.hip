@@ -28,6 +28,7 @@
 // forward / dQ; the 2 key subtiles x 2 query subtiles of a 32-query step in dK/dV) and the words go
 // round by quad-broadcast DPP moves: one Philox call per 16 scores instead of one per 4.
 #include "../common.h"
+#include "../launchers.h"
 #include "../philox.h"
 
 #include <type_traits>

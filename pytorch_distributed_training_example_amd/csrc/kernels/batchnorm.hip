@@ -19,6 +19,7 @@
 //   reduce+finalize : Σdz, Σdz(x-mean) with dz = dy·mask → dgamma, dbeta, dx coefficients
 //   apply           : dx = A·dz + B·(x-mean) + D (and dres = dz for the residual branch)
 #include "../common.h"
+#include "../launchers.h"
 #include <algorithm>
 #include "../tile_stats.h"
 

@@ -16,6 +16,7 @@
 // W, the coefficients and the fp32 products G (= W^T diag(B) W) and BWG (= diag(B) W Gram).
 // Not in the reference (LeNet has no BatchNorm, /root/reference/cnn.py:9-23).
 #include "../common.h"
+#include "../launchers.h"
 
 #include <stdlib.h>
 

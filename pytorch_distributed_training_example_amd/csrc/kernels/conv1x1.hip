@@ -52,6 +52,7 @@
 //                 dz from the bf16 values written). The pass that would re-read dy is gone; xb is
 //                 read once here instead (ops/batchnorm.py GradStatsSource, bn_bwd_train_tiles).
 #include "../common.h"
+#include "../launchers.h"
 #include "../tile_stats.h"
 
 #include <stdlib.h>

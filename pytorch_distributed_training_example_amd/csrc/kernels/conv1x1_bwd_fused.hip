@@ -41,6 +41,7 @@
 //     bn2's ReLU mask is computed from xb and WRITTEN here (bn2's backward apply reads it next): xa and
 //     the mask bits are never read.
 #include "../common.h"
+#include "../launchers.h"
 #include "../tile_stats.h"
 
 using namespace pdt;

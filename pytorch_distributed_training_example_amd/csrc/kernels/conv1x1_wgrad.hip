@@ -23,6 +23,7 @@
 //     bank groups;
 //   * waves tile the block as WCO x WCI of v_mfma_f32_32x32x16_bf16 32x32 accumulators.
 #include "../common.h"
+#include "../launchers.h"
 
 using namespace pdt;
 

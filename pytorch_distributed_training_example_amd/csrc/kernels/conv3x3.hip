@@ -28,6 +28,7 @@
 //   * block -> tile map XCD-aware (xcd_remap): the output-channel tiles of one pixel tile, and
 //     neighbouring pixel tiles (which share input rows), run on one XCD's L2.
 #include "../common.h"
+#include "../launchers.h"
 #include "../tile_stats.h"
 
 using namespace pdt;

@@ -26,6 +26,7 @@
 // rows, operands swapped so a lane's accumulator holds 4 channels of one pixel, bf16 tile staged
 // through LDS for 16-B row stores and the fused BatchNorm epilogues, XCD-aware tile map).
 #include "../common.h"
+#include "../launchers.h"
 #include "../tile_stats.h"
 
 using namespace pdt;

@@ -37,6 +37,7 @@
 // stay conflict-free) and tap (kh, kw) is the row shift kh * 2 HALF + {0, HALF, 1}[kw]. About 4
 // input pixels per output pixel are staged (vs ~1.5 at stride 1), so tiles are 2-8 output rows.
 #include "../common.h"
+#include "../launchers.h"
 
 using namespace pdt;
 

@@ -32,6 +32,7 @@
 //     non-persistent version (4-row tiles, 3 workgroups per CU, weights re-staged and the window
 //     loaded then waited on per tile) ran 384 us at batch 512 vs MIOpen's 860 us.
 #include "../common.h"
+#include "../launchers.h"
 #include "../tile_stats.h"
 
 #include <algorithm>

@@ -8,6 +8,7 @@
 //   dropout_mask_*        the bool mask itself, through the same device functions the fused kernels
 //                         (layernorm.hip, attention.hip) inline: what the tests compare with the CPU.
 #include "../common.h"
+#include "../launchers.h"
 #include "../philox.h"
 
 using namespace pdt;

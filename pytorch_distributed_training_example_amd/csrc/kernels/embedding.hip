@@ -18,6 +18,7 @@
 // row is zeros, its gradient row is dropped) and sets a device error word that the host reads
 // (ops/embedding.py: raised like nn.Embedding's index error), instead of out-of-bounds atomics.
 #include "../common.h"
+#include "../launchers.h"
 
 using namespace pdt;
 

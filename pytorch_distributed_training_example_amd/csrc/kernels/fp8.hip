@@ -15,6 +15,7 @@
 //   fp8_update_scales: one launch per step for ALL fp8 tensors of a model: push amax into the
 //     history (shift register), scale = 448 / (max(history) * 2^margin), scale_inv = 1/scale, reset amax.
 #include "../common.h"
+#include "../launchers.h"
 #include "../fp8_pack.h"
 #include "../gelu_math.h"
 

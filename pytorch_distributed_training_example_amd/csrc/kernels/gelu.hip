@@ -6,6 +6,7 @@
 // fixed order) and reduced by a small finalize kernel. The same column-strip kernel without the
 // GELU part is the bias gradient of every Linear layer (pdt_colsum, ops/linear.py).
 #include "../common.h"
+#include "../launchers.h"
 #include "../gelu_math.h"
 
 using namespace pdt;

@@ -36,6 +36,7 @@
 //     map is XCD-aware (xcd_remap): the ~32 tiles resident on one XCD span 4 A bands x 8 B bands
 //     and share both in its L2 (8k^3: 1421 vs 1309 TF for plain N-first order).
 #include "../common.h"
+#include "../launchers.h"
 
 #include <algorithm>
 

@@ -12,6 +12,7 @@
 // residual stream's own gradient, dx = LN'(dy) + ds. That removes the separate add kernels
 // (2 per block forward, 2 per block backward) and one full read of s.
 #include "../common.h"
+#include "../launchers.h"
 #include "../fp8_pack.h"
 #include "../philox.h"
 

@@ -25,6 +25,7 @@
 // and the momentum buffers bit for bit. lr, the inverse loss scale, the inf flag and LAMB's step count
 // are read from device memory: a captured step replays with the current values.
 #include "../multi_tensor.h"
+#include "../launchers.h"
 
 using namespace pdt;
 

@@ -23,6 +23,7 @@
 //     and with the eval metrics (sum loss, correct count accumulated on device — no per-batch
 //     .item() like train.py:68-70).
 #include "../common.h"
+#include "../launchers.h"
 
 using namespace pdt;
 

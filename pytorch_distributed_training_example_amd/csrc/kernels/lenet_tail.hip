@@ -22,6 +22,7 @@
 //                    (dW3 = sum_b g3 (x) p2, dfw1 = sum_b g4 (x) h3, dfw2 = sum_b dl (x) h4, the biases, and
 //                    the conv2 slabs): deterministic, no atomics.
 #include "../common.h"
+#include "../launchers.h"
 
 using namespace pdt;
 

@@ -9,6 +9,7 @@
 // inverse scale, the inf flag and the Adam step come from device memory so a captured
 // hipGraph replays with the current values.
 #include "../multi_tensor.h"
+#include "../launchers.h"
 
 using namespace pdt;
 

@@ -37,6 +37,7 @@
 // ends. Waits test `== epoch` on monotonically increasing values in per-kind slots, so a peer
 // that is one call ahead never overwrites a flag I have not read yet.
 #include "../common.h"
+#include "../launchers.h"
 
 using namespace pdt;
 

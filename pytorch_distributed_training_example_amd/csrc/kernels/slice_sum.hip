@@ -7,6 +7,7 @@
 // the first add), one 16-B store, a grid-stride loop of 8 workgroups per CU.
 // Not in the reference (no weight-gradient code there: torch autograd, /root/reference/train.py:49).
 #include "../common.h"
+#include "../launchers.h"
 
 using namespace pdt;
 

@@ -11,6 +11,7 @@
 // -inf logits (masked vocabulary columns) are allowed off the target column when smoothing == 0:
 // they carry zero probability and zero gradient, as in F.cross_entropy.
 #include "../common.h"
+#include "../launchers.h"
 
 using namespace pdt;
 

@@ -7,6 +7,7 @@
 // iteration, consecutive lanes along the contiguous channel run, a grid-stride loop over
 // (output pixel, 8-channel chunk). Not in the reference (LeNet has no strided shortcut).
 #include "../common.h"
+#include "../launchers.h"
 
 namespace {
 

@@ -11,6 +11,7 @@
 // taps * C at src + src_tap(t) * C, written as [C][R] with row stride taps * R at dst + t * R. One
 // workgroup moves one 64 x 64 tile through LDS (coalesced 128-B reads and writes); grid.y = item.
 #include "../common.h"
+#include "../launchers.h"
 
 namespace {
 
