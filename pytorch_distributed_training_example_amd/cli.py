@@ -96,7 +96,18 @@ MODEL_DEFAULTS = {
     # computed from the logits by one fused kernel (--loss cross_entropy for the usual loss)
     "lenet": dict(optimizer="adadelta", loss="nll_on_probs"),
     "mlp": dict(optimizer="sgd", loss="mse"),
+    # the Llama-style decoders: what gpt2_* get (the fall-back below), spelled out. --lr defaults to 0.1, an SGD
+    # rate; pass --optimizer adamw with its own --lr for the usual recipe
+    **{name: dict(optimizer="sgd", loss="cross_entropy") for name in ("llama_tiny", "llama_small", "llama_medium")},
 }
+
+FP8_LLAMA_MSG = ("--precision fp8: the Llama-style models have no fp8 path (RMSNorm and SwiGLU have no fp8-emitting "
+                 "forms, so the GEMMs would silently run in bf16); use --precision bf16")
+
+
+def is_token_model(model_name: str) -> bool:
+    """Models fed token ids [batch, seq_len] by the synthetic loader (the others take images)."""
+    return model_name.startswith(("gpt", "llama"))
 
 
 def _datasets(args, rank, world):
@@ -222,8 +233,10 @@ def run(rank: int, world: int, args) -> dict:
     else:
         from .data import SyntheticBatches
         steps = args.steps_per_epoch or 10
-        if args.model.startswith("gpt"):
-            vocab = min(50257, model.cfg.vocab_size)  # gpt2_tiny's vocabulary is smaller than GPT-2's
+        if is_token_model(args.model):
+            vocab = model.cfg.vocab_size
+            if args.model.startswith("gpt"):
+                vocab = min(50257, vocab)  # gpt2_tiny's vocabulary is smaller than GPT-2's; 50304 is padding
             train_loader = SyntheticBatches((per_rank, args.seq_len), vocab, steps, device, seed=args.seed + rank,
                                             int_inputs=True)
         else:
@@ -334,6 +347,8 @@ def main(argv: Optional[list] = None) -> int:
         raise SystemExit(f"--dropout must be in [0, 1), got {args.dropout}")
     if args.dropout > 0 and not has_dropout_sites(args.model):
         raise SystemExit(dropout_unsupported_msg(args.model))
+    if args.precision == "fp8" and args.model.startswith("llama"):
+        raise SystemExit(FP8_LLAMA_MSG)
     if args.hipgraph:
         # MIOpen reads its solver switches once per process: set before any convolution
         from .engine.graph import make_miopen_capture_safe

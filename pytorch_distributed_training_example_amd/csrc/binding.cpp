@@ -1668,6 +1668,127 @@ std::vector<Tensor> ln_bwd(Tensor dy, Tensor x, Tensor w, Tensor mean, Tensor rs
   return {dx, dw, db};
 }
 
+// ----------------------------------------------------------------------------- rmsnorm / rope / swiglu
+bool aligned16(const Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; }
+
+// A result: the caller's own tensor (`out`: checked against the shape / dtype / device the kernel writes), or a
+// new one.
+Tensor out_or_new(const Op& op, const char* name, const c10::optional<Tensor>& out, at::IntArrayRef shape,
+                  const at::TensorOptions& opt) {
+  if (!has(out)) return at::empty(shape, opt);
+  TORCH_CHECK(out->is_contiguous() && out->sizes() == shape && out->scalar_type() == opt.dtype().toScalarType() &&
+                  out->device() == op.dev && aligned16(*out),
+              op.name, ": ", name, " must be a contiguous, 16-byte aligned ", opt.dtype(), " tensor of shape ", shape,
+              " on ", op.dev);
+  return *out;
+}
+
+// res: optional residual branch; then the sum s = x + res is returned as a 3rd output and normalised.
+// {y, rstd, s}; y_out / rstd_out / sum_out: write into these instead of new tensors.
+std::vector<Tensor> rms_fwd(Tensor x, Tensor w, double eps, c10::optional<Tensor> res, c10::optional<Tensor> y_out,
+                            c10::optional<Tensor> rstd_out, c10::optional<Tensor> sum_out) {
+  const Op op("rms_fwd", x);
+  TORCH_CHECK(x.is_contiguous() && x.dim() >= 1 && aligned16(x), "rms_fwd: x must be contiguous and 16-byte aligned");
+  const int64_t D = x.size(-1), N = D > 0 ? x.numel() / D : 0;
+  const bool hr = has(res);
+  if (hr)
+    TORCH_CHECK(res->is_contiguous() && res->sizes() == x.sizes() && res->scalar_type() == x.scalar_type() &&
+                    res->device() == op.dev && aligned16(*res),
+                "rms_fwd: residual must match x (contiguous, same shape/dtype/device)");
+  const int dt = dcode(x);
+  const float* wp = f32_ptr(op, "w", w, D);
+  TORCH_CHECK(hr || !has(sum_out), "rms_fwd: sum_out without a residual");
+  auto y = out_or_new(op, "y_out", y_out, x.sizes(), x.options());
+  Tensor sum;
+  if (hr) sum = out_or_new(op, "sum_out", sum_out, x.sizes(), x.options());
+  auto rstd = out_or_new(op, "rstd_out", rstd_out, {N}, x.options().dtype(at::kFloat));
+  int rc = pdt_rms_fwd(x.data_ptr(), hr ? res->data_ptr() : nullptr, dt, wp, y.data_ptr(),
+                       hr ? sum.data_ptr() : nullptr, rstd.data_ptr<float>(), N, (int)D, (float)eps, stream());
+  TORCH_CHECK(rc == 0, "pdt_rms_fwd: unsupported D=", D);
+  return {y, rstd, sum};
+}
+
+// dres: optional gradient added into dx (the residual stream's own gradient). {dx, dw}
+std::vector<Tensor> rms_bwd(Tensor dy, Tensor x, Tensor w, Tensor rstd, c10::optional<Tensor> dres,
+                            c10::optional<Tensor> dx_out, c10::optional<Tensor> dw_out) {
+  const Op op("rms_bwd", x);
+  TORCH_CHECK(x.is_contiguous() && x.dim() >= 1 && aligned16(x), "rms_bwd: x must be contiguous and 16-byte aligned");
+  const auto like_x = [&](const Tensor& t) {
+    return t.is_contiguous() && t.sizes() == x.sizes() && t.scalar_type() == x.scalar_type() && t.device() == op.dev &&
+           aligned16(t);
+  };
+  TORCH_CHECK(like_x(dy), "rms_bwd: dy must match x (contiguous, same shape/dtype/device)");
+  const int64_t D = x.size(-1), N = D > 0 ? x.numel() / D : 0;
+  const bool hr = has(dres);
+  if (hr) TORCH_CHECK(like_x(*dres), "rms_bwd: dres must match x (contiguous, same shape/dtype/device)");
+  const int dt = dcode(x);
+  const float* wp = f32_ptr(op, "w", w, D);
+  const float* rp = f32_ptr(op, "rstd", rstd, N);
+  TORCH_CHECK(D > 0 && D % 256 == 0 && D <= 2048, "pdt_rms_bwd: unsupported D=", D);
+  auto fopt = x.options().dtype(at::kFloat);
+  auto dx = out_or_new(op, "dx_out", dx_out, x.sizes(), x.options());
+  auto dw = out_or_new(op, "dw_out", dw_out, {D}, fopt);
+  auto ws = at::empty({std::max<int64_t>(pdt_rms_workspace_floats(N, (int)D), 1)}, fopt);
+  int rc = pdt_rms_bwd(dy.data_ptr(), x.data_ptr(), hr ? dres->data_ptr() : nullptr, dt, wp, rp, dx.data_ptr(),
+                       dw.data_ptr<float>(), N, (int)D, ws.data_ptr<float>(), stream());
+  TORCH_CHECK(rc == 0, "pdt_rms_bwd: unsupported D=", D);
+  return {dx, dw};
+}
+
+// Rotary embedding in place on the Q and K thirds of qkv [B, T, 3 * heads * 64] bf16 (rope.hip); cos, sin
+// fp32 [T_max, 32]. conj: rotate by -theta (the inverse, and the backward).
+void rope_qkv(Tensor qkv, Tensor cos, Tensor sin, int64_t heads, bool conj) {
+  const Op op("rope_qkv", qkv);
+  TORCH_CHECK(qkv.scalar_type() == at::kBFloat16, "rope_qkv: qkv must be bf16, got ", qkv.scalar_type());
+  TORCH_CHECK(qkv.dim() == 3 && qkv.stride(-1) == 1 && qkv.is_contiguous() && aligned16(qkv),
+              "rope_qkv: qkv must be a contiguous [B, T, 3 * heads * 64] tensor (unit stride on the last dim)");
+  const int64_t B = qkv.size(0), T = qkv.size(1);
+  TORCH_CHECK(heads > 0 && qkv.size(2) == 3 * heads * 64, "rope_qkv: head dim must be 64: last dim ", qkv.size(2),
+              " is not 3 * heads * 64 with heads = ", heads);
+  TORCH_CHECK(cos.dim() == 2 && cos.size(1) == 32 && sin.sizes() == cos.sizes(),
+              "rope_qkv: cos and sin must be [T_max, 32] tables");
+  const int64_t Tmax = cos.size(0);
+  TORCH_CHECK(T <= Tmax, "rope_qkv: sequence length T = ", T, " exceeds the table's T_max = ", Tmax);
+  const float* cp = f32_ptr(op, "cos", cos, Tmax * 32);
+  const float* sp = f32_ptr(op, "sin", sin, Tmax * 32);
+  TORCH_CHECK(aligned16(cos) && aligned16(sin), "rope_qkv: cos / sin must be 16-byte aligned");
+  int rc = pdt_rope_qkv(bf16_out(qkv), cp, sp, (int)B, (int)T, (int)heads, conj ? 1 : 0, stream());
+  TORCH_CHECK(rc == 0, "pdt_rope_qkv failed: ", rc);
+}
+
+// y = silu(gu[:, :F]) * gu[:, F:] for gu [..., 2F] (swiglu.hip)
+Tensor swiglu_fwd(Tensor gu, c10::optional<Tensor> y_out) {
+  const Op op("swiglu_fwd", gu);
+  TORCH_CHECK(gu.is_contiguous() && gu.dim() >= 1 && aligned16(gu),
+              "swiglu_fwd: gu must be contiguous and 16-byte aligned");
+  const int64_t F2 = gu.size(-1), F = F2 / 2;
+  TORCH_CHECK(F2 % 16 == 0 && F2 > 0, "swiglu_fwd: last dim 2F with F % 8 == 0, got ", F2);
+  const int64_t N = gu.numel() / F2;
+  auto shape = gu.sizes().vec();
+  shape.back() = F;
+  auto y = out_or_new(op, "y_out", y_out, shape, gu.options());
+  int rc = pdt_swiglu_fwd(gu.data_ptr(), dcode(gu), y.data_ptr(), N, (int)F, stream());
+  TORCH_CHECK(rc == 0, "pdt_swiglu_fwd failed: ", rc);
+  return y;
+}
+
+// dgu = [dg | du] from dy [..., F] and the saved gu [..., 2F]
+Tensor swiglu_bwd(Tensor dy, Tensor gu, c10::optional<Tensor> dgu_out) {
+  const Op op("swiglu_bwd", gu);
+  TORCH_CHECK(gu.is_contiguous() && gu.dim() >= 1 && aligned16(gu),
+              "swiglu_bwd: gu must be contiguous and 16-byte aligned");
+  const int64_t F2 = gu.size(-1), F = F2 / 2;
+  TORCH_CHECK(F2 % 16 == 0 && F2 > 0, "swiglu_bwd: last dim 2F with F % 8 == 0, got ", F2);
+  const int64_t N = gu.numel() / F2;
+  TORCH_CHECK(dy.is_contiguous() && dy.scalar_type() == gu.scalar_type() && dy.device() == op.dev &&
+                  dy.dim() == gu.dim() && dy.size(-1) == F && dy.numel() == N * F && aligned16(dy),
+              "swiglu_bwd: dy must be contiguous [..., F] of gu's dtype on gu's device");
+  auto dgu = out_or_new(op, "dgu_out", dgu_out, gu.sizes(), gu.options());
+  int rc = pdt_swiglu_bwd(dy.data_ptr(), gu.data_ptr(), dcode(gu), dgu.data_ptr(), N, (int)F, stream());
+  TORCH_CHECK(rc == 0, "pdt_swiglu_bwd failed: ", rc);
+  return dgu;
+}
+
 // ----------------------------------------------------------------------------- dropout (philox.h)
 const int64_t* ticket_ptr(const Tensor& ticket, const Tensor& like) {
   TORCH_CHECK(ticket.is_cuda() && ticket.scalar_type() == at::kLong && ticket.numel() == 2 && ticket.is_contiguous() &&
@@ -2464,6 +2585,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ln_fwd_drop", &ln_fwd_drop);
   m.def("ln_bwd_drop", &ln_bwd_drop);
   m.def("colsum", &colsum);
+  m.def("rms_fwd", &rms_fwd, py::arg("x"), py::arg("w"), py::arg("eps"), py::arg("res") = py::none(),
+        py::arg("y_out") = py::none(), py::arg("rstd_out") = py::none(), py::arg("sum_out") = py::none());
+  m.def("rms_bwd", &rms_bwd, py::arg("dy"), py::arg("x"), py::arg("w"), py::arg("rstd"),
+        py::arg("dres") = py::none(), py::arg("dx_out") = py::none(), py::arg("dw_out") = py::none());
+  m.def("rope_qkv", &rope_qkv, py::arg("qkv"), py::arg("cos"), py::arg("sin"), py::arg("heads"),
+        py::arg("conj") = false);
+  m.def("swiglu_fwd", &swiglu_fwd, py::arg("gu"), py::arg("y_out") = py::none());
+  m.def("swiglu_bwd", &swiglu_bwd, py::arg("dy"), py::arg("gu"), py::arg("dgu_out") = py::none());
   py::class_<P2PComm>(m, "P2PComm")
       .def(py::init<int, int, int64_t, int, int>(), py::arg("rank"), py::arg("world"), py::arg("capacity_bytes"),
            py::arg("max_blocks"), py::arg("device"))

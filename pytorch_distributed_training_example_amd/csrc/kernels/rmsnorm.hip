@@ -1,0 +1,238 @@
+// RMSNorm forward/backward for gfx950 (Llama-style decoders: D = 768, 1024, 2048).
+//
+// The design of layernorm.hip without the mean and the bias. One wave64 per row: the row stays in
+// registers (D/64 values per lane, 8-byte bf16 vectors), so the forward is one HBM read and one write:
+//   rstd = 1 / sqrt(mean_j(x_j^2) + eps),   y = round_T(x * rstd * w),   rstd kept (fp32) for the backward.
+// The backward computes, with xh = x * rstd,
+//   dx = rstd * (g w - xh * mean_j(g w xh))   (+ ds)
+// per row in registers and per-workgroup partial dw slabs, summed by a fixed-order second pass
+// (deterministic, no atomics).
+//
+// Residual fusion (pre-norm blocks), as ln_fwd_kernel does it: the forward optionally adds a residual
+// branch first, s = round_T(x + h) (exactly what a separate add would store), writes s (the new residual
+// stream) and normalises it; the backward optionally adds the residual stream's own gradient ds.
+#include "../common.h"
+#include "../launchers.h"
+
+using namespace pdt;
+
+namespace {
+
+constexpr int kRowsPerBlock = 4;  // 4 waves, one row each
+
+template <typename T> __device__ __forceinline__ float round_to(float v) { return v; }
+template <> __device__ __forceinline__ float round_to<uint16_t>(float v) { return bf2f(f2bf(v)); }
+
+// K = D / 256: 4-element groups per lane (D = 256*K)
+template <typename T, int K>
+__global__ __launch_bounds__(256) void rms_fwd_kernel(const T* __restrict__ x, const T* __restrict__ res,
+                                                      const float* __restrict__ w, T* __restrict__ y,
+                                                      T* __restrict__ sum_out, float* __restrict__ rstd_out,
+                                                      int64_t N, float eps) {
+  constexpr int D = 256 * K;
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
+  if (row >= N) return;
+  const T* xr = x + row * D;
+  float v[K][4];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    Vec4<T>::ld(xr, (int64_t)(k * 256 + lane * 4), v[k]);
+    if (res != nullptr) {  // s = x + h, stored and normalised at storage precision
+      float hv[4];
+      Vec4<T>::ld(res + row * D, (int64_t)(k * 256 + lane * 4), hv);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[k][j] = round_to<T>(v[k][j] + hv[j]);
+      Vec4<T>::st(sum_out + row * D, (int64_t)(k * 256 + lane * 4), v[k]);
+    }
+  }
+  float q = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) q += v[k][j] * v[k][j];
+  const float rstd = rsqrtf(wave_sum(q) * (1.f / D) + eps);
+  T* yr = y + row * D;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const int c = k * 256 + lane * 4;
+    float wv[4], o[4];
+    Vec4<float>::ld(w, c, wv);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = v[k][j] * rstd * wv[j];
+    Vec4<T>::st(yr, (int64_t)c, o);
+  }
+  if (lane == 0) rstd_out[row] = rstd;
+}
+
+// Backward: dx per row; per-workgroup partial dw written to part[blk][D]. A workgroup owns the rows
+// [blk * rows_per_block, (blk + 1) * rows_per_block), its 4 waves take them interleaved.
+template <typename T, int K>
+__global__ __launch_bounds__(256) void rms_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
+                                                      const T* __restrict__ dres, const float* __restrict__ w,
+                                                      const float* __restrict__ rstd, T* __restrict__ dx,
+                                                      float* __restrict__ part, int64_t N, int rows_per_block) {
+  constexpr int D = 256 * K;
+  __shared__ float sdw[4][D];
+  const int lane = threadIdx.x & 63, wv_id = threadIdx.x >> 6;
+  float dw[K][4], wr[K][4];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    Vec4<float>::ld(w, k * 256 + lane * 4, wr[k]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) dw[k][j] = 0.f;
+  }
+  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+  const int64_t r1 = min(N, r0 + rows_per_block);
+  // RF rows per wave in flight (rows r, r + 4, ...): all their loads are issued before any row's math,
+  // so a wave exposes the memory latency once per RF rows (as ln_bwd_kernel)
+  constexpr int RF = K <= 4 ? 4 : 2;
+  for (int64_t row0 = r0 + wv_id; row0 < r1; row0 += 4 * RF) {
+    float g[RF][K][4], xh[RF][K][4], rr[RF][K][4];
+    float rs[RF];
+    bool ok[RF];
+#pragma unroll
+    for (int q = 0; q < RF; ++q) {
+      const int64_t row = row0 + 4 * q;
+      ok[q] = row < r1;
+      const int64_t rw = ok[q] ? row : row0;  // duplicate load for a missing row, result unused
+      rs[q] = rstd[rw];
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const int64_t c = rw * D + k * 256 + lane * 4;
+        Vec4<T>::ld(dy, c, g[q][k]);
+        Vec4<T>::ld(x, c, xh[q][k]);
+        if (dres != nullptr) Vec4<T>::ld(dres, c, rr[q][k]);
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < RF; ++q) {
+      if (!ok[q]) continue;
+      const int64_t row = row0 + 4 * q;
+      float s2 = 0.f;
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          xh[q][k][j] *= rs[q];
+          dw[k][j] += g[q][k][j] * xh[q][k][j];
+          g[q][k][j] *= wr[k][j];  // g w from here on
+          s2 += g[q][k][j] * xh[q][k][j];
+        }
+      s2 = wave_sum(s2) * (1.f / D);
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        float o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          o[j] = rs[q] * (g[q][k][j] - xh[q][k][j] * s2);
+          if (dres != nullptr) o[j] += rr[q][k][j];  // + the residual stream's own gradient
+        }
+        Vec4<T>::st(dx, row * D + k * 256 + lane * 4, o);
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sdw[wv_id][k * 256 + lane * 4 + j] = dw[k][j];
+  __syncthreads();
+  for (int c = threadIdx.x; c < D; c += 256)
+    part[(int64_t)blockIdx.x * D + c] = sdw[0][c] + sdw[1][c] + sdw[2][c] + sdw[3][c];
+}
+
+// Fixed-order column sums of the per-workgroup partials: 16 columns x 16 slab groups per workgroup,
+// so each thread sums only nblk/16 independent values (latency-bound otherwise).
+__global__ __launch_bounds__(256) void rms_bwd_finalize_kernel(const float* __restrict__ part, int nblk, int D,
+                                                               float* __restrict__ dw) {
+  __shared__ float red[16][17];
+  const int grp = threadIdx.x >> 4, cl = threadIdx.x & 15;
+  const int c = blockIdx.x * 16 + cl;
+  float a = 0.f;
+  if (c < D)
+    for (int blk = grp; blk < nblk; blk += 16) a += part[(int64_t)blk * D + c];
+  red[grp][cl] = a;
+  __syncthreads();
+  if (grp == 0 && c < D) {
+    float sa = 0.f;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) sa += red[q][cl];
+    dw[c] = sa;
+  }
+}
+
+// The backward's partition: at least kBwdMinRows rows per workgroup (8 per wave), at most kBwdMaxBlocks
+// workgroups (2 per CU; the dw slab is nblk x D floats). Past kBwdMinRows * kBwdMaxBlocks rows a
+// workgroup owns more than kBwdMinRows.
+constexpr int64_t kBwdMinRows = 32, kBwdMaxBlocks = 512;
+
+inline int rms_bwd_blocks(int64_t N, int& rows_per_block) {
+  int64_t nblk = (N + kBwdMinRows - 1) / kBwdMinRows;
+  if (nblk > kBwdMaxBlocks) nblk = kBwdMaxBlocks;
+  if (nblk < 1) nblk = 1;
+  rows_per_block = (int)((N + nblk - 1) / nblk);
+  return (int)((N + rows_per_block - 1) / rows_per_block);
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t pdt_rms_workspace_floats(int64_t N, int D) {
+  int rpb;
+  return (int64_t)rms_bwd_blocks(N, rpb) * D;
+}
+
+#define PDT_RMS_SWITCH(MACRO) \
+  switch (D / 256) {          \
+    case 1: MACRO(1); break;  \
+    case 2: MACRO(2); break;  \
+    case 3: MACRO(3); break;  \
+    case 4: MACRO(4); break;  \
+    case 5: MACRO(5); break;  \
+    case 6: MACRO(6); break;  \
+    case 8: MACRO(8); break;  \
+    default: return -1;       \
+  }
+
+// res / sum_out: optional residual branch h and the stored sum s = x + h (both or neither).
+int pdt_rms_fwd(const void* x, const void* res, int dtype, const float* w, void* y, void* sum_out, float* rstd,
+                int64_t N, int D, float eps, hipStream_t s) {
+  if ((res == nullptr) != (sum_out == nullptr)) return -2;
+  if (D <= 0 || D % 256 != 0) return -1;
+  if (N == 0) return 0;
+  const dim3 grid((unsigned)((N + kRowsPerBlock - 1) / kRowsPerBlock));
+#define PDT_RMSF(K)                                                                                             \
+  if (dtype == 0)                                                                                               \
+    hipLaunchKernelGGL((rms_fwd_kernel<float, K>), grid, dim3(256), 0, s, (const float*)x, (const float*)res, w, \
+                       (float*)y, (float*)sum_out, rstd, N, eps);                                               \
+  else                                                                                                          \
+    hipLaunchKernelGGL((rms_fwd_kernel<uint16_t, K>), grid, dim3(256), 0, s, (const uint16_t*)x,                 \
+                       (const uint16_t*)res, w, (uint16_t*)y, (uint16_t*)sum_out, rstd, N, eps);
+  PDT_RMS_SWITCH(PDT_RMSF)
+#undef PDT_RMSF
+  return 0;
+}
+
+// dres: optional gradient added into dx (residual stream), same dtype/layout as dx. ws: pdt_rms_workspace_floats.
+int pdt_rms_bwd(const void* dy, const void* x, const void* dres, int dtype, const float* w, const float* rstd,
+                void* dx, float* dw, int64_t N, int D, float* ws, hipStream_t s) {
+  if (D <= 0 || D % 256 != 0) return -1;
+  int rpb;
+  const int nblk = N > 0 ? rms_bwd_blocks(N, rpb) : 0;
+#define PDT_RMSB(K)                                                                                              \
+  if (N > 0) {                                                                                                   \
+    if (dtype == 0)                                                                                              \
+      hipLaunchKernelGGL((rms_bwd_kernel<float, K>), dim3(nblk), dim3(256), 0, s, (const float*)dy,               \
+                         (const float*)x, (const float*)dres, w, rstd, (float*)dx, ws, N, rpb);                  \
+    else                                                                                                         \
+      hipLaunchKernelGGL((rms_bwd_kernel<uint16_t, K>), dim3(nblk), dim3(256), 0, s, (const uint16_t*)dy,         \
+                         (const uint16_t*)x, (const uint16_t*)dres, w, rstd, (uint16_t*)dx, ws, N, rpb);         \
+  }
+  PDT_RMS_SWITCH(PDT_RMSB)
+#undef PDT_RMSB
+  hipLaunchKernelGGL(rms_bwd_finalize_kernel, dim3((D + 15) / 16), dim3(256), 0, s, ws, nblk, D, dw);
+  return 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,135 @@
+// SwiGLU (gated SiLU) on the packed gate/up GEMM output, forward/backward for gfx950.
+//
+// gu: [N, 2F] (bf16 / fp32), gate g = gu[:, :F], up projection u = gu[:, F:] (one GEMM with the packed
+// [2F, D] weight). With sg = sigma(g) = 1 / (1 + e^-g):
+//   forward   y[n, f] = round_T(g sg u)                                   [N, F]
+//   backward  dg = dy u sg (1 + g (1 - sg)),   du = dy g sg               packed dgu [N, 2F], one pass
+// sg is recomputed from gu in the backward; nothing but gu is saved. fp32 math on value pairs (gelu_math.h:
+// packed multiplies / FMAs, one v_exp_f32 + one v_rcp_f32 per value). 1 - sg is formed as e^-g sg for
+// g > 0, where the subtraction would cancel. F % 8 == 0: a lane owns 8 columns of one row, 16-byte accesses.
+#include "../common.h"
+#include "../launchers.h"
+#include "../gelu_math.h"
+
+using namespace pdt;
+
+namespace {
+
+// 8 consecutive elements <-> 8 floats (16 B for bf16, 2 x 16 B for fp32).
+template <typename T> struct Vec8;
+template <> struct Vec8<uint16_t> {
+  __device__ __forceinline__ static void ld(const uint16_t* p, float (&v)[8]) { ld8_bf16(p, v); }
+  __device__ __forceinline__ static void st(uint16_t* p, const float (&v)[8]) { st8_bf16(p, v); }
+};
+template <> struct Vec8<float> {
+  __device__ __forceinline__ static void ld(const float* p, float (&v)[8]) {
+    const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+  }
+  __device__ __forceinline__ static void st(float* p, const float (&v)[8]) {
+    reinterpret_cast<float4*>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
+    reinterpret_cast<float4*>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
+  }
+};
+
+// e^-g and sigma(g) of a pair. e^-g = 2^(-g log2 e) overflows to inf below g ~ -88.7: sigma = 0, cleanly.
+// (Just above that, down from g ~ -87.3, sigma is subnormal and v_rcp_f32 may return 0 for it: |g sigma| < 1e-35.)
+__device__ __forceinline__ void sigmoid2(gf2 g, gf2& e, gf2& sg) {
+  e = exp2_2(g2(-1.4426950408889634f) * g);
+  sg = rcp2(g2(1.f) + e);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void swiglu_fwd_kernel(const T* __restrict__ gu, T* __restrict__ y, int64_t items,
+                                                         int F8) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= items) return;
+  const int64_t n = i / F8;
+  const int c = (int)(i - n * F8) * 8;
+  const int64_t F = (int64_t)F8 * 8;
+  float g[8], u[8], o[8];
+  Vec8<T>::ld(gu + n * 2 * F + c, g);
+  Vec8<T>::ld(gu + n * 2 * F + F + c, u);
+#pragma unroll
+  for (int j = 0; j < 8; j += 2) {
+    const gf2 gv{g[j], g[j + 1]};
+    gf2 e, sg;
+    sigmoid2(gv, e, sg);
+    const gf2 r = gv * sg * gf2{u[j], u[j + 1]};
+    o[j] = r.x;
+    o[j + 1] = r.y;
+  }
+  Vec8<T>::st(y + n * F + c, o);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void swiglu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ gu,
+                                                         T* __restrict__ dgu, int64_t items, int F8) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= items) return;
+  const int64_t n = i / F8;
+  const int c = (int)(i - n * F8) * 8;
+  const int64_t F = (int64_t)F8 * 8;
+  float d[8], g[8], u[8], og[8], ou[8];
+  Vec8<T>::ld(dy + n * F + c, d);
+  Vec8<T>::ld(gu + n * 2 * F + c, g);
+  Vec8<T>::ld(gu + n * 2 * F + F + c, u);
+#pragma unroll
+  for (int j = 0; j < 8; j += 2) {
+    const gf2 gv{g[j], g[j + 1]}, dv{d[j], d[j + 1]};
+    gf2 e, sg;
+    sigmoid2(gv, e, sg);
+    const gf2 a = e * sg, b = g2(1.f) - sg;  // 1 - sg two ways
+    const gf2 oms{gv.x > 0.f ? a.x : b.x, gv.y > 0.f ? a.y : b.y};
+    const gf2 rg = dv * gf2{u[j], u[j + 1]} * sg * fma2(gv, oms, g2(1.f));
+    const gf2 ru = dv * gv * sg;
+    og[j] = rg.x; og[j + 1] = rg.y;
+    ou[j] = ru.x; ou[j + 1] = ru.y;
+  }
+  Vec8<T>::st(dgu + n * 2 * F + c, og);
+  Vec8<T>::st(dgu + n * 2 * F + F + c, ou);
+}
+
+inline int swiglu_grid(int64_t N, int F, int64_t& items, dim3& grid) {
+  if (F <= 0 || F % 8 != 0 || N < 0) return -1;
+  items = N * (F / 8);
+  const int64_t nb = (items + 255) / 256;
+  if (nb > 0x7fffffffLL) return -1;
+  grid = dim3((unsigned)nb);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+// gu [N, 2F] -> y [N, F]; both contiguous and 16-byte aligned, F % 8 == 0.
+int pdt_swiglu_fwd(const void* gu, int dtype, void* y, int64_t N, int F, hipStream_t s) {
+  int64_t items;
+  dim3 grid;
+  if (swiglu_grid(N, F, items, grid) != 0) return -1;
+  if (items == 0) return 0;
+  if (dtype == 0)
+    hipLaunchKernelGGL(swiglu_fwd_kernel<float>, grid, dim3(256), 0, s, (const float*)gu, (float*)y, items, F / 8);
+  else
+    hipLaunchKernelGGL(swiglu_fwd_kernel<uint16_t>, grid, dim3(256), 0, s, (const uint16_t*)gu, (uint16_t*)y, items,
+                       F / 8);
+  return 0;
+}
+
+// dy [N, F], gu [N, 2F] -> dgu [N, 2F] = [dg | du].
+int pdt_swiglu_bwd(const void* dy, const void* gu, int dtype, void* dgu, int64_t N, int F, hipStream_t s) {
+  int64_t items;
+  dim3 grid;
+  if (swiglu_grid(N, F, items, grid) != 0) return -1;
+  if (items == 0) return 0;
+  if (dtype == 0)
+    hipLaunchKernelGGL(swiglu_bwd_kernel<float>, grid, dim3(256), 0, s, (const float*)dy, (const float*)gu,
+                       (float*)dgu, items, F / 8);
+  else
+    hipLaunchKernelGGL(swiglu_bwd_kernel<uint16_t>, grid, dim3(256), 0, s, (const uint16_t*)dy, (const uint16_t*)gu,
+                       (uint16_t*)dgu, items, F / 8);
+  return 0;
+}
+
+}  // extern "C"

@@ -313,6 +313,16 @@ int pdt_p2p_allreduce(const void* in, void* out, int64_t n, int dtype, char* con
                       uint32_t* const* flag_ptrs, int rank, int world, int64_t cap, float post_scale, uint32_t* st,
                       int algo, int max_blocks, double timeout_s, hipStream_t s);
 
+// kernels/rmsnorm.hip
+int64_t pdt_rms_workspace_floats(int64_t N, int D);
+int pdt_rms_fwd(const void* x, const void* res, int dtype, const float* w, void* y, void* sum_out, float* rstd,
+                int64_t N, int D, float eps, hipStream_t s);
+int pdt_rms_bwd(const void* dy, const void* x, const void* dres, int dtype, const float* w, const float* rstd,
+                void* dx, float* dw, int64_t N, int D, float* ws, hipStream_t s);
+
+// kernels/rope.hip
+int pdt_rope_qkv(uint16_t* qkv, const float* cos, const float* sin, int B, int T, int H, int conj, hipStream_t s);
+
 // kernels/slice_sum.hip
 int pdt_slice_sum_bf16(const uint16_t* x, uint16_t* out, int S, int64_t n, hipStream_t s);
 
@@ -326,6 +336,10 @@ int pdt_ce_bwd(const void* logits, int dtype, const int64_t* target, const float
 // kernels/subsample.hip
 int pdt_subsample_gather(const uint16_t* x, uint16_t* xs, int N, int H, int W, int C, int s, hipStream_t st);
 int pdt_subsample_scatter_add(const uint16_t* t, uint16_t* full, int N, int H, int W, int C, int s, hipStream_t st);
+
+// kernels/swiglu.hip
+int pdt_swiglu_fwd(const void* gu, int dtype, void* y, int64_t N, int F, hipStream_t s);
+int pdt_swiglu_bwd(const void* dy, const void* gu, int dtype, void* dgu, int64_t N, int F, hipStream_t s);
 
 // kernels/weight_prep.hip
 int pdt_weight_prep_max_items();

@@ -1,4 +1,4 @@
-"""Model zoo: LeNet (reference model), MLP (plumbing), ResNet, ViT, GPT-2."""
+"""Model zoo: LeNet (reference model), MLP (plumbing), ResNet, ViT, GPT-2, Llama-style decoder."""
 from __future__ import annotations
 
 from typing import Callable, Dict
@@ -30,7 +30,7 @@ def get_model(name: str, **kw) -> nn.Module:
 
 def _lazy():
     try:
-        from . import vit, gpt2  # noqa: F401  (register themselves)
+        from . import vit, gpt2, llama  # noqa: F401  (register themselves)
     except ImportError:
         pass
 

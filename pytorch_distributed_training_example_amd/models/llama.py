@@ -1,0 +1,179 @@
+"""Llama-style decoder: RMSNorm, rotary position embedding, SwiGLU MLP, no biases, untied LM head.
+
+The three pieces that differ from GPT-2 each run on a HIP kernel of their own (ops/rmsnorm.py,
+ops/rope.py, ops/swiglu.py); everything else is the GPT-2 hot path: flash attention reading Q/K/V in
+place from the packed QKV GEMM output at head dim 64, the bias-free GEMMs of ops/linear.py and the
+fused cross-entropy. As in ``run_blocks`` every residual add is inside the RMSNorm that follows it,
+one kernel per residual step each way.
+
+Multi-head attention only (no grouped-query attention), head dim 64, no dropout sites, no fp8 forms,
+sequence length at most ``block_size`` (the RoPE table). Parameter names follow the nanoGPT-style
+layout of models/gpt2.py: ``transformer.wte``, ``transformer.h.{i}.ln_1``, ``.attn.c_attn`` (packed
+q, k, v rows), ``.attn.c_proj``, ``.ln_2``, ``.mlp.c_fc`` (packed [gate; up] rows), ``.mlp.c_proj``,
+``transformer.ln_f``, ``lm_head``; ``from_hf_state_dict`` maps a Hugging Face Llama state dict onto it.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Dict
+
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+from ..config import SW
+from ..ops.attention import attention_qkv
+from ..ops.cross_entropy import cross_entropy
+from ..ops.linear import linear
+from ..ops.rmsnorm import RMSNorm, add_rms_norm
+from ..ops.rope import RotaryTable, rope_qkv_
+from ..ops.swiglu import swiglu
+from .transformer import init_weights
+
+HEAD_DIM = 64
+
+
+@dataclass
+class LlamaConfig:
+    n_layer: int = 24
+    n_head: int = 16
+    n_embd: int = 1024
+    ffn: int = 2816
+    block_size: int = 1024
+    vocab_size: int = 32000
+    rope_base: float = 10000.0
+    eps: float = 1e-5
+
+
+class LlamaAttention(nn.Module):
+    def __init__(self, dim: int, heads: int):
+        super().__init__()
+        assert dim == heads * HEAD_DIM, f"head dim must be {HEAD_DIM}: n_embd {dim}, n_head {heads}"
+        self.heads = heads
+        self.c_attn = nn.Linear(dim, 3 * dim, bias=False)
+        self.c_proj = nn.Linear(dim, dim, bias=False)
+
+    def forward(self, x: torch.Tensor, rope: RotaryTable) -> torch.Tensor:
+        qkv = linear(x, self.c_attn.weight)  # [B, T, 3D]; its backward needs x and W only, so
+        qkv = rope_qkv_(qkv, rope.cos, rope.sin, self.heads)  # Q and K are rotated in place
+        y = attention_qkv(qkv, self.heads, causal=True)
+        return linear(y, self.c_proj.weight)
+
+
+class LlamaMLP(nn.Module):
+    def __init__(self, dim: int, hidden: int):
+        super().__init__()
+        self.c_fc = nn.Linear(dim, 2 * hidden, bias=False)  # rows [0, F): gate, [F, 2F): up
+        self.c_proj = nn.Linear(hidden, dim, bias=False)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return linear(swiglu(linear(x, self.c_fc.weight)), self.c_proj.weight)
+
+
+class LlamaBlock(nn.Module):
+    """Pre-norm block: x + attn(ln_1(x)), then x + mlp(ln_2(x))."""
+
+    def __init__(self, cfg: LlamaConfig):
+        super().__init__()
+        self.ln_1 = RMSNorm(cfg.n_embd, eps=cfg.eps)
+        self.attn = LlamaAttention(cfg.n_embd, cfg.n_head)
+        self.ln_2 = RMSNorm(cfg.n_embd, eps=cfg.eps)
+        self.mlp = LlamaMLP(cfg.n_embd, cfg.ffn)
+
+    def forward(self, x: torch.Tensor, rope: RotaryTable) -> torch.Tensor:
+        """Unfused path (PDT_FUSED_ADDLN=0, or a block called on its own)."""
+        x = x + self.attn(self.ln_1(x), rope)
+        return x + self.mlp(self.ln_2(x))
+
+
+def run_llama_blocks(blocks, x: torch.Tensor, final_norm: RMSNorm, rope: RotaryTable) -> torch.Tensor:
+    """``final_norm(blocks(x))`` with every residual add fused into the RMSNorm that follows it (the
+    block's ln_2, the next block's ln_1, finally ``final_norm``), as ``transformer.run_blocks`` does
+    with LayerNorm: one add+RMSNorm kernel per residual step forward, one backward kernel that also
+    accumulates the residual stream's gradient."""
+    blocks = list(blocks)
+    if not blocks or not SW.fused_addln:
+        for blk in blocks:
+            x = blk(x, rope)
+        return final_norm(x)
+    y = blocks[0].ln_1(x)
+    for i, blk in enumerate(blocks):
+        x, y = add_rms_norm(x, blk.attn(y, rope), blk.ln_2)
+        x, y = add_rms_norm(x, blk.mlp(y), blocks[i + 1].ln_1 if i + 1 < len(blocks) else final_norm)
+    return y
+
+
+class Llama(nn.Module):
+    def __init__(self, cfg: LlamaConfig = LlamaConfig()):
+        super().__init__()
+        self.cfg = cfg
+        self.transformer = nn.ModuleDict(dict(
+            wte=nn.Embedding(cfg.vocab_size, cfg.n_embd),
+            h=nn.ModuleList([LlamaBlock(cfg) for _ in range(cfg.n_layer)]),
+            ln_f=RMSNorm(cfg.n_embd, eps=cfg.eps),
+        ))
+        self.lm_head = nn.Linear(cfg.n_embd, cfg.vocab_size, bias=False)  # untied
+        self.rope = RotaryTable(cfg.block_size, cfg.rope_base, HEAD_DIM)  # non-persistent fp32 buffers
+        init_weights(self, n_layer=cfg.n_layer)
+
+    def forward(self, idx: torch.Tensor, targets: torch.Tensor | None = None):
+        if idx.shape[1] > self.cfg.block_size:
+            raise ValueError(f"sequence length {idx.shape[1]} exceeds block_size {self.cfg.block_size} "
+                             "(the RoPE table)")
+        x = F.embedding(idx, self.transformer.wte.weight)
+        x = run_llama_blocks(self.transformer.h, x, self.transformer.ln_f, self.rope)
+        logits = linear(x, self.lm_head.weight)
+        if targets is None:
+            return logits
+        return cross_entropy(logits.reshape(-1, logits.shape[-1]), targets.reshape(-1))
+
+
+def from_hf_state_dict(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """A Hugging Face ``LlamaForCausalLM`` state dict (multi-head attention, head dim 64) in this
+    file's layout: q/k/v rows concatenated into ``c_attn``, gate/up rows into ``c_fc``.
+
+    No row permutation is needed: HF applies RoPE in the half-split ``rotate_half`` convention, pair
+    (j, j + 32) of each head, which is the convention of ops/rope.py. (The interleaved pairs
+    (2j, 2j + 1) of the original Meta checkpoints are permuted away when those are converted to HF.)"""
+    out: Dict[str, torch.Tensor] = {
+        "transformer.wte.weight": sd["model.embed_tokens.weight"],
+        "transformer.ln_f.weight": sd["model.norm.weight"],
+        "lm_head.weight": sd["lm_head.weight"] if "lm_head.weight" in sd else sd["model.embed_tokens.weight"],
+    }
+    i = 0
+    while f"model.layers.{i}.input_layernorm.weight" in sd:
+        src, dst = f"model.layers.{i}.", f"transformer.h.{i}."
+        q, k, v = (sd[f"{src}self_attn.{n}_proj.weight"] for n in ("q", "k", "v"))
+        if not (q.shape == k.shape == v.shape):
+            raise ValueError(f"layer {i}: grouped-query attention (k/v {tuple(k.shape)} against q "
+                             f"{tuple(q.shape)}) is not supported")
+        out[dst + "ln_1.weight"] = sd[src + "input_layernorm.weight"]
+        out[dst + "attn.c_attn.weight"] = torch.cat([q, k, v], 0)
+        out[dst + "attn.c_proj.weight"] = sd[src + "self_attn.o_proj.weight"]
+        out[dst + "ln_2.weight"] = sd[src + "post_attention_layernorm.weight"]
+        out[dst + "mlp.c_fc.weight"] = torch.cat([sd[src + "mlp.gate_proj.weight"], sd[src + "mlp.up_proj.weight"]], 0)
+        out[dst + "mlp.c_proj.weight"] = sd[src + "mlp.down_proj.weight"]
+        i += 1
+    return out
+
+
+def llama_medium(**kw) -> Llama:
+    """GPT-2-medium's depth and width (24 x 1024, 16 heads), F = 2816."""
+    return Llama(LlamaConfig(**kw))
+
+
+def llama_small(**kw) -> Llama:
+    return Llama(LlamaConfig(**{**dict(n_layer=12, n_head=12, n_embd=768, ffn=2048), **kw}))
+
+
+def llama_tiny(**kw) -> Llama:
+    """Small config for tests."""
+    return Llama(LlamaConfig(**{**dict(n_layer=2, n_head=4, n_embd=256, ffn=768, block_size=64, vocab_size=512),
+                                **kw}))
+
+
+from . import register  # noqa: E402
+
+register("llama_medium", llama_medium)
+register("llama_small", llama_small)
+register("llama_tiny", llama_tiny)

@@ -11,7 +11,12 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-NORM_TYPES = (nn.BatchNorm1d, nn.BatchNorm2d, nn.BatchNorm3d, nn.LayerNorm, nn.GroupNorm)
+from ..ops.rmsnorm import RMSNorm
+from ..ops.rope import RotaryTable
+
+# RMSNorm's weight stays fp32 like LayerNorm's; RotaryTable is no norm but is kept out of the cast for
+# the same reason: its cos / sin buffers are the fp32 table the RoPE kernel reads
+NORM_TYPES = (nn.BatchNorm1d, nn.BatchNorm2d, nn.BatchNorm3d, nn.LayerNorm, nn.GroupNorm, RMSNorm, RotaryTable)
 
 
 def to_bf16_mixed(model: nn.Module) -> nn.Module:

@@ -143,7 +143,9 @@ class _LinearFn(torch.autograd.Function):
         if _ours(x, w, "bias" if b is not None else "nobias", b):
             x2 = x.reshape(-1, x.shape[-1]).contiguous()
             y = native().gemm_nt(x2, w.contiguous(), b, 1 if b is not None else 0, False)[0]
-            return y.view(*x.shape[:-1], w.shape[0])
+            # (not .view: autograd refuses an in-place op, ops/rope.py, on a view made inside a Function;
+            # y is this call's own tensor, which is what _unsafe_view is for, as F.linear itself does)
+            return torch.ops.aten._unsafe_view(y, [*x.shape[:-1], w.shape[0]])
         return F.linear(x, w, b)
 
     @staticmethod

@@ -1,0 +1,101 @@
+"""Rotary position embedding on the packed QKV tensor (csrc/kernels/rope.hip).
+
+``rope_qkv_(qkv, cos, sin, heads)`` rotates the Q and K thirds of the ``c_attn`` output
+[B, T, 3·H·Dh] in place and returns it; V is not touched. Half-split convention (HF's
+``rotate_half``): for every head, position t and j < Dh/2
+
+    x'[j]        = x[j]·cos[t, j] − x[j + Dh/2]·sin[t, j]
+    x'[j + Dh/2] = x[j + Dh/2]·cos[t, j] + x[j]·sin[t, j]
+
+The rotation is orthogonal, so the backward is the same kernel with the sine negated, run in place
+on the packed gradient attention's backward returns: one read and one write of two thirds of the
+tensor each way, no copy of V, nothing saved but the table. bf16 GPU tensors at head dim 64 take the
+HIP kernel; anything else (CPU, fp32, ``PDT_DISABLE_NATIVE=1``) the same math in plain PyTorch.
+"""
+from __future__ import annotations
+
+import torch
+from torch import nn
+
+from ._native import native, use_native
+
+KERNEL_HEAD_DIM = 64
+
+
+def rope_table(T_max: int, base: float = 10000.0, dim: int = 64):
+    """``(cos, sin)``, fp32 [T_max, dim/2]: the angle of position t and pair j is t · base^(−2j/dim),
+    formed in float64 and rounded once."""
+    assert dim % 2 == 0
+    j = torch.arange(dim // 2, dtype=torch.float64)
+    inv_freq = torch.pow(torch.tensor(float(base), dtype=torch.float64), -2.0 * j / dim)
+    ang = torch.arange(T_max, dtype=torch.float64)[:, None] * inv_freq[None, :]
+    return torch.cos(ang).float(), torch.sin(ang).float()
+
+
+class RotaryTable(nn.Module):
+    """The table as non-persistent buffers ``cos`` / ``sin`` (not in the state_dict; rebuilt from
+    ``base``). A module of its own so that the precision policies can leave it in fp32
+    (models/precision.py), which is what the kernel reads."""
+
+    def __init__(self, T_max: int, base: float = 10000.0, dim: int = 64):
+        super().__init__()
+        cos, sin = rope_table(T_max, base, dim)
+        self.register_buffer("cos", cos, persistent=False)
+        self.register_buffer("sin", sin, persistent=False)
+
+
+def _native_ok(qkv, cos, sin, heads) -> bool:
+    return (use_native(qkv) and qkv.dtype == torch.bfloat16 and qkv.dim() == 3 and qkv.is_contiguous()
+            and qkv.shape[-1] == 3 * heads * KERNEL_HEAD_DIM and cos.dtype == torch.float32
+            and cos.shape[-1] == KERNEL_HEAD_DIM // 2 and qkv.data_ptr() % 16 == 0)
+
+
+def _rotate_reference_(qkv, cos, sin, heads, conj):
+    B, T, C3 = qkv.shape
+    dh = C3 // (3 * heads)
+    half = dh // 2
+    qk = qkv.view(B, T, 3, heads, dh)[:, :, :2]
+    lo, hi = qk[..., :half].float(), qk[..., half:].float()
+    c = cos[:T].float().view(1, T, 1, 1, half)
+    s = sin[:T].float().view(1, T, 1, 1, half)
+    if conj:
+        s = -s
+    new_lo, new_hi = lo * c - hi * s, hi * c + lo * s  # both before either write: lo / hi alias qkv in fp32
+    qk[..., :half] = new_lo.to(qkv.dtype)
+    qk[..., half:] = new_hi.to(qkv.dtype)
+    return qkv
+
+
+def _rotate_(qkv, cos, sin, heads, conj):
+    B, T, C3 = qkv.shape
+    if T > cos.shape[0]:
+        raise ValueError(f"rope: sequence length {T} exceeds the table's {cos.shape[0]} positions")
+    if _native_ok(qkv, cos, sin, heads):
+        native().rope_qkv(qkv, cos, sin, heads, conj)
+        return qkv
+    return _rotate_reference_(qkv, cos, sin, heads, conj)
+
+
+class _RopeQKVFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, cos, sin, heads):
+        ctx.mark_dirty(qkv)
+        ctx.save_for_backward(cos, sin)
+        ctx.heads = heads
+        return _rotate_(qkv, cos, sin, heads, False)
+
+    @staticmethod
+    def backward(ctx, dqkv):
+        cos, sin = ctx.saved_tensors
+        # in place on the gradient attention's backward just wrote (contiguous() is then a no-op)
+        return _rotate_(dqkv.contiguous(), cos, sin, ctx.heads, True), None, None, None
+
+
+def rope_qkv_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, heads: int) -> torch.Tensor:
+    """Rotate Q and K of the packed ``qkv`` [B, T, 3·heads·Dh] in place; returns ``qkv``."""
+    assert qkv.dim() == 3 and qkv.shape[-1] % (3 * heads) == 0, qkv.shape
+    if not qkv.is_contiguous():
+        raise ValueError("rope_qkv_: qkv must be contiguous (it is rotated in place)")
+    if torch.is_grad_enabled() and qkv.requires_grad:
+        return _RopeQKVFn.apply(qkv, cos, sin, heads)
+    return _rotate_(qkv, cos, sin, heads, False)

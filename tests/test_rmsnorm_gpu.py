@@ -1,0 +1,172 @@
+"""RMSNorm / add+RMSNorm (csrc/kernels/rmsnorm.hip) against the fp64 oracle, elementwise inside the
+envelopes of tests/llama_oracle.py: every supported width (so every RF = 4 and RF = 2 instantiation of the
+backward), row counts below / at / past one wave per row slot and around the backward's 32-row minimum per
+workgroup, and a row count past its 512-workgroup cap, where a workgroup owns several row groups. dw is held
+to the worst case of any fp32 summation order and run with *probe* gradients too: dy (and ds) zero except
+on the first and last row of each workgroup's range, so a row left out of a partition is an O(1) relative
+error. The stored s = x + h is compared bit for bit, dw must repeat bit for bit, and a guard band after
+every output must stay untouched."""
+import pytest
+import torch
+
+import llama_oracle as lo
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+WIDTHS = [256 * k for k in (1, 2, 3, 4, 5, 6, 8)]
+VARIANTS = ["plain", "add", "add_ds"]
+DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
+
+
+def _norm(w):
+    from pytorch_distributed_training_example_amd.ops.rmsnorm import RMSNorm
+    norm = RMSNorm(w.numel(), eps=lo.EPS).to(DEV)
+    with torch.no_grad():
+        norm.weight.copy_(w)
+    return norm
+
+
+def _run_and_compare(N, D, dtype, variant, regime, tag):
+    from pytorch_distributed_training_example_amd.ops.rmsnorm import add_rms_norm, rms_norm
+    x, dy, h, ds, w = [t.to(DEV) if t is not None else None
+                       for t in lo.rms_inputs(N, D, dtype, variant != "plain", regime)]
+    if variant == "add":
+        ds = None
+    norm = _norm(w)
+    xg = x.clone().requires_grad_()
+    got = {}
+    if variant == "plain":
+        y = rms_norm(xg, norm.weight, norm.eps)
+        assert type(y.grad_fn).__name__.startswith("_RMSFn"), y.grad_fn  # the HIP kernel, not the reference
+        y.backward(dy)
+    else:
+        hg = h.clone().requires_grad_()
+        s, y = add_rms_norm(xg, hg, norm)
+        assert type(y.grad_fn).__name__.startswith("_AddRMSFn"), y.grad_fn
+        torch.autograd.backward([s, y], [ds, dy]) if ds is not None else y.backward(dy)
+        got["s"], got["dh"] = s.detach(), hg.grad
+    got.update(y=y.detach(), dx=xg.grad, dw=norm.weight.grad)
+    ref, env = lo.rmsnorm_oracle(x, w, lo.EPS, dy, h, ds)
+    errors = []
+    if variant != "plain":
+        if not torch.equal(got["s"], ref["s"]):
+            errors.append(f"{tag}: s = x + h differs from the correctly rounded sum")
+        if not torch.equal(got["dh"], got["dx"]):
+            errors.append(f"{tag}: dh != dx")
+    for name, c in (("y", lo.RMS_C), ("dx", lo.RMS_C), ("dw", lo.RMS_C_SUM)):
+        try:
+            r = lo.assert_within(got[name], ref[name], env[name], c, lo.FLOOR, name=f"{tag} {name}")
+            print(f"ratio {tag} {name} {r:.4g}")
+        except AssertionError as e:
+            errors.append(str(e))
+            print(f"FAIL {e}")
+    assert not errors, "\n".join(errors)
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("dtype", list(DTYPES))
+@pytest.mark.parametrize("D", WIDTHS)
+def test_every_width(D, dtype, variant):
+    """N = 33 (two workgroups of 17 and 16 rows) and 129, dense and probe gradients."""
+    for N in (33, 129):
+        for regime in ("smooth", "probe"):
+            _run_and_compare(N, D, DTYPES[dtype], variant, regime, f"rms D={D} {dtype} {variant} N={N} {regime}")
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("dtype", list(DTYPES))
+@pytest.mark.parametrize("D", [768, 1024])
+def test_row_counts(D, dtype, variant):
+    """Fewer rows than waves, one full slot, one past it; 31 / 32 / 33: one below, at and one above the backward's
+    rows-per-workgroup minimum (33 is the first count with two workgroups)."""
+    assert lo.rms_partition(32) == (32, 1) and lo.rms_partition(33) == (17, 2)
+    for N in (1, 3, 4, 5, 31, 32, 33):
+        for regime in ("smooth", "probe"):
+            _run_and_compare(N, D, DTYPES[dtype], variant, regime, f"rms D={D} {dtype} {variant} N={N} {regime}")
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("dtype", list(DTYPES))
+@pytest.mark.parametrize("D", [768, 1024])
+def test_past_the_workgroup_cap(D, dtype, variant):
+    """N = 16385 > 512 x 32: the backward runs at its cap with 33 rows per workgroup, no multiple of the 4 x RF
+    rows a workgroup takes per step, and the last workgroup is short. Probe gradients."""
+    N = 16385
+    assert lo.rms_partition(N) == (33, 497) and len(lo.rms_probe_rows(N)) == 10
+    _run_and_compare(N, D, DTYPES[dtype], variant, "probe", f"rms-cap D={D} {dtype} {variant} N={N} probe")
+
+
+@pytest.mark.parametrize("D", WIDTHS)
+def test_large_mean_fp32(D):
+    """x = 50 + 0.1 randn: mean(x^2) is a sum of positive terms, so the bounds hold without a kappa term."""
+    _run_and_compare(33, D, torch.float32, "plain", "largemean", f"rms-largemean D={D} fp32 N=33")
+    _run_and_compare(33, D, torch.float32, "add_ds", "largemean", f"rms-largemean D={D} fp32 add_ds N=33")
+
+
+@pytest.mark.parametrize("dtype", list(DTYPES))
+@pytest.mark.parametrize("N,D", [(129, 768), (4099, 1024)])
+def test_dw_repeats_bit_for_bit(N, D, dtype):
+    from pytorch_distributed_training_example_amd.ops._native import native
+    x, dy, _, ds, w = [t.to(DEV) for t in lo.rms_inputs(N, D, DTYPES[dtype], True)]
+    y, rstd, _ = native().rms_fwd(x, w, lo.EPS)
+    first = native().rms_bwd(dy, x, w, rstd, ds)
+    for _ in range(2):
+        again = native().rms_bwd(dy, x, w, rstd, ds)
+        assert torch.equal(again[1], first[1]) and torch.equal(again[0], first[0])
+
+
+GUARD = 64
+
+
+def _guarded(shape, dtype, fill):
+    """(a contiguous tensor of ``shape`` at the front of a longer buffer, the GUARD elements behind it)."""
+    n = 1
+    for s in shape:
+        n *= s
+    buf = torch.full((n + GUARD,), fill, dtype=dtype, device=DEV)
+    return buf[:n].view(shape), buf[n:]
+
+
+@pytest.mark.parametrize("dtype", list(DTYPES))
+@pytest.mark.parametrize("N,D", [(1, 256), (5, 768), (33, 1024), (37, 2048)])
+def test_guard_bands_untouched(N, D, dtype):
+    """The outputs are the front of longer buffers: the 64 elements behind y, s, rstd, dx and dw keep
+    their fill, and the results equal those written into tensors of the op's own."""
+    from pytorch_distributed_training_example_amd.ops._native import native
+    dt = DTYPES[dtype]
+    x, dy, h, ds, w = [t.to(DEV) for t in lo.rms_inputs(N, D, dt, True)]
+    want_f = native().rms_fwd(x, w, lo.EPS, h)
+    want_b = native().rms_bwd(dy, want_f[2], w, want_f[1], ds)
+    (y, gy), (s, gs), (rstd, gr) = _guarded((N, D), dt, 7.0), _guarded((N, D), dt, 7.0), _guarded((N,), torch.float32, 7.0)
+    (dx, gdx), (dw, gdw) = _guarded((N, D), dt, 7.0), _guarded((D,), torch.float32, 7.0)
+    native().rms_fwd(x, w, lo.EPS, h, y, rstd, s)
+    native().rms_bwd(dy, s, w, rstd, ds, dx, dw)
+    torch.cuda.synchronize()
+    for name, g in (("y", gy), ("s", gs), ("rstd", gr), ("dx", gdx), ("dw", gdw)):
+        assert bool((g == 7.0).all()), f"guard band after {name} was written"
+    for a, b in ((y, want_f[0]), (rstd, want_f[1]), (s, want_f[2]), (dx, want_b[0]), (dw, want_b[1])):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("D", [320, 1792, 2304])
+def test_unsupported_width_falls_back(D):
+    """No multiple of 256, K = 7 and K = 9 have no kernel: the op takes the PyTorch form of the same math, and the
+    launcher itself refuses the width before any launch."""
+    from pytorch_distributed_training_example_amd.ops._native import native
+    from pytorch_distributed_training_example_amd.ops.rmsnorm import add_rms_norm, rms_norm
+    x, dy, h, ds, w = [t.to(DEV) for t in lo.rms_inputs(9, D, torch.float32, True)]
+    norm = _norm(w)
+    xg, hg = x.clone().requires_grad_(), h.clone().requires_grad_()
+    y = rms_norm(xg, norm.weight, norm.eps)
+    assert not type(y.grad_fn).__name__.startswith("_RMSFn")
+    s, y2 = add_rms_norm(xg, hg, norm)
+    torch.autograd.backward([y, s, y2], [dy, ds, dy])
+    ref, env = lo.rmsnorm_oracle(x, w, lo.EPS, dy)
+    torch.testing.assert_close(y.detach().double(), ref["y"], rtol=1e-5, atol=1e-5)
+    ref2, _ = lo.rmsnorm_oracle(x, w, lo.EPS, dy, h, ds)
+    assert torch.equal(s.detach(), ref2["s"])
+    torch.testing.assert_close(y2.detach().double(), ref2["y"], rtol=1e-5, atol=1e-5)
+    torch.testing.assert_close(xg.grad.double(), ref["dx"] + ref2["dx"], rtol=1e-4, atol=1e-5)
+    torch.testing.assert_close(norm.weight.grad.double(), ref["dw"] + ref2["dw"], rtol=1e-4, atol=1e-4)
+    with pytest.raises(RuntimeError, match="unsupported D"):
+        native().rms_fwd(x, w, lo.EPS)
