@@ -86,6 +86,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--dropout", type=float, default=0.0, metavar="P",
                    help="dropout probability for the models that have dropout sites (gpt2_*, vit_*): embedding, "
                         "attention and residual dropout from counter-generated masks, seeded from --seed and the rank")
+    p.add_argument("--kv-heads", type=int, default=None, metavar="N",
+                   help="llama_* only: N K/V heads shared by groups of query heads (grouped-query attention); N must "
+                        "divide the model's head count. Default: the model's own (multi-head for llama_medium / _small)")
     p.add_argument("--profile", default=None, metavar="DIR",
                    help="torch.profiler trace of a few steps of epoch 1 into DIR (rank 0), roctx ranges on")
     return p
@@ -98,11 +101,28 @@ MODEL_DEFAULTS = {
     "mlp": dict(optimizer="sgd", loss="mse"),
     # the Llama-style decoders: what gpt2_* get (the fall-back below), spelled out. --lr defaults to 0.1, an SGD
     # rate; pass --optimizer adamw with its own --lr for the usual recipe
-    **{name: dict(optimizer="sgd", loss="cross_entropy") for name in ("llama_tiny", "llama_small", "llama_medium")},
+    **{name: dict(optimizer="sgd", loss="cross_entropy") for name in ("llama_tiny", "llama_tiny_gqa", "llama_small", "llama_medium")},
 }
 
 FP8_LLAMA_MSG = ("--precision fp8: the Llama-style models have no fp8 path (RMSNorm and SwiGLU have no fp8-emitting "
                  "forms, so the GEMMs would silently run in bf16); use --precision bf16")
+
+
+def _llama_heads(model_name: str):
+    from .models.llama import n_heads
+    return n_heads(model_name)
+
+
+def kv_heads_msg(model_name: str, n: int) -> str:
+    heads = _llama_heads(model_name)
+    about = f"{heads} heads" if heads else "no grouped-query form"
+    return (f"--kv-heads {n}: takes a llama_* model and a positive N that divides its head count "
+            f"(model {model_name}: {about})")
+
+
+def kv_heads_ok(model_name: str, n: int) -> bool:
+    heads = _llama_heads(model_name)
+    return heads is not None and n > 0 and heads % n == 0
 
 
 def is_token_model(model_name: str) -> bool:
@@ -173,6 +193,8 @@ def run(rank: int, world: int, args) -> dict:
         model = get_model("lenet", output="logits")
     elif args.dropout > 0:
         model = get_model(args.model, dropout=args.dropout)
+    elif getattr(args, "kv_heads", None) is not None:
+        model = get_model(args.model, n_kv_head=args.kv_heads)
     else:
         model = get_model(args.model)
     # dropout masks: one seed for the job, the rank enters the Philox key (ops/dropout.py)
@@ -349,6 +371,8 @@ def main(argv: Optional[list] = None) -> int:
         raise SystemExit(dropout_unsupported_msg(args.model))
     if args.precision == "fp8" and args.model.startswith("llama"):
         raise SystemExit(FP8_LLAMA_MSG)
+    if args.kv_heads is not None and not kv_heads_ok(args.model, args.kv_heads):
+        raise SystemExit(kv_heads_msg(args.model, args.kv_heads))
     if args.hipgraph:
         # MIOpen reads its solver switches once per process: set before any convolution
         from .engine.graph import make_miopen_capture_safe

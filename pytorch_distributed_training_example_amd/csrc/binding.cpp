@@ -1756,6 +1756,29 @@ void rope_qkv(Tensor qkv, Tensor cos, Tensor sin, int64_t heads, bool conj) {
   TORCH_CHECK(rc == 0, "pdt_rope_qkv failed: ", rc);
 }
 
+// The grouped-query form: qkv [B, T, (heads + 2 * kv_heads) * 64], heads Q heads, then kv_heads K heads (both
+// rotated), then kv_heads V heads (untouched).
+void rope_qkv_gqa(Tensor qkv, Tensor cos, Tensor sin, int64_t heads, int64_t kv_heads, bool conj) {
+  const Op op("rope_qkv_gqa", qkv);
+  TORCH_CHECK(qkv.scalar_type() == at::kBFloat16, "rope_qkv_gqa: qkv must be bf16, got ", qkv.scalar_type());
+  TORCH_CHECK(qkv.dim() == 3 && qkv.stride(-1) == 1 && qkv.is_contiguous() && aligned16(qkv),
+              "rope_qkv_gqa: qkv must be a contiguous [B, T, (heads + 2 * kv_heads) * 64] tensor");
+  const int64_t B = qkv.size(0), T = qkv.size(1);
+  TORCH_CHECK(heads > 0 && kv_heads > 0 && heads % kv_heads == 0, "rope_qkv_gqa: heads = ", heads,
+              " is not a positive multiple of kv_heads = ", kv_heads);
+  TORCH_CHECK(qkv.size(2) == (heads + 2 * kv_heads) * 64, "rope_qkv_gqa: head dim must be 64: last dim ", qkv.size(2),
+              " is not (heads + 2 * kv_heads) * 64 with heads = ", heads, ", kv_heads = ", kv_heads);
+  TORCH_CHECK(cos.dim() == 2 && cos.size(1) == 32 && sin.sizes() == cos.sizes(),
+              "rope_qkv_gqa: cos and sin must be [T_max, 32] tables");
+  const int64_t Tmax = cos.size(0);
+  TORCH_CHECK(T <= Tmax, "rope_qkv_gqa: sequence length T = ", T, " exceeds the table's T_max = ", Tmax);
+  const float* cp = f32_ptr(op, "cos", cos, Tmax * 32);
+  const float* sp = f32_ptr(op, "sin", sin, Tmax * 32);
+  TORCH_CHECK(aligned16(cos) && aligned16(sin), "rope_qkv_gqa: cos / sin must be 16-byte aligned");
+  int rc = pdt_rope_qkv_gqa(bf16_out(qkv), cp, sp, (int)B, (int)T, (int)heads, (int)kv_heads, conj ? 1 : 0, stream());
+  TORCH_CHECK(rc == 0, "pdt_rope_qkv_gqa failed: ", rc);
+}
+
 // y = silu(gu[:, :F]) * gu[:, F:] for gu [..., 2F] (swiglu.hip)
 Tensor swiglu_fwd(Tensor gu, c10::optional<Tensor> y_out) {
   const Op op("swiglu_fwd", gu);
@@ -1952,6 +1975,50 @@ void attn_bwd_out(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor ls
                         os.v, lse.data_ptr<float>(), delta.data_ptr<float>(), bf16_out(dq), bf16_out(dk), bf16_out(dv),
                         gs.v, B, H, T, Dh, causal, (float)scale, stream());
   TORCH_CHECK(rc == 0, "pdt_attn_bwd: unsupported head dim ", Dh);
+}
+
+// Grouped-query attention (attention.hip GQA): q/o/dout/dq [B, H, T, Dh], k/v/dk/dv [B, Hkv, T, Dh] with
+// H % Hkv == 0; query head h reads K/V head h / (H / Hkv). Every check runs before any launch.
+struct GqaDims {
+  int B, H, Hkv, T, Dh;
+};
+GqaDims gqa_dims(const char* what, const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& lse) {
+  TORCH_CHECK(k.sizes() == v.sizes(), what, ": k and v must have equal sizes, got ", k.sizes(), " and ", v.sizes());
+  TORCH_CHECK(k.size(0) == q.size(0) && k.size(2) == q.size(2) && k.size(3) == q.size(3), what,
+              ": k/v must match q in B, T and Dh, got q ", q.sizes(), " and k ", k.sizes());
+  TORCH_CHECK(k.size(1) > 0 && q.size(1) % k.size(1) == 0, what, ": the ", q.size(1),
+              " query heads are not a multiple of the ", k.size(1), " K/V heads");
+  TORCH_CHECK(q.size(3) == 64, what, ": unsupported head dim ", q.size(3));
+  check_cuda(lse, "lse");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() && lse.dim() == 3 && lse.size(0) == q.size(0) &&
+              lse.size(1) == q.size(1) && lse.size(2) == q.size(2), what, ": lse must be fp32 [B,H,T]");
+  return {(int)q.size(0), (int)q.size(1), (int)k.size(1), (int)q.size(2), (int)q.size(3)};
+}
+
+void attn_fwd_gqa_out(Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal, double scale) {
+  auto qs = bht_strides(q, "q"), ks = bht_strides(k, "k"), vs = bht_strides(v, "v"), os = bht_strides(o, "o");
+  TORCH_CHECK(q.sizes() == o.sizes(), "attn gqa: o must have q's shape");
+  const GqaDims d = gqa_dims("attn gqa", q, k, v, lse);
+  int rc = pdt_attn_fwd_gqa(bf16_ptr(q), qs.v, bf16_ptr(k), ks.v, bf16_ptr(v), vs.v, bf16_out(o), os.v,
+                            lse.data_ptr<float>(), d.B, d.H, d.Hkv, d.T, d.Dh, causal, (float)scale, stream());
+  TORCH_CHECK(rc == 0, "pdt_attn_fwd_gqa failed: ", rc);
+}
+
+void attn_bwd_gqa_out(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor dq, Tensor dk, Tensor dv,
+                      bool causal, double scale) {
+  auto dos = bht_strides(dout, "dout"), qs = bht_strides(q, "q"), ks = bht_strides(k, "k"), vs = bht_strides(v, "v"),
+       os = bht_strides(o, "o"), gs = bht_strides(dq, "dq"), gk = bht_strides(dk, "dk"), gv = bht_strides(dv, "dv");
+  TORCH_CHECK(gs.v[0] == gk.v[0] && gs.v[1] == gk.v[1] && gs.v[2] == gk.v[2] && gs.v[0] == gv.v[0] &&
+              gs.v[1] == gv.v[1] && gs.v[2] == gv.v[2], "attn gqa bwd: dq/dk/dv must share strides");
+  TORCH_CHECK(q.sizes() == o.sizes() && q.sizes() == dout.sizes() && q.sizes() == dq.sizes() &&
+              k.sizes() == dk.sizes() && v.sizes() == dv.sizes(), "attn gqa bwd: shape mismatch");
+  const GqaDims d = gqa_dims("attn gqa bwd", q, k, v, lse);
+  auto delta = at::empty({(int64_t)d.B * d.H * d.T}, q.options().dtype(at::kFloat));
+  int rc = pdt_attn_bwd_gqa(bf16_ptr(dout), dos.v, bf16_ptr(q), qs.v, bf16_ptr(k), ks.v, bf16_ptr(v), vs.v,
+                            bf16_ptr(o), os.v, lse.data_ptr<float>(), delta.data_ptr<float>(), bf16_out(dq),
+                            bf16_out(dk), bf16_out(dv), gs.v, d.B, d.H, d.Hkv, d.T, d.Dh, causal, (float)scale,
+                            stream());
+  TORCH_CHECK(rc == 0, "pdt_attn_bwd_gqa failed: ", rc);
 }
 
 // Attention dropout: the same calls with the mask of P regenerated from the ticket (attention.hip DROP).
@@ -2579,6 +2646,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_bwd_out", &attn_bwd_out);
   m.def("attn_fwd_drop_out", &attn_fwd_drop_out);
   m.def("attn_bwd_drop_out", &attn_bwd_drop_out);
+  m.def("attn_fwd_gqa_out", &attn_fwd_gqa_out);
+  m.def("attn_bwd_gqa_out", &attn_bwd_gqa_out);
   m.def("dropout_begin", &dropout_begin);
   m.def("dropout_fwd", &dropout_fwd);
   m.def("dropout_mask", &dropout_mask);
@@ -2591,6 +2660,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dres") = py::none(), py::arg("dx_out") = py::none(), py::arg("dw_out") = py::none());
   m.def("rope_qkv", &rope_qkv, py::arg("qkv"), py::arg("cos"), py::arg("sin"), py::arg("heads"),
         py::arg("conj") = false);
+  m.def("rope_qkv_gqa", &rope_qkv_gqa, py::arg("qkv"), py::arg("cos"), py::arg("sin"), py::arg("heads"),
+        py::arg("kv_heads"), py::arg("conj") = false);
   m.def("swiglu_fwd", &swiglu_fwd, py::arg("gu"), py::arg("y_out") = py::none());
   m.def("swiglu_bwd", &swiglu_bwd, py::arg("dy"), py::arg("gu"), py::arg("dgu_out") = py::none());
   py::class_<P2PComm>(m, "P2PComm")

@@ -162,12 +162,15 @@ __device__ __forceinline__ void drop_tile_words(const DropSite& site, uint64_t b
 // grid (ceil(T/128), H, B), 256 threads; wave w owns queries [blk*128 + 32w, +32) as 2 x 16.
 // ~155 VGPRs: 3 waves per SIMD. Measured alternatives (tools/attn_bench.py, GPT-2 shape): forcing
 // 4 waves/SIMD spills (-14%); prefetching K/V two tiles ahead (+24 VGPR) is -7%.
-template <bool CAUSAL, bool DROP = false>
+// GQA instantiations: K and V have H / G heads and query head h stages the slice of head h / G (G a
+// kernel argument); nothing else differs. No DROP x GQA instantiation exists.
+template <bool CAUSAL, bool DROP = false, bool GQA = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(Tensor4 Q, Tensor4 K, Tensor4 V, uint16_t* __restrict__ O,
                                                        int64_t o_sb, int64_t o_sh, int64_t o_st,
                                                        float* __restrict__ LSE, int H, int T, float sl2,
                                                        const int64_t* __restrict__ ticket = nullptr, int dstream = 0,
-                                                       int thr = 0) {
+                                                       int thr = 0, int G = 1) {
+  static_assert(!(DROP && GQA), "no dropout on the grouped-query kernels");
   __shared__ __attribute__((aligned(16))) char lds[2 * 64 * ROW_BYTES];
   char* Ks = lds;
   char* Vs = lds + 64 * ROW_BYTES;
@@ -176,9 +179,10 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(Tensor4 Q, Tensor4 K, 
   const int b = blockIdx.z, h = blockIdx.y;
   const int qblk = blockIdx.x * 128;
   const int qbase = qblk + 32 * w;
+  const int hk = GQA ? h / G : h;  // the K/V head this query head reads
   const int64_t qoff = (int64_t)b * Q.sb + (int64_t)h * Q.sh;
-  const int64_t koff = (int64_t)b * K.sb + (int64_t)h * K.sh;
-  const int64_t voff = (int64_t)b * V.sb + (int64_t)h * V.sh;
+  const int64_t koff = (int64_t)b * K.sb + (int64_t)hk * K.sh;
+  const int64_t voff = (int64_t)b * V.sb + (int64_t)hk * V.sh;
   const __amdgpu_buffer_rsrc_t krs = slice_rsrc(K.p + koff, T, K.st), vrs = slice_rsrc(V.p + voff, T, V.st);
   DropSite site;
   if constexpr (DROP) site = drop_site(ticket, dstream, thr);
@@ -345,13 +349,15 @@ __global__ __launch_bounds__(256) void attn_bwd_pre_kernel(Tensor4 DO, Tensor4 O
 // ============================================================================ backward: dQ
 // Forward structure: S^T = K Q^T, dP^T = V dO^T (lane = query), dS^T = P^T (dP^T - delta),
 // dQ^T += K^T dS^T (K^T by transposed LDS reads).
-template <bool CAUSAL, bool DROP = false>
+// GQA instantiations: K/V of head h / G, as in the forward.
+template <bool CAUSAL, bool DROP = false, bool GQA = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(Tensor4 Q, Tensor4 K, Tensor4 V, Tensor4 DO,
                                                           const float* __restrict__ LSE, const float* __restrict__ DELTA,
                                                           uint16_t* __restrict__ DQ, int64_t dq_sb, int64_t dq_sh,
                                                           int64_t dq_st, int H, int T, float sl2, float scale,
                                                           const int64_t* __restrict__ ticket = nullptr, int dstream = 0,
-                                                          int thr = 0) {
+                                                          int thr = 0, int G = 1) {
+  static_assert(!(DROP && GQA), "no dropout on the grouped-query kernels");
   __shared__ __attribute__((aligned(16))) char lds[2 * 64 * ROW_BYTES];
   char* Ks = lds;
   char* Vs = lds + 64 * ROW_BYTES;
@@ -361,9 +367,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(Tensor4 Q, Tensor4 
   const int qblk = blockIdx.x * 128;
   const int qbase = qblk + 32 * w;
   const int64_t qoff = (int64_t)b * Q.sb + (int64_t)h * Q.sh;
+  const int hk = GQA ? h / G : h;
   const int64_t dooff = (int64_t)b * DO.sb + (int64_t)h * DO.sh;
-  const int64_t koff = (int64_t)b * K.sb + (int64_t)h * K.sh;
-  const int64_t voff = (int64_t)b * V.sb + (int64_t)h * V.sh;
+  const int64_t koff = (int64_t)b * K.sb + (int64_t)hk * K.sh;
+  const int64_t voff = (int64_t)b * V.sb + (int64_t)hk * V.sh;
   const int64_t rowoff = ((int64_t)b * H + h) * T;
   DropSite site;
   if constexpr (DROP) site = drop_site(ticket, dstream, thr);
@@ -483,31 +490,32 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(Tensor4 Q, Tensor4 
 // grid (ceil(T/128), H, B); wave w owns keys [blk*128 + 32w, +32) as 2 key subtiles of 16.
 // Per 64-query tile (Q, dO staged in LDS): S = Q K^T and dP = dO V^T with lane = key,
 // dV^T += dO^T P and dK^T += Q^T dS (dO^T, Q^T via transposed LDS reads).
-template <bool CAUSAL, bool DROP = false>
+// GQA instantiations: grid (ceil(T/128), H / G, B), blockIdx.y = K/V head j. The K/V fragments are loaded
+// once; the query-tile loop runs once per query head h = j G + gq of the group, in that order, into the
+// same fp32 dk/dv registers, and the epilogue rounds to bf16 once: the group sum needs no atomics and has
+// one fixed order.
+template <bool CAUSAL, bool DROP = false, bool GQA = false>
 __global__ __launch_bounds__(256, DKDV_MINW) void attn_bwd_dkdv_kernel(Tensor4 Q, Tensor4 K, Tensor4 V, Tensor4 DO,
                                                             const float* __restrict__ LSE,
                                                             const float* __restrict__ DELTA, uint16_t* __restrict__ DK,
                                                             uint16_t* __restrict__ DV, int64_t g_sb, int64_t g_sh,
                                                             int64_t g_st, int H, int T, float sl2, float scale,
                                                             const int64_t* __restrict__ ticket = nullptr,
-                                                            int dstream = 0, int thr = 0) {
+                                                            int dstream = 0, int thr = 0, int G = 1) {
+  static_assert(!(DROP && GQA), "no dropout on the grouped-query kernels");
   __shared__ __attribute__((aligned(16))) char lds[2 * 64 * ROW_BYTES];
   __shared__ float srow[2][64];  // lse2, delta of the staged query tile
   char* Qs = lds;
   char* Ds = lds + 64 * ROW_BYTES;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int c = lane & 15, g = lane >> 4;
-  const int b = blockIdx.z, h = blockIdx.y;
+  const int b = blockIdx.z, hk = blockIdx.y;  // hk: the K/V head (the query head too unless GQA)
   const int kblk = blockIdx.x * 128;
   const int kbase = kblk + 32 * w;
-  const int64_t qoff = (int64_t)b * Q.sb + (int64_t)h * Q.sh;
-  const int64_t dooff = (int64_t)b * DO.sb + (int64_t)h * DO.sh;
-  const int64_t koff = (int64_t)b * K.sb + (int64_t)h * K.sh;
-  const int64_t voff = (int64_t)b * V.sb + (int64_t)h * V.sh;
-  const int64_t rowoff = ((int64_t)b * H + h) * T;
+  const int64_t koff = (int64_t)b * K.sb + (int64_t)hk * K.sh;
+  const int64_t voff = (int64_t)b * V.sb + (int64_t)hk * V.sh;
   DropSite site;
   if constexpr (DROP) site = drop_site(ticket, dstream, thr);
-  const uint64_t bh = (uint64_t)b * H + h;
   const int TP = (T + 3) >> 2;
 
   // K^T and V^T as B operands (lane = key column), held in registers: [key subtile][k-step]
@@ -533,95 +541,102 @@ __global__ __launch_bounds__(256, DKDV_MINW) void attn_bwd_dkdv_kernel(Tensor4 Q
 
   const int q_start = CAUSAL ? (kblk / 64) * 64 : 0;
   const int ntiles = (T - q_start + 63) / 64;
-  const __amdgpu_buffer_rsrc_t qrs = slice_rsrc(Q.p + qoff, T, Q.st), drs = slice_rsrc(DO.p + dooff, T, DO.st);
-  Stage sq, sd;
-  sq.load(qrs, Q.st, q_start, tid);
-  sd.load(drs, DO.st, q_start, tid);
-  for (int t = 0; t < ntiles; ++t) {
-    const int q0 = q_start + t * 64;
-    __syncthreads();
-    sq.store(Qs, tid);
-    sd.store(Ds, tid);
-    if (tid < 64) {
-      const int qr = q0 + tid;
-      srow[0][tid] = qr < T ? LSE[rowoff + qr] * LOG2E : 0.f;
-      srow[1][tid] = qr < T ? DELTA[rowoff + qr] : 0.f;
-    }
-    __syncthreads();
-    if (t + 1 < ntiles) {
-      sq.load(qrs, Q.st, q0 + 64, tid);
-      sd.load(drs, DO.st, q0 + 64, tid);
-    }
-    // no key of this wave exists, or every query of the tile precedes this wave's keys
-    if (kbase >= T || (CAUSAL && q0 + 63 < kbase)) continue;
-    // masking only on tiles that cross the sequence end or the causal diagonal; interior tiles
-    // run a mask-free instantiation (no per-score compare/select: ~80 VALU ops per tile)
-    const bool edge = (q0 + 64 > T) || (kbase + 32 > T) || (CAUSAL && q0 < kbase + 32);
-    auto tile_body = [&](auto edge_c) {
-      constexpr bool EDGE = decltype(edge_c)::value;
+  for (int gq = 0; gq < (GQA ? G : 1); ++gq) {  // the query heads that read this K/V head
+    const int h = GQA ? hk * G + gq : hk;
+    const int64_t qoff = (int64_t)b * Q.sb + (int64_t)h * Q.sh;
+    const int64_t dooff = (int64_t)b * DO.sb + (int64_t)h * DO.sh;
+    const int64_t rowoff = ((int64_t)b * H + h) * T;
+    const uint64_t bh = (uint64_t)b * H + h;
+    const __amdgpu_buffer_rsrc_t qrs = slice_rsrc(Q.p + qoff, T, Q.st), drs = slice_rsrc(DO.p + dooff, T, DO.st);
+    Stage sq, sd;
+    sq.load(qrs, Q.st, q_start, tid);
+    sd.load(drs, DO.st, q_start, tid);
+    for (int t = 0; t < ntiles; ++t) {
+      const int q0 = q_start + t * 64;
+      __syncthreads();
+      sq.store(Qs, tid);
+      sd.store(Ds, tid);
+      if (tid < 64) {
+        const int qr = q0 + tid;
+        srow[0][tid] = qr < T ? LSE[rowoff + qr] * LOG2E : 0.f;
+        srow[1][tid] = qr < T ? DELTA[rowoff + qr] : 0.f;
+      }
+      __syncthreads();
+      if (t + 1 < ntiles) {
+        sq.load(qrs, Q.st, q0 + 64, tid);
+        sd.load(drs, DO.st, q0 + 64, tid);
+      }
+      // no key of this wave exists, or every query of the tile precedes this wave's keys
+      if (kbase >= T || (CAUSAL && q0 + 63 < kbase)) continue;
+      // masking only on tiles that cross the sequence end or the causal diagonal; interior tiles
+      // run a mask-free instantiation (no per-score compare/select: ~80 VALU ops per tile)
+      const bool edge = (q0 + 64 > T) || (kbase + 32 > T) || (CAUSAL && q0 < kbase + 32);
+      auto tile_body = [&](auto edge_c) {
+        constexpr bool EDGE = decltype(edge_c)::value;
 #pragma unroll
-      for (int kq = 0; kq < 2; ++kq) {  // 32-query k-step for the dV/dK products
-        bf16x8 pb[2], dsb[2];
-        // quad lane i (= key & 3) computes the block of (key subtile i >> 1, query subtile 2 kq + (i & 1))
-        PhiloxOut mine;
-        if constexpr (DROP)
-          mine = drop_block(site, drop_attn_block(bh, TP, q0 + (2 * kq + (lane & 1)) * 16 + 4 * g,
-                                                  kbase + 16 * ((lane >> 1) & 1) + c));
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-          f4 pp[2], dd[2];
-#pragma unroll
-          for (int half = 0; half < 2; ++half) {
-            const int qs = 2 * kq + half;  // 16-query subtile
-            const bf16x8 qa0 = lds_row8(Qs, qs * 16 + c, g), qa1 = lds_row8(Qs, qs * 16 + c, 4 + g);
-            const bf16x8 da0 = lds_row8(Ds, qs * 16 + c, g), da1 = lds_row8(Ds, qs * 16 + c, 4 + g);
-            f4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-            s = mfma(qa0, bk[kb][0], s);
-            s = mfma(qa1, bk[kb][1], s);
-            dp = mfma(da0, bv[kb][0], dp);
-            dp = mfma(da1, bv[kb][1], dp);
-            const int key = kbase + 16 * kb + c;
-            PhiloxOut mo;
-            if constexpr (DROP) mo = quad_block(mine, 2 * kb + half);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int ql = qs * 16 + 4 * g + r;
-              const int qi = q0 + ql;
-              float p = fast_exp2(fmaf(s[r], sl2, -srow[0][ql]));
-              if (EDGE && (qi >= T || key >= T || (CAUSAL && key > qi))) p = 0.f;
-              if constexpr (DROP) {  // dV takes P m (scale in the epilogue), dS = P (m scale dP - delta)
-                const bool keep = drop_keep(mo.w[r], key & 3, site.thr);
-                pp[half][r] = keep ? p : 0.f;
-                dd[half][r] = p * ((keep ? dp[r] * site.scale : 0.f) - srow[1][ql]);
-              } else {
-                pp[half][r] = p;
-                dd[half][r] = p * (dp[r] - srow[1][ql]);
-              }
-            }
-          }
-          pb[kb] = pack8(pp[0], pp[1]);
-          dsb[kb] = pack8(dd[0], dd[1]);
-        }
-#pragma unroll
-        for (int n = 0; n < 4; ++n) {
-          const bf16x8 doT = cat8(lds_tr4(Ds, 32 * kq + 4 * g, 16 * n, lane), lds_tr4(Ds, 32 * kq + 16 + 4 * g, 16 * n, lane));
-          const bf16x8 qT = cat8(lds_tr4(Qs, 32 * kq + 4 * g, 16 * n, lane), lds_tr4(Qs, 32 * kq + 16 + 4 * g, 16 * n, lane));
+        for (int kq = 0; kq < 2; ++kq) {  // 32-query k-step for the dV/dK products
+          bf16x8 pb[2], dsb[2];
+          // quad lane i (= key & 3) computes the block of (key subtile i >> 1, query subtile 2 kq + (i & 1))
+          PhiloxOut mine;
+          if constexpr (DROP)
+            mine = drop_block(site, drop_attn_block(bh, TP, q0 + (2 * kq + (lane & 1)) * 16 + 4 * g,
+                                                    kbase + 16 * ((lane >> 1) & 1) + c));
 #pragma unroll
           for (int kb = 0; kb < 2; ++kb) {
-            dv[kb][n] = mfma(doT, pb[kb], dv[kb][n]);
-            dk[kb][n] = mfma(qT, dsb[kb], dk[kb][n]);
+            f4 pp[2], dd[2];
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+              const int qs = 2 * kq + half;  // 16-query subtile
+              const bf16x8 qa0 = lds_row8(Qs, qs * 16 + c, g), qa1 = lds_row8(Qs, qs * 16 + c, 4 + g);
+              const bf16x8 da0 = lds_row8(Ds, qs * 16 + c, g), da1 = lds_row8(Ds, qs * 16 + c, 4 + g);
+              f4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+              s = mfma(qa0, bk[kb][0], s);
+              s = mfma(qa1, bk[kb][1], s);
+              dp = mfma(da0, bv[kb][0], dp);
+              dp = mfma(da1, bv[kb][1], dp);
+              const int key = kbase + 16 * kb + c;
+              PhiloxOut mo;
+              if constexpr (DROP) mo = quad_block(mine, 2 * kb + half);
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                const int ql = qs * 16 + 4 * g + r;
+                const int qi = q0 + ql;
+                float p = fast_exp2(fmaf(s[r], sl2, -srow[0][ql]));
+                if (EDGE && (qi >= T || key >= T || (CAUSAL && key > qi))) p = 0.f;
+                if constexpr (DROP) {  // dV takes P m (scale in the epilogue), dS = P (m scale dP - delta)
+                  const bool keep = drop_keep(mo.w[r], key & 3, site.thr);
+                  pp[half][r] = keep ? p : 0.f;
+                  dd[half][r] = p * ((keep ? dp[r] * site.scale : 0.f) - srow[1][ql]);
+                } else {
+                  pp[half][r] = p;
+                  dd[half][r] = p * (dp[r] - srow[1][ql]);
+                }
+              }
+            }
+            pb[kb] = pack8(pp[0], pp[1]);
+            dsb[kb] = pack8(dd[0], dd[1]);
+          }
+#pragma unroll
+          for (int n = 0; n < 4; ++n) {
+            const bf16x8 doT = cat8(lds_tr4(Ds, 32 * kq + 4 * g, 16 * n, lane), lds_tr4(Ds, 32 * kq + 16 + 4 * g, 16 * n, lane));
+            const bf16x8 qT = cat8(lds_tr4(Qs, 32 * kq + 4 * g, 16 * n, lane), lds_tr4(Qs, 32 * kq + 16 + 4 * g, 16 * n, lane));
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb) {
+              dv[kb][n] = mfma(doT, pb[kb], dv[kb][n]);
+              dk[kb][n] = mfma(qT, dsb[kb], dk[kb][n]);
+            }
           }
         }
-      }
-    };
-    if (edge) tile_body(std::true_type{});
-    else tile_body(std::false_type{});
+      };
+      if (edge) tile_body(std::true_type{});
+      else tile_body(std::false_type{});
+    }
   }
 #pragma unroll
   for (int kb = 0; kb < 2; ++kb) {
     const int kr = kbase + 16 * kb + c;
     if (kr >= T) continue;
-    const int64_t off = (int64_t)b * g_sb + (int64_t)h * g_sh + (int64_t)kr * g_st;
+    const int64_t off = (int64_t)b * g_sb + (int64_t)hk * g_sh + (int64_t)kr * g_st;
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
       float a4[4] = {dk[kb][n][0] * scale, dk[kb][n][1] * scale, dk[kb][n][2] * scale, dk[kb][n][3] * scale};
@@ -678,6 +693,55 @@ int pdt_attn_bwd(const uint16_t* dout, const int64_t* dos, const uint16_t* q, co
                        gs[2], H, T, sl2, scale);
     hipLaunchKernelGGL(attn_bwd_dkdv_kernel<false>, grid, dim3(256), 0, s, Q, K, V, DO, lse, delta, dk, dv, gs[0],
                        gs[1], gs[2], H, T, sl2, scale);
+  }
+  return 0;
+}
+
+// Grouped-query attention: q/o/dout/dq are [B, H, T, 64] views, k/v/dk/dv [B, Hkv, T, 64] views; query head h
+// reads K/V head h / (H / Hkv). lse / delta stay [B, H, T]. No dropout form.
+int pdt_attn_fwd_gqa(const uint16_t* q, const int64_t* qs, const uint16_t* k, const int64_t* ks, const uint16_t* v,
+                     const int64_t* vs, uint16_t* o, const int64_t* os, float* lse, int B, int H, int Hkv, int T,
+                     int Dh, int causal, float scale, hipStream_t s) {
+  if (Dh != D) return -1;
+  if (Hkv <= 0 || H % Hkv != 0) return -3;
+  const Tensor4 Q{q, qs[0], qs[1], qs[2]}, K{k, ks[0], ks[1], ks[2]}, V{v, vs[0], vs[1], vs[2]};
+  const dim3 grid((T + 127) / 128, H, B);
+  const float sl2 = scale * LOG2E;
+  const int G = H / Hkv;
+  if (causal)
+    hipLaunchKernelGGL((attn_fwd_kernel<true, false, true>), grid, dim3(256), 0, s, Q, K, V, o, os[0], os[1], os[2],
+                       lse, H, T, sl2, (const int64_t*)nullptr, 0, 0, G);
+  else
+    hipLaunchKernelGGL((attn_fwd_kernel<false, false, true>), grid, dim3(256), 0, s, Q, K, V, o, os[0], os[1], os[2],
+                       lse, H, T, sl2, (const int64_t*)nullptr, 0, 0, G);
+  return 0;
+}
+
+// dq takes the strides gs at H heads, dk/dv the same strides at Hkv heads (slices of one packed dqkv).
+int pdt_attn_bwd_gqa(const uint16_t* dout, const int64_t* dos, const uint16_t* q, const int64_t* qs,
+                     const uint16_t* k, const int64_t* ks, const uint16_t* v, const int64_t* vs, const uint16_t* o,
+                     const int64_t* os, const float* lse, float* delta, uint16_t* dq, uint16_t* dk, uint16_t* dv,
+                     const int64_t* gs, int B, int H, int Hkv, int T, int Dh, int causal, float scale, hipStream_t s) {
+  if (Dh != D) return -1;
+  if (Hkv <= 0 || H % Hkv != 0) return -3;
+  const Tensor4 Q{q, qs[0], qs[1], qs[2]}, K{k, ks[0], ks[1], ks[2]}, V{v, vs[0], vs[1], vs[2]};
+  const Tensor4 DO{dout, dos[0], dos[1], dos[2]}, Ot{o, os[0], os[1], os[2]};
+  const int64_t rows = (int64_t)B * H * T;
+  hipLaunchKernelGGL(attn_bwd_pre_kernel, dim3((unsigned)((rows * 8 + 255) / 256)), dim3(256), 0, s, DO, Ot, delta, H,
+                     T, rows);
+  const dim3 grid((T + 127) / 128, H, B), gridkv((T + 127) / 128, Hkv, B);
+  const float sl2 = scale * LOG2E;
+  const int G = H / Hkv;
+  if (causal) {
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<true, false, true>), grid, dim3(256), 0, s, Q, K, V, DO, lse, delta, dq,
+                       gs[0], gs[1], gs[2], H, T, sl2, scale, (const int64_t*)nullptr, 0, 0, G);
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<true, false, true>), gridkv, dim3(256), 0, s, Q, K, V, DO, lse, delta,
+                       dk, dv, gs[0], gs[1], gs[2], H, T, sl2, scale, (const int64_t*)nullptr, 0, 0, G);
+  } else {
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<false, false, true>), grid, dim3(256), 0, s, Q, K, V, DO, lse, delta, dq,
+                       gs[0], gs[1], gs[2], H, T, sl2, scale, (const int64_t*)nullptr, 0, 0, G);
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<false, false, true>), gridkv, dim3(256), 0, s, Q, K, V, DO, lse, delta,
+                       dk, dv, gs[0], gs[1], gs[2], H, T, sl2, scale, (const int64_t*)nullptr, 0, 0, G);
   }
   return 0;
 }

@@ -38,6 +38,15 @@ int pdt_attn_bwd_drop(const uint16_t* dout, const int64_t* dos, const uint16_t* 
                       const int64_t* os, const float* lse, float* delta, uint16_t* dq, uint16_t* dk, uint16_t* dv,
                       const int64_t* gs, int B, int H, int T, int Dh, int causal, float scale, const int64_t* ticket,
                       int dstream, int thr, hipStream_t s);
+// Grouped-query attention: q/o/do/dq have H heads, k/v/dk/dv have Hkv (H % Hkv == 0); query head h reads
+// K/V head h / (H / Hkv). lse, delta: [B, H, T].
+int pdt_attn_fwd_gqa(const uint16_t* q, const int64_t* qs, const uint16_t* k, const int64_t* ks, const uint16_t* v,
+                     const int64_t* vs, uint16_t* o, const int64_t* os, float* lse, int B, int H, int Hkv, int T,
+                     int Dh, int causal, float scale, hipStream_t s);
+int pdt_attn_bwd_gqa(const uint16_t* dout, const int64_t* dos, const uint16_t* q, const int64_t* qs,
+                     const uint16_t* k, const int64_t* ks, const uint16_t* v, const int64_t* vs, const uint16_t* o,
+                     const int64_t* os, const float* lse, float* delta, uint16_t* dq, uint16_t* dk, uint16_t* dv,
+                     const int64_t* gs, int B, int H, int Hkv, int T, int Dh, int causal, float scale, hipStream_t s);
 
 // kernels/batchnorm.hip
 int64_t pdt_bn_workspace_floats(int64_t M, int C);
@@ -322,6 +331,8 @@ int pdt_rms_bwd(const void* dy, const void* x, const void* dres, int dtype, cons
 
 // kernels/rope.hip
 int pdt_rope_qkv(uint16_t* qkv, const float* cos, const float* sin, int B, int T, int H, int conj, hipStream_t s);
+int pdt_rope_qkv_gqa(uint16_t* qkv, const float* cos, const float* sin, int B, int T, int H, int Hkv, int conj,
+                     hipStream_t s);
 
 // kernels/slice_sum.hip
 int pdt_slice_sum_bf16(const uint16_t* x, uint16_t* out, int S, int64_t n, hipStream_t s);

@@ -6,11 +6,13 @@ place from the packed QKV GEMM output at head dim 64, the bias-free GEMMs of ops
 fused cross-entropy. As in ``run_blocks`` every residual add is inside the RMSNorm that follows it,
 one kernel per residual step each way.
 
-Multi-head attention only (no grouped-query attention), head dim 64, no dropout sites, no fp8 forms,
-sequence length at most ``block_size`` (the RoPE table). Parameter names follow the nanoGPT-style
-layout of models/gpt2.py: ``transformer.wte``, ``transformer.h.{i}.ln_1``, ``.attn.c_attn`` (packed
-q, k, v rows), ``.attn.c_proj``, ``.ln_2``, ``.mlp.c_fc`` (packed [gate; up] rows), ``.mlp.c_proj``,
-``transformer.ln_f``, ``lm_head``; ``from_hf_state_dict`` maps a Hugging Face Llama state dict onto it.
+Multi-head or grouped-query attention (``n_kv_head`` K/V heads, each shared by ``n_head / n_kv_head``
+consecutive query heads, HF's ``repeat_kv`` order; the flash kernels read the shared heads in place),
+head dim 64, no dropout sites, no fp8 forms, sequence length at most ``block_size`` (the RoPE table).
+Parameter names follow the nanoGPT-style layout of models/gpt2.py: ``transformer.wte``,
+``transformer.h.{i}.ln_1``, ``.attn.c_attn`` (packed q, k, v rows: ``(n_head + 2·n_kv_head)·64`` of them),
+``.attn.c_proj``, ``.ln_2``, ``.mlp.c_fc`` (packed [gate; up] rows), ``.mlp.c_proj``, ``transformer.ln_f``,
+``lm_head``; ``from_hf_state_dict`` maps a Hugging Face Llama state dict onto it.
 """
 from __future__ import annotations
 
@@ -43,20 +45,28 @@ class LlamaConfig:
     vocab_size: int = 32000
     rope_base: float = 10000.0
     eps: float = 1e-5
+    n_kv_head: int | None = None  # K/V heads (grouped-query attention); None: n_head, multi-head attention
+
+    @property
+    def kv_heads(self) -> int:
+        return self.n_head if self.n_kv_head is None else self.n_kv_head
 
 
 class LlamaAttention(nn.Module):
-    def __init__(self, dim: int, heads: int):
+    def __init__(self, dim: int, heads: int, kv_heads: int | None = None):
         super().__init__()
         assert dim == heads * HEAD_DIM, f"head dim must be {HEAD_DIM}: n_embd {dim}, n_head {heads}"
-        self.heads = heads
-        self.c_attn = nn.Linear(dim, 3 * dim, bias=False)
+        kv_heads = heads if kv_heads is None else kv_heads
+        if kv_heads <= 0 or heads % kv_heads != 0:
+            raise ValueError(f"n_kv_head = {kv_heads} must be positive and divide n_head = {heads}")
+        self.heads, self.kv_heads = heads, kv_heads
+        self.c_attn = nn.Linear(dim, (heads + 2 * kv_heads) * HEAD_DIM, bias=False)  # q, then k, then v rows
         self.c_proj = nn.Linear(dim, dim, bias=False)
 
     def forward(self, x: torch.Tensor, rope: RotaryTable) -> torch.Tensor:
-        qkv = linear(x, self.c_attn.weight)  # [B, T, 3D]; its backward needs x and W only, so
-        qkv = rope_qkv_(qkv, rope.cos, rope.sin, self.heads)  # Q and K are rotated in place
-        y = attention_qkv(qkv, self.heads, causal=True)
+        qkv = linear(x, self.c_attn.weight)  # [B, T, (H + 2 Hkv) 64]; its backward needs x and W only, so
+        qkv = rope_qkv_(qkv, rope.cos, rope.sin, self.heads, self.kv_heads)  # Q and K are rotated in place
+        y = attention_qkv(qkv, self.heads, causal=True, kv_heads=self.kv_heads)
         return linear(y, self.c_proj.weight)
 
 
@@ -76,7 +86,7 @@ class LlamaBlock(nn.Module):
     def __init__(self, cfg: LlamaConfig):
         super().__init__()
         self.ln_1 = RMSNorm(cfg.n_embd, eps=cfg.eps)
-        self.attn = LlamaAttention(cfg.n_embd, cfg.n_head)
+        self.attn = LlamaAttention(cfg.n_embd, cfg.n_head, cfg.n_kv_head)
         self.ln_2 = RMSNorm(cfg.n_embd, eps=cfg.eps)
         self.mlp = LlamaMLP(cfg.n_embd, cfg.ffn)
 
@@ -128,9 +138,11 @@ class Llama(nn.Module):
         return cross_entropy(logits.reshape(-1, logits.shape[-1]), targets.reshape(-1))
 
 
-def from_hf_state_dict(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-    """A Hugging Face ``LlamaForCausalLM`` state dict (multi-head attention, head dim 64) in this
-    file's layout: q/k/v rows concatenated into ``c_attn``, gate/up rows into ``c_fc``.
+def from_hf_state_dict(sd: Dict[str, torch.Tensor], n_kv_head: int | None = None) -> Dict[str, torch.Tensor]:
+    """A Hugging Face ``LlamaForCausalLM`` state dict (head dim 64) in this file's layout: q/k/v rows
+    concatenated into ``c_attn``, gate/up rows into ``c_fc``. A grouped-query checkpoint (k/v projections
+    of ``num_key_value_heads·64`` rows) needs ``n_kv_head`` = that count, which is also the ``n_kv_head``
+    of the ``LlamaConfig`` to load it into; without it only multi-head state dicts are accepted.
 
     No row permutation is needed: HF applies RoPE in the half-split ``rotate_half`` convention, pair
     (j, j + 32) of each head, which is the convention of ops/rope.py. (The interleaved pairs
@@ -144,9 +156,14 @@ def from_hf_state_dict(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     while f"model.layers.{i}.input_layernorm.weight" in sd:
         src, dst = f"model.layers.{i}.", f"transformer.h.{i}."
         q, k, v = (sd[f"{src}self_attn.{n}_proj.weight"] for n in ("q", "k", "v"))
-        if not (q.shape == k.shape == v.shape):
-            raise ValueError(f"layer {i}: grouped-query attention (k/v {tuple(k.shape)} against q "
-                             f"{tuple(q.shape)}) is not supported")
+        if n_kv_head is None:
+            if not (q.shape == k.shape == v.shape):
+                raise ValueError(f"layer {i}: grouped-query attention (k/v {tuple(k.shape)} against q "
+                                 f"{tuple(q.shape)}) needs n_kv_head: pass from_hf_state_dict(sd, n_kv_head="
+                                 "num_key_value_heads)")
+        elif not (k.shape == v.shape == (n_kv_head * HEAD_DIM, q.shape[1]) and q.shape[0] % k.shape[0] == 0):
+            raise ValueError(f"layer {i}: k/v {tuple(k.shape)}, {tuple(v.shape)} are not n_kv_head·{HEAD_DIM} = "
+                             f"{n_kv_head * HEAD_DIM} rows each dividing q's {q.shape[0]}")
         out[dst + "ln_1.weight"] = sd[src + "input_layernorm.weight"]
         out[dst + "attn.c_attn.weight"] = torch.cat([q, k, v], 0)
         out[dst + "attn.c_proj.weight"] = sd[src + "self_attn.o_proj.weight"]
@@ -157,19 +174,38 @@ def from_hf_state_dict(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return out
 
 
+# the registered presets: what each overrides of LlamaConfig's defaults (llama_medium's)
+PRESETS = {
+    "llama_medium": {},  # GPT-2-medium's depth and width (24 x 1024, 16 heads), F = 2816
+    "llama_small": dict(n_layer=12, n_head=12, n_embd=768, ffn=2048),
+    "llama_tiny": dict(n_layer=2, n_head=4, n_embd=256, ffn=768, block_size=64, vocab_size=512),  # for tests
+}
+PRESETS["llama_tiny_gqa"] = dict(PRESETS["llama_tiny"], n_kv_head=2)  # 2 K/V heads for its 4 query heads
+
+
+def _preset(name: str, kw: dict) -> Llama:
+    return Llama(LlamaConfig(**{**PRESETS[name], **kw}))
+
+
 def llama_medium(**kw) -> Llama:
-    """GPT-2-medium's depth and width (24 x 1024, 16 heads), F = 2816."""
-    return Llama(LlamaConfig(**kw))
+    return _preset("llama_medium", kw)
 
 
 def llama_small(**kw) -> Llama:
-    return Llama(LlamaConfig(**{**dict(n_layer=12, n_head=12, n_embd=768, ffn=2048), **kw}))
+    return _preset("llama_small", kw)
 
 
 def llama_tiny(**kw) -> Llama:
-    """Small config for tests."""
-    return Llama(LlamaConfig(**{**dict(n_layer=2, n_head=4, n_embd=256, ffn=768, block_size=64, vocab_size=512),
-                                **kw}))
+    return _preset("llama_tiny", kw)
+
+
+def llama_tiny_gqa(**kw) -> Llama:
+    return _preset("llama_tiny_gqa", kw)
+
+
+def n_heads(model_name: str) -> int | None:
+    """The query-head count of a registered preset (None for any other name), without building the model."""
+    return LlamaConfig(**PRESETS[model_name]).n_head if model_name in PRESETS else None
 
 
 from . import register  # noqa: E402
@@ -177,3 +213,4 @@ from . import register  # noqa: E402
 register("llama_medium", llama_medium)
 register("llama_small", llama_small)
 register("llama_tiny", llama_tiny)
+register("llama_tiny_gqa", llama_tiny_gqa)

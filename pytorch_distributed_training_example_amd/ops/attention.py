@@ -8,6 +8,14 @@ permute/contiguous/cat copies around attention (PyTorch SDPA needs three of them
 
 Head dim 64 (ViT-B/16, GPT-2-medium) runs on the HIP kernels; anything else falls back to
 ``F.scaled_dot_product_attention``. CPU tensors use the math reference.
+
+Grouped-query attention: ``attention_qkv(qkv, heads, causal, kv_heads=Hkv)`` takes the packed tensor
+[B, T, (H + 2·Hkv)·Dh] (H query heads, then Hkv key heads, then Hkv value heads: the row order of
+``torch.cat([q_proj, k_proj, v_proj]).weight``); query head h reads K/V head h // (H / Hkv), HF's
+``repeat_kv`` order. The GQA kernels read the Hkv heads in place (no expanded copy) and the dK/dV
+kernel sums a group's query heads in fp32 registers in a fixed order: no atomics, one rounding.
+``kv_heads`` of ``None`` or ``heads`` is multi-head attention, the code path above unchanged. There is
+no dropout on the grouped-query path.
 """
 from __future__ import annotations
 
@@ -53,6 +61,64 @@ class _FlashQKVFn(torch.autograd.Function):
         return dqkv, None, None, None
 
 
+def _views_gqa(qkv: torch.Tensor, heads: int, kv_heads: int):
+    """q [B, H, T, Dh], k and v [B, Hkv, T, Dh]: strided views of the packed [B, T, (H + 2·Hkv)·Dh]."""
+    B, T, C = qkv.shape
+    dh = C // (heads + 2 * kv_heads)
+    v4 = qkv.view(B, T, heads + 2 * kv_heads, dh).permute(0, 2, 1, 3)
+    return (v4[:, :heads], v4[:, heads:heads + kv_heads], v4[:, heads + kv_heads:]), dh
+
+
+class _FlashGQAFn(torch.autograd.Function):
+    """_FlashQKVFn for kv_heads < heads: the GQA instantiations of the flash kernels on views of the
+    packed tensor; the backward fills one packed dqkv of the forward's layout."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, kv_heads, causal, scale):
+        B, T, _ = qkv.shape
+        (q, k, v), dh = _views_gqa(qkv, heads, kv_heads)
+        out = torch.empty(B, T, heads, dh, device=qkv.device, dtype=qkv.dtype)
+        lse = torch.empty(B, heads, T, device=qkv.device, dtype=torch.float32)
+        native().attn_fwd_gqa_out(q, k, v, out.permute(0, 2, 1, 3), lse, causal, scale)
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.heads, ctx.kv_heads, ctx.causal, ctx.scale = heads, kv_heads, causal, scale
+        return out.view(B, T, heads * dh)
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse = ctx.saved_tensors
+        B, T, _ = qkv.shape
+        heads, kv_heads = ctx.heads, ctx.kv_heads
+        (q, k, v), dh = _views_gqa(qkv, heads, kv_heads)
+        dout = dout.contiguous().view(B, T, heads, dh).permute(0, 2, 1, 3)
+        dqkv = torch.empty_like(qkv)
+        (dq, dk, dv), _ = _views_gqa(dqkv, heads, kv_heads)
+        native().attn_bwd_gqa_out(dout, q, k, v, out.permute(0, 2, 1, 3), lse, dq, dk, dv, ctx.causal, ctx.scale)
+        return dqkv, None, None, None, None
+
+
+def _attention_gqa(qkv, heads, kv_heads, causal, scale):
+    if kv_heads <= 0 or heads % kv_heads != 0:
+        raise ValueError(f"attention_qkv: heads = {heads} is not a positive multiple of kv_heads = {kv_heads}")
+    B, T, C = qkv.shape
+    if C % (heads + 2 * kv_heads) != 0:
+        raise ValueError(f"attention_qkv: last dim {C} is not (heads + 2·kv_heads)·Dh with heads = {heads}, "
+                         f"kv_heads = {kv_heads}")
+    dh = C // (heads + 2 * kv_heads)
+    scale = scale if scale is not None else 1.0 / math.sqrt(dh)
+    flash = (use_native(qkv) and qkv.dtype == torch.bfloat16 and dh in KERNEL_HEAD_DIMS and qkv.stride(-1) == 1)
+    if flash:  # a build without the GQA launchers is an error here, not a fall-back
+        return _FlashGQAFn.apply(qkv.contiguous(), heads, kv_heads, causal, scale)
+    (q, k, v), _ = _views_gqa(qkv, heads, kv_heads)
+    G = heads // kv_heads  # expanded K/V; autograd sums each group's gradient
+    k, v = k.repeat_interleave(G, dim=1), v.repeat_interleave(G, dim=1)
+    if qkv.is_cuda:
+        y = F.scaled_dot_product_attention(q, k, v, is_causal=causal, scale=scale)
+    else:
+        y = attention_reference(q, k, v, causal, scale).to(qkv.dtype)
+    return y.transpose(1, 2).reshape(B, T, heads * dh)
+
+
 class _FlashQKVDropFn(torch.autograd.Function):
     """_FlashQKVFn with dropout on the attention probabilities: the DROP kernels regenerate the mask
     from (ticket, stream) in the forward, dQ and dK/dV kernels (csrc/philox.h); nothing else is saved."""
@@ -83,12 +149,20 @@ class _FlashQKVDropFn(torch.autograd.Function):
 
 
 def attention_qkv(qkv: torch.Tensor, heads: int, causal: bool = False, dropout_p: float = 0.0,
-                  scale: float | None = None, ticket=None, stream: int | None = None) -> torch.Tensor:
-    """Packed-QKV attention: [B, T, 3·H·Dh] -> [B, T, H·Dh].
+                  scale: float | None = None, ticket=None, stream: int | None = None,
+                  kv_heads: int | None = None) -> torch.Tensor:
+    """Packed-QKV attention: [B, T, 3·H·Dh] -> [B, T, H·Dh]; with ``kv_heads`` (grouped-query attention)
+    [B, T, (H + 2·Hkv)·Dh] -> [B, T, H·Dh]. ``kv_heads`` of ``None`` or ``heads`` is multi-head attention.
 
     ``dropout_p > 0`` with a ``ticket`` (ops/dropout.py) drops attention probabilities with the
     counter-generated mask and stays on the flash kernels (GPU) / the masked math reference (CPU).
-    Without a ticket (or under PDT_DROPOUT_FUSED=0) ``dropout_p > 0`` is aten's: SDPA on the GPU."""
+    Without a ticket (or under PDT_DROPOUT_FUSED=0) ``dropout_p > 0`` is aten's: SDPA on the GPU.
+    Grouped-query attention has no dropout form: ``kv_heads != heads`` with ``dropout_p > 0`` raises."""
+    if kv_heads is not None and kv_heads != heads:
+        if dropout_p != 0.0:
+            raise ValueError("attention_qkv: dropout is not supported with grouped-query attention "
+                             f"(kv_heads = {kv_heads}, heads = {heads})")
+        return _attention_gqa(qkv, heads, kv_heads, causal, scale)
     B, T, C3 = qkv.shape
     dh = C3 // (3 * heads)
     scale = scale if scale is not None else 1.0 / math.sqrt(dh)

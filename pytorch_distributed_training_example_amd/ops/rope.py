@@ -1,15 +1,17 @@
 """Rotary position embedding on the packed QKV tensor (csrc/kernels/rope.hip).
 
 ``rope_qkv_(qkv, cos, sin, heads)`` rotates the Q and K thirds of the ``c_attn`` output
-[B, T, 3·H·Dh] in place and returns it; V is not touched. Half-split convention (HF's
+[B, T, 3·H·Dh] in place and returns it; V is not touched. With ``kv_heads=Hkv`` (grouped-query
+attention) the tensor is [B, T, (H + 2·Hkv)·Dh]: the H query heads and the Hkv key heads, columns
+[0, (H + Hkv)·Dh), are rotated and the Hkv value heads behind them are neither read nor written. Half-split convention (HF's
 ``rotate_half``): for every head, position t and j < Dh/2
 
     x'[j]        = x[j]·cos[t, j] − x[j + Dh/2]·sin[t, j]
     x'[j + Dh/2] = x[j + Dh/2]·cos[t, j] + x[j]·sin[t, j]
 
 The rotation is orthogonal, so the backward is the same kernel with the sine negated, run in place
-on the packed gradient attention's backward returns: one read and one write of two thirds of the
-tensor each way, no copy of V, nothing saved but the table. bf16 GPU tensors at head dim 64 take the
+on the packed gradient attention's backward returns: one read and one write of the rotated heads
+each way, no copy of V, nothing saved but the table. bf16 GPU tensors at head dim 64 take the
 HIP kernel; anything else (CPU, fp32, ``PDT_DISABLE_NATIVE=1``) the same math in plain PyTorch.
 """
 from __future__ import annotations
@@ -44,20 +46,20 @@ class RotaryTable(nn.Module):
         self.register_buffer("sin", sin, persistent=False)
 
 
-def _native_ok(qkv, cos, sin, heads) -> bool:
+def _native_ok(qkv, cos, sin, heads, kv_heads) -> bool:
     return (use_native(qkv) and qkv.dtype == torch.bfloat16 and qkv.dim() == 3 and qkv.is_contiguous()
-            and qkv.shape[-1] == 3 * heads * KERNEL_HEAD_DIM and cos.dtype == torch.float32
+            and qkv.shape[-1] == (heads + 2 * kv_heads) * KERNEL_HEAD_DIM and cos.dtype == torch.float32
             and cos.shape[-1] == KERNEL_HEAD_DIM // 2 and qkv.data_ptr() % 16 == 0)
 
 
-def _rotate_reference_(qkv, cos, sin, heads, conj):
-    B, T, C3 = qkv.shape
-    dh = C3 // (3 * heads)
+def _rotate_reference_(qkv, cos, sin, heads, kv_heads, conj):
+    B, T, C = qkv.shape
+    dh = C // (heads + 2 * kv_heads)
     half = dh // 2
-    qk = qkv.view(B, T, 3, heads, dh)[:, :, :2]
+    qk = qkv.view(B, T, heads + 2 * kv_heads, dh)[:, :, :heads + kv_heads]  # the Q heads, then the K heads
     lo, hi = qk[..., :half].float(), qk[..., half:].float()
-    c = cos[:T].float().view(1, T, 1, 1, half)
-    s = sin[:T].float().view(1, T, 1, 1, half)
+    c = cos[:T].float().view(1, T, 1, half)
+    s = sin[:T].float().view(1, T, 1, half)
     if conj:
         s = -s
     new_lo, new_hi = lo * c - hi * s, hi * c + lo * s  # both before either write: lo / hi alias qkv in fp32
@@ -66,36 +68,46 @@ def _rotate_reference_(qkv, cos, sin, heads, conj):
     return qkv
 
 
-def _rotate_(qkv, cos, sin, heads, conj):
-    B, T, C3 = qkv.shape
+def _rotate_(qkv, cos, sin, heads, kv_heads, conj):
+    B, T, C = qkv.shape
     if T > cos.shape[0]:
         raise ValueError(f"rope: sequence length {T} exceeds the table's {cos.shape[0]} positions")
-    if _native_ok(qkv, cos, sin, heads):
-        native().rope_qkv(qkv, cos, sin, heads, conj)
+    if _native_ok(qkv, cos, sin, heads, kv_heads):
+        if kv_heads == heads:
+            native().rope_qkv(qkv, cos, sin, heads, conj)
+        else:
+            native().rope_qkv_gqa(qkv, cos, sin, heads, kv_heads, conj)
         return qkv
-    return _rotate_reference_(qkv, cos, sin, heads, conj)
+    return _rotate_reference_(qkv, cos, sin, heads, kv_heads, conj)
 
 
 class _RopeQKVFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, cos, sin, heads):
+    def forward(ctx, qkv, cos, sin, heads, kv_heads):
         ctx.mark_dirty(qkv)
         ctx.save_for_backward(cos, sin)
-        ctx.heads = heads
-        return _rotate_(qkv, cos, sin, heads, False)
+        ctx.heads, ctx.kv_heads = heads, kv_heads
+        return _rotate_(qkv, cos, sin, heads, kv_heads, False)
 
     @staticmethod
     def backward(ctx, dqkv):
         cos, sin = ctx.saved_tensors
         # in place on the gradient attention's backward just wrote (contiguous() is then a no-op)
-        return _rotate_(dqkv.contiguous(), cos, sin, ctx.heads, True), None, None, None
+        return _rotate_(dqkv.contiguous(), cos, sin, ctx.heads, ctx.kv_heads, True), None, None, None, None
 
 
-def rope_qkv_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, heads: int) -> torch.Tensor:
-    """Rotate Q and K of the packed ``qkv`` [B, T, 3·heads·Dh] in place; returns ``qkv``."""
-    assert qkv.dim() == 3 and qkv.shape[-1] % (3 * heads) == 0, qkv.shape
+def rope_qkv_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, heads: int,
+              kv_heads: int | None = None) -> torch.Tensor:
+    """Rotate Q and K of the packed ``qkv`` [B, T, (heads + 2·kv_heads)·Dh] in place; returns ``qkv``.
+    ``kv_heads`` of ``None`` is ``heads``: the multi-head layout [B, T, 3·heads·Dh]."""
+    kv_heads = heads if kv_heads is None else kv_heads
+    if kv_heads <= 0 or heads % kv_heads != 0:
+        raise ValueError(f"rope_qkv_: heads = {heads} is not a positive multiple of kv_heads = {kv_heads}")
+    if qkv.dim() != 3 or qkv.shape[-1] % (heads + 2 * kv_heads) != 0:
+        raise ValueError(f"rope_qkv_: qkv {tuple(qkv.shape)} is not [B, T, (heads + 2·kv_heads)·Dh] with "
+                         f"heads = {heads}, kv_heads = {kv_heads}")
     if not qkv.is_contiguous():
         raise ValueError("rope_qkv_: qkv must be contiguous (it is rotated in place)")
     if torch.is_grad_enabled() and qkv.requires_grad:
-        return _RopeQKVFn.apply(qkv, cos, sin, heads)
-    return _rotate_(qkv, cos, sin, heads, False)
+        return _RopeQKVFn.apply(qkv, cos, sin, heads, kv_heads)
+    return _rotate_(qkv, cos, sin, heads, kv_heads, False)

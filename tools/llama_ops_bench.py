@@ -99,10 +99,10 @@ def bench_kernels(rounds, iters, emit):
     rope_bytes = 2 * N * 2 * H * 64 * ELT
     emit(_line("rope fwd (in place)", rope_bytes, _alternate(
         {"ours": lambda: nat.rope_qkv(qkv, cos, sin, H, False),
-         "aten": lambda: rope._rotate_reference_(qkv2, cos, sin, H, False)}, rounds, iters)))
+         "aten": lambda: rope._rotate_reference_(qkv2, cos, sin, H, H, False)}, rounds, iters)))
     emit(_line("rope bwd (in place, conj)", rope_bytes, _alternate(
         {"ours": lambda: nat.rope_qkv(qkv, cos, sin, H, True),
-         "aten": lambda: rope._rotate_reference_(qkv2, cos, sin, H, True)}, rounds, iters)))
+         "aten": lambda: rope._rotate_reference_(qkv2, cos, sin, H, H, True)}, rounds, iters)))
     del qkv, qkv2
 
     # ---- SwiGLU on the packed gate/up
