@@ -2386,7 +2386,7 @@ std::vector<Tensor> embedding_bwd(Tensor idx, Tensor dout, int64_t V, int64_t P)
 
 // ---- Linear GEMM with fused epilogues (csrc/kernels/gemm.hip) ----
 // a [M, K], b [N, K] contiguous bf16 -> {C [M, N]} (epi 0: a·bᵀ, 1: a·bᵀ + bias) or {C, G} (epi 2:
-// C = a·bᵀ, G = gelu(C + bias)). bias [N] fp32 or bf16. N % 256 == 0, K % 64 == 0 (gemm_nt_ok).
+// C = a·bᵀ, G = gelu(C + bias)). bias [N] fp32 or bf16. N % 128 == 0, K % 64 == 0 (gemm_nt_ok).
 std::vector<Tensor> gemm_nt(Tensor a, Tensor b, c10::optional<Tensor> bias, int64_t epi, bool tanh_form) {
   check_cuda(a, "a");
   check_cuda(b, "b");
@@ -2443,6 +2443,11 @@ Tensor gemm_nt_fp8(Tensor a, Tensor b, Tensor sa, Tensor sb, c10::optional<Tenso
   TORCH_CHECK(rc == 0, "pdt_gemm_nt_fp8 failed (", rc, ") for M=", M, " N=", N, " K=", K);
   return c;
 }
+
+// Read-only queries (no launch): the tile width (128 / 256; 0 = shape not served) gemm_nt and gemm_nt_fp8 run
+// [M, N] with, and the number of K splits gemm_nt_fp8 takes without a bias.
+int64_t gemm_nt_tile_n(int64_t M, int64_t N) { return pdt_gemm_nt_tile_n((int)M, (int)N); }
+int64_t gemm_nt_fp8_ksplit(int64_t M, int64_t N, int64_t K) { return pdt_gemm_nt_fp8_ksplit((int)M, (int)N, (int)K); }
 
 // ---- LeNet (reference model) ops: csrc/kernels/lenet.hip ----
 constexpr int kStemIpb = 4;  // images per workgroup in the conv1 weight-gradient reduction
@@ -2617,6 +2622,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("embedding_fwd", &embedding_fwd);
   m.def("gemm_nt", &gemm_nt);
   m.def("gemm_nt_fp8", &gemm_nt_fp8, py::arg("a"), py::arg("b"), py::arg("sa"), py::arg("sb"), py::arg("bias") = py::none());
+  m.def("gemm_nt_tile_n", &gemm_nt_tile_n);
+  m.def("gemm_nt_fp8_ksplit", &gemm_nt_fp8_ksplit);
   m.def("embedding_bwd", &embedding_bwd);
   m.def("embedding_err", &embedding_err);
   m.def("conv3x3_wgrad_tune", [](int target_wgs, int co_tile) { pdt_conv3x3_wgrad_tune(target_wgs, co_tile); });

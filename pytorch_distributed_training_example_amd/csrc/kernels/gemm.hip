@@ -31,7 +31,7 @@
 //     up to 1.5 K-steps ahead) sped the load path alone by 20 % but the whole kernel lost 15 %:
 //     the extra DMA lands in the LDS-read-heavy phases. Rejected.
 //   * Rows of A past M are clamped onto row M-1 (valid memory, results never stored), so any M
-//     runs; N % 256 == 0 and K % 64 == 0 (every ViT-B/16 and GPT-2 Linear).
+//     runs; N % 128 == 0 (256 x 128 tiles when N % 256 != 0) and K % 64 == 0.
 //   * Tiles are ordered in groups of 4 A bands (bands fastest, then N tiles) and the block -> tile
 //     map is XCD-aware (xcd_remap): the ~32 tiles resident on one XCD span 4 A bands x 8 B bands
 //     and share both in its L2 (8k^3: 1421 vs 1309 TF for plain N-first order).
@@ -474,6 +474,13 @@ int pdt_gemm_nt(const uint16_t* A, const uint16_t* B, uint16_t* C, uint16_t* G, 
     case EPI_GELU: return launch<EPI_GELU>(A, B, C, G, bias, bias_f32, tanh_form, M, N, K, s);
     default: return -1;
   }
+}
+
+// Read-only query: the tile width (128 or 256) both pdt_gemm_nt and pdt_gemm_nt_fp8 run [M, N] with; 0 when
+// the shape is not served. Launches nothing.
+int pdt_gemm_nt_tile_n(int M, int N) {
+  if (M < 1 || N % 128 != 0 || N < 128) return 0;
+  return pick_bn(M, N);
 }
 
 // fp8 e4m3 operands: C[M, N] bf16 = (A sa)(B sb)^T (+ bias, epi 1) from A [M, K] and B [N, K] row-major e4m3

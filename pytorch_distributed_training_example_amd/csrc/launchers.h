@@ -246,6 +246,7 @@ int pdt_colsum(const void* x, int dtype, int64_t N, int D, void* out, int odtype
 // kernels/gemm.hip
 int pdt_gemm_nt(const uint16_t* A, const uint16_t* B, uint16_t* C, uint16_t* G, const void* bias, int bias_f32,
                 int epi, int tanh_form, int M, int N, int K, hipStream_t s);
+int pdt_gemm_nt_tile_n(int M, int N);
 int pdt_gemm_nt_fp8_ksplit(int M, int N, int K);
 int pdt_gemm_nt_fp8(const uint8_t* A, const uint8_t* B, uint16_t* C, const float* sa, const float* sb,
                     const void* bias, int bias_f32, int epi, int M, int N, int K, float* ws, int ksplit,
