@@ -1301,6 +1301,25 @@ Tensor check_w3x3(const Op& op, const Tensor& w, int64_t Ci) {
   return w.contiguous(at::MemoryFormat::ChannelsLast);
 }
 
+// Which kernel conv3x3s1_fwd (and _fwd_stats / _fwd_bnbwd, where they have the epilogue) runs at this shape
+// under the current conv3x3_opt bits: the launchers' own decision (conv3x3.hip variant_of). Host only.
+const char* conv3x3s1_variant(int64_t N, int64_t H, int64_t W, int64_t Ci, int64_t Co) {
+  static const char* const names[] = {"tap_wide", "tap_narrow", "halo_wide", "halo_narrow", "wst", "wsr"};
+  static_assert(PDT_C3_TAP_WIDE == 0 && PDT_C3_TAP_NARROW == 1 && PDT_C3_HALO_WIDE == 2 && PDT_C3_HALO_NARROW == 3 &&
+                    PDT_C3_WST == 4 && PDT_C3_WSR == 5, "names follow launchers.h");
+  const int v = pdt_conv3x3s1_variant((int)N, (int)H, (int)W, (int)Ci, (int)Co);
+  TORCH_CHECK(v >= 0 && v <= PDT_C3_WSR, "conv3x3s1_variant: shape not taken by conv3x3s1_fwd: ", v);
+  return names[v];
+}
+
+// (R, ntiles, tiles_per_split, nsplit, co_tile) of conv3x3s1_wgrad / conv3x3s2_wgrad at this INPUT shape under
+// the current conv3x3_wgrad_tune setting (conv3x3_wgrad.hip geo_of), or None where the kernel declines. Host only.
+py::object conv3x3_wgrad_geo(int64_t N, int64_t H, int64_t W, int64_t Ci, int64_t Co, int64_t stride) {
+  int g[5];
+  if (!pdt_conv3x3_wgrad_geo((int)N, (int)H, (int)W, (int)Ci, (int)Co, (int)stride, g)) return py::none();
+  return py::make_tuple(g[0], g[1], g[2], g[3], g[4]);
+}
+
 // y = conv2d(x, w, stride=1, padding=1) for channels_last bf16 x [N,Ci,H,W] and w [Co,Ci,3,3].
 Tensor conv3x3s1_fwd(Tensor x, Tensor w) {
   const Op op("conv3x3s1_fwd", x);
@@ -2594,6 +2613,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_fwd_train_tiles", &bn_fwd_train_tiles, py::arg("x"), py::arg("part"), py::arg("res"), py::arg("weight"),
         py::arg("bias"), py::arg("running_mean"), py::arg("running_var"), py::arg("momentum"), py::arg("eps"),
         py::arg("relu"), py::arg("res_ab") = py::none(), py::arg("apply") = true, py::arg("sub") = 0);
+  m.def("conv3x3s1_variant", &conv3x3s1_variant);
+  m.def("conv3x3_wgrad_geo", &conv3x3_wgrad_geo);
   m.def("conv3x3s1_fwd", &conv3x3s1_fwd);
   m.def("conv3x3s1_fwd_stats", &conv3x3s1_fwd_stats);
   m.def("conv3x3s1_fwd_bnbwd", &conv3x3s1_fwd_bnbwd);

@@ -1476,77 +1476,104 @@ inline bool h_wide(int64_t M, int Co) { return Co % 128 == 0 && !small_grid_narr
 using CfWide = Cfg<256, 128, 4, 2, 32>;   // Co % 128 == 0: 8 waves of 64x64, 72 KB LDS -> 2 WG/CU
 using CfNarrow = Cfg<256, 64, 4, 1, 32>;  // Co == 64: 4 waves of 64x64, 60 KB LDS
 
+// Shapes the stride-1 entries take: 0, or the error they return.
+inline int check_shape(int N, int H, int W, int Ci, int Co) {
+  if (Ci % 32 != 0 || Co % 64 != 0 || N < 1 || H < 1 || W < 1) return -1;
+  const int64_t M = (int64_t)N * H * W;
+  if (M * (Ci > Co ? Ci : Co) >= (int64_t)1 << 31 || (int64_t)Co * 9 * Ci >= (int64_t)1 << 31) return -2;
+  return 0;
+}
+
+// THE dispatch decision of the stride-1 forward (a PDT_C3_* of launchers.h), under the current conv3x3_opt bits
+// and PDT_SMALL_GRID_NARROW; pdt_conv3x3s1_fwd, _fwd_stats, _fwd_bnbwd and the pdt_conv3x3s1_variant query all
+// go through it. Row-tile kernel where it applies; 64 -> 64 channels: weight-stationary; otherwise the halo
+// kernel, 128 channels wide unless the grid would leave CUs idle; a halo larger than the chosen kernel's LDS
+// buffer (tiny W): per-tap staging, wide where Co % 128 == 0.
+inline int variant_of(int N, int H, int W, int Ci, int Co) {
+  if (wsr_applies(N, H, W, Ci, Co)) return PDT_C3_WSR;
+  if (Ci == 64 && Co == 64) {
+    using Cf = SCfg<64, 64>;
+    if (halo_rows_bound(H, W, Cf::BM) <= Cf::kHaloRows) return PDT_C3_WST;
+  } else if (halo_rows_bound(H, W, HWide::BM) <= HWide::kHaloRows) {
+    static_assert(HWide::BM == HNarrow::BM && HWide::kHaloRows == HNarrow::kHaloRows, "one halo bound");
+    return h_wide((int64_t)N * H * W, Co) ? PDT_C3_HALO_WIDE : PDT_C3_HALO_NARROW;
+  }
+  return Co % 128 == 0 ? PDT_C3_TAP_WIDE : PDT_C3_TAP_NARROW;
+}
+
 }  // namespace
 
 extern "C" {
+
+// The kernel pdt_conv3x3s1_fwd runs at this shape (PDT_C3_*), or its error code (< 0). Host only.
+int pdt_conv3x3s1_variant(int N, int H, int W, int Ci, int Co) {
+  const int rc = check_shape(N, H, W, Ci, Co);
+  return rc ? rc : variant_of(N, H, W, Ci, Co);
+}
 
 // y[N,H,W,Co] = conv3x3(x[N,H,W,Ci], w[Co,3,3,Ci]), stride 1, padding 1 (all NHWC / channels_last
 // bf16). Ci % 64 == 0, Co % 64 == 0, N*H*W*max(Ci,Co) < 2^31. Returns 0 on success.
 int pdt_conv3x3s1_fwd(const uint16_t* x, const uint16_t* w, uint16_t* y, int N, int H, int W, int Ci, int Co,
                       hipStream_t s) {
-  if (Ci % 32 != 0 || Co % 64 != 0 || N < 1 || H < 1 || W < 1) return -1;
-  const int64_t M = (int64_t)N * H * W;
-  if (M * (Ci > Co ? Ci : Co) >= (int64_t)1 << 31 || (int64_t)Co * 9 * Ci >= (int64_t)1 << 31) return -2;
+  if (const int rc = check_shape(N, H, W, Ci, Co)) return rc;
 #ifdef PDT_CONV_CFG_OVERRIDE
   return PDT_CONV_LAUNCH<PDT_CONV_CFG_OVERRIDE>(x, w, y, N, H, W, Ci, Co, s);
 #endif
-  int rc = -1;
-  if (wsr_applies(N, H, W, Ci, Co)) return launch_wsr<false>(x, w, y, N, H, s);
-  if (Ci == 64 && Co == 64) rc = launch_wst<SCfg<64, 64>>(x, w, y, N, H, W, Ci, Co, s);
-  if (rc == -1) rc = h_wide(M, Co) ? launch_h<HWide>(x, w, y, N, H, W, Ci, Co, s) : launch_h<HNarrow>(x, w, y, N, H, W, Ci, Co, s);
-  if (rc != -4) return rc;
-  // halo larger than the LDS buffer (tiny W): per-tap staging
-  if (Co % 128 == 0) return launch<CfWide>(x, w, y, N, H, W, Ci, Co, s);
-  return launch<CfNarrow>(x, w, y, N, H, W, Ci, Co, s);
+  switch (variant_of(N, H, W, Ci, Co)) {
+    case PDT_C3_WSR: return launch_wsr<false>(x, w, y, N, H, s);
+    case PDT_C3_WST: return launch_wst<SCfg<64, 64>>(x, w, y, N, H, W, Ci, Co, s);
+    case PDT_C3_HALO_WIDE: return launch_h<HWide>(x, w, y, N, H, W, Ci, Co, s);
+    case PDT_C3_HALO_NARROW: return launch_h<HNarrow>(x, w, y, N, H, W, Ci, Co, s);
+    case PDT_C3_TAP_WIDE: return launch<CfWide>(x, w, y, N, H, W, Ci, Co, s);
+    default: return launch<CfNarrow>(x, w, y, N, H, W, Ci, Co, s);
+  }
 }
 
 // Rows per statistics tile of pdt_conv3x3s1_fwd_stats at this shape: 224 where the row-tile kernel runs
 // (part then has M / 224 tiles), else 256.
 int pdt_conv3x3s1_stats_tile_rows(int N, int H, int W, int Ci, int Co) {
-  return wsr_applies(N, H, W, Ci, Co) ? RCfg56::BM : 256;
+  return variant_of(N, H, W, Ci, Co) == PDT_C3_WSR ? RCfg56::BM : 256;
 }
 
 // Same for the backward reduction of pdt_conv3x3s1_fwd_bnbwd.
 int pdt_conv3x3s1_bnbwd_tile_rows(int N, int H, int W, int Ci, int Co) {
-  return wsr_applies(N, H, W, Ci, Co) && (conv3x3_opt() & 128) ? RCfg56::BM : 256;
+  return variant_of(N, H, W, Ci, Co) == PDT_C3_WSR && (conv3x3_opt() & 128) ? RCfg56::BM : 256;
 }
 
 // Forward + per-tile BatchNorm statistics of y into part ([2][T][Co] fp32, tile_stats.h; tiles of
 // pdt_conv3x3s1_stats_tile_rows rows).
-// The halo and weight-stationary (64 -> 64) kernels have the statistics epilogue: returns -5 where
+// The halo, weight-stationary (64 -> 64) and row-tile kernels have the statistics epilogue: returns -5 where
 // another kernel would run (tiny W: per-tap staging) — caller falls back.
 int pdt_conv3x3s1_fwd_stats(const uint16_t* x, const uint16_t* w, uint16_t* y, float* part, int N, int H, int W,
                             int Ci, int Co, hipStream_t s) {
-  if (Ci % 32 != 0 || Co % 64 != 0 || N < 1 || H < 1 || W < 1) return -1;
-  const int64_t M = (int64_t)N * H * W;
-  if (M * (Ci > Co ? Ci : Co) >= (int64_t)1 << 31 || (int64_t)Co * 9 * Ci >= (int64_t)1 << 31) return -2;
-  if (wsr_applies(N, H, W, Ci, Co)) return launch_wsr<true>(x, w, y, N, H, s, part);  // 224-row tiles
-  if (Ci == 64 && Co == 64) {
-    const int rc = launch_wst<SCfg<64, 64>, true>(x, w, y, N, H, W, Ci, Co, s, part);
-    return rc == -4 ? -5 : rc;
+  if (const int rc = check_shape(N, H, W, Ci, Co)) return rc;
+  switch (variant_of(N, H, W, Ci, Co)) {
+    case PDT_C3_WSR: return launch_wsr<true>(x, w, y, N, H, s, part);  // 224-row tiles
+    case PDT_C3_WST: return launch_wst<SCfg<64, 64>, true>(x, w, y, N, H, W, Ci, Co, s, part);
+    case PDT_C3_HALO_WIDE: return launch_h<HWide, true>(x, w, y, N, H, W, Ci, Co, s, part);
+    case PDT_C3_HALO_NARROW: return launch_h<HNarrow, true>(x, w, y, N, H, W, Ci, Co, s, part);
+    default: return -5;
   }
-  if (halo_rows_bound(H, W, 256) > 512) return -5;
-  return h_wide(M, Co) ? launch_h<HWide, true>(x, w, y, N, H, W, Ci, Co, s, part)
-                       : launch_h<HNarrow, true>(x, w, y, N, H, W, Ci, Co, s, part);
 }
 
 // Data gradient y = conv3x3(dy, flipped w) whose output y is the gradient at a BatchNorm's output
 // (input bn_x [N,H,W,Co] bf16, ReLU bit-mask bn_mask or null, batch mean bn_mean [Co]): also writes
-// that BatchNorm's backward per-tile partials bn_part [2][T][Co] (tile_stats.h). Halo kernel only:
-// returns -5 where another kernel would run (caller falls back to a plain launch + reduce pass).
+// that BatchNorm's backward per-tile partials bn_part [2][T][Co] (tile_stats.h). Halo kernel, and the
+// row-tile kernel under opt bit 7: returns -5 where another kernel would run (caller falls back to a plain
+// launch + reduce pass; the 256-pixel weight-stationary kernel's reduction did not pay).
 int pdt_conv3x3s1_fwd_bnbwd(const uint16_t* x, const uint16_t* w, uint16_t* y, const uint16_t* bn_x,
                             const uint8_t* bn_mask, const float* bn_mean, float* bn_part, int N, int H, int W, int Ci,
                             int Co, hipStream_t s) {
-  if (Ci % 32 != 0 || Co % 64 != 0 || N < 1 || H < 1 || W < 1 || !bn_x || !bn_mean || !bn_part) return -1;
-  const int64_t M = (int64_t)N * H * W;
-  if (M * (Ci > Co ? Ci : Co) >= (int64_t)1 << 31 || (int64_t)Co * 9 * Ci >= (int64_t)1 << 31) return -2;
+  if (!bn_x || !bn_mean || !bn_part) return -1;
+  if (const int rc = check_shape(N, H, W, Ci, Co)) return rc;
   const BnSrc bs{bn_x, bn_mask, bn_mean, bn_part};
-  // the row-tile kernel takes it (224-row tiles); the 256-pixel weight-stationary one's reduction did not pay
-  if (wsr_applies(N, H, W, Ci, Co) && (conv3x3_opt() & 128)) return launch_wsr<false, true>(x, w, y, N, H, s, nullptr, bs);
-  if (Ci == 64 && Co == 64) return -5;
-  if (halo_rows_bound(H, W, 256) > 512) return -5;
-  return h_wide(M, Co) ? launch_h<HWide, false, true>(x, w, y, N, H, W, Ci, Co, s, nullptr, bs)
-                       : launch_h<HNarrow, false, true>(x, w, y, N, H, W, Ci, Co, s, nullptr, bs);
+  switch (variant_of(N, H, W, Ci, Co)) {
+    case PDT_C3_WSR:  // 224-row tiles
+      return (conv3x3_opt() & 128) ? launch_wsr<false, true>(x, w, y, N, H, s, nullptr, bs) : -5;
+    case PDT_C3_HALO_WIDE: return launch_h<HWide, false, true>(x, w, y, N, H, W, Ci, Co, s, nullptr, bs);
+    case PDT_C3_HALO_NARROW: return launch_h<HNarrow, false, true>(x, w, y, N, H, W, Ci, Co, s, nullptr, bs);
+    default: return -5;
+  }
 }
 
 // Set the 3x3 variant bits (conv3x3_opt); -1 re-reads PDT_CONV3X3_OPT. Returns the previous value.

@@ -459,17 +459,36 @@ int launch_pitch(const uint16_t* x, const uint16_t* dy, uint16_t* dw, float* ws,
   }
 }
 
+inline int s2_co_tile(int Co) { return (g_co_tile == 64 || Co % 128 != 0) ? 64 : 128; }
+
+// Shape checks, channel tile and tile / split geometry of the weight gradient at stride S (H, W: the INPUT
+// size), under the current pdt_conv3x3_wgrad_tune setting: what the workspace size, the launch and the
+// pdt_conv3x3_wgrad_geo query all use. 0, or < 0 for a shape the kernel declines (-4: no tile geometry).
+inline int plan(int N, int H, int W, int Ci, int Co, int S, Geo& g, int& co_t) {
+  const int lo = S == 1 ? 1 : 2;
+  if (Ci % 64 != 0 || Co % 64 != 0 || N < 1 || H < lo || W < lo) return -1;
+  if ((int64_t)N * H * W * (Ci > Co ? Ci : Co) >= (int64_t)1 << 31) return -2;  // 32-bit buffer offsets
+  co_t = S == 1 ? co_tile_of(Co) : s2_co_tile(Co);
+  const bool ok = S == 1 ? geo_of(N, H, W, Ci, Co, co_t, target_wgs(co_t), g)
+                         : geo_of(N, (H - 1) / 2 + 1, (W - 1) / 2 + 1, Ci, Co, co_t, target_wgs(co_t), g, 2, H, W);
+  return ok ? 0 : -4;
+}
+
+inline int64_t ws_floats(int N, int H, int W, int Ci, int Co, int S, int* nsplit_out) {
+  Geo g;
+  int co_t = 0;
+  if (plan(N, H, W, Ci, Co, S, g, co_t) != 0) return 0;
+  if (nsplit_out) *nsplit_out = g.nsplit;
+  return (int64_t)g.nsplit * 9 * Co * Ci;
+}
+
 }  // namespace
 
 extern "C" {
 
 // fp32 workspace floats for pdt_conv3x3s1_wgrad at this shape (0: unsupported shape).
 int64_t pdt_conv3x3_wgrad_ws_floats(int N, int H, int W, int Ci, int Co, int* nsplit_out) {
-  Geo g;
-  const int co_t = co_tile_of(Co);
-  if (Ci % 64 != 0 || Co % 64 != 0 || !geo_of(N, H, W, Ci, Co, co_t, target_wgs(co_t), g)) return 0;
-  if (nsplit_out) *nsplit_out = g.nsplit;
-  return (int64_t)g.nsplit * 9 * Co * Ci;
+  return ws_floats(N, H, W, Ci, Co, 1, nsplit_out);
 }
 
 // dw[Co,3,3,Ci] (bf16, channels_last weight storage) of the stride-1 pad-1 3x3 conv from
@@ -477,36 +496,35 @@ int64_t pdt_conv3x3_wgrad_ws_floats(int N, int H, int W, int Ci, int Co, int* ns
 // Returns 0, or < 0 for an unsupported shape (caller falls back).
 int pdt_conv3x3s1_wgrad(const uint16_t* x, const uint16_t* dy, uint16_t* dw, float* ws, int N, int H, int W, int Ci,
                         int Co, hipStream_t s) {
-  if (Ci % 64 != 0 || Co % 64 != 0 || N < 1 || H < 1 || W < 1) return -1;
-  if ((int64_t)N * H * W * (Ci > Co ? Ci : Co) >= (int64_t)1 << 31) return -2;  // 32-bit buffer offsets
   Geo g;
-  const int co_t = co_tile_of(Co);
-  if (!geo_of(N, H, W, Ci, Co, co_t, target_wgs(co_t), g)) return -4;
+  int co_t = 0;
+  if (const int rc = plan(N, H, W, Ci, Co, 1, g, co_t)) return rc;
   return co_t == 128 ? launch_pitch<128, true, 1>(x, dy, dw, ws, g, s) : launch_pitch<64, false, 1>(x, dy, dw, ws, g, s);
 }
 
 // Stride 2 / pad 1 (input x [N,H,W,Ci], dy [N,Ho,Wo,Co], Ho = (H-1)/2+1), Ci % 64 == 0, Co % 64 == 0.
 // CO_T 128 (one 8-wave workgroup per CU, next tile prefetched in registers) unless forced to 64
 // (pdt_conv3x3_wgrad_tune) or Co % 128 != 0: 4 waves, 2 workgroups per CU, synchronous staging.
-inline int s2_co_tile(int Co) { return (g_co_tile == 64 || Co % 128 != 0) ? 64 : 128; }
-
 int64_t pdt_conv3x3s2_wgrad_ws_floats(int N, int H, int W, int Ci, int Co, int* nsplit_out) {
-  Geo g;
-  if (Ci % 64 != 0 || Co % 64 != 0 || H < 2 || W < 2) return 0;
-  const int co_t = s2_co_tile(Co);
-  if (!geo_of(N, (H - 1) / 2 + 1, (W - 1) / 2 + 1, Ci, Co, co_t, target_wgs(co_t), g, 2, H, W)) return 0;
-  if (nsplit_out) *nsplit_out = g.nsplit;
-  return (int64_t)g.nsplit * 9 * Co * Ci;
+  return ws_floats(N, H, W, Ci, Co, 2, nsplit_out);
 }
 
 int pdt_conv3x3s2_wgrad(const uint16_t* x, const uint16_t* dy, uint16_t* dw, float* ws, int N, int H, int W, int Ci,
                         int Co, hipStream_t s) {
-  if (Ci % 64 != 0 || Co % 64 != 0 || N < 1 || H < 2 || W < 2) return -1;
-  if ((int64_t)N * H * W * (Ci > Co ? Ci : Co) >= (int64_t)1 << 31) return -2;  // 32-bit buffer offsets
   Geo g;
-  const int co_t = s2_co_tile(Co);
-  if (!geo_of(N, (H - 1) / 2 + 1, (W - 1) / 2 + 1, Ci, Co, co_t, target_wgs(co_t), g, 2, H, W)) return -4;
+  int co_t = 0;
+  if (const int rc = plan(N, H, W, Ci, Co, 2, g, co_t)) return rc;
   return co_t == 128 ? launch_pitch<128, true, 2>(x, dy, dw, ws, g, s) : launch_pitch<64, false, 2>(x, dy, dw, ws, g, s);
+}
+
+// (R, ntiles, tiles_per_split, nsplit, co_tile) of the launch at this shape and stride into geo5; returns 1, or
+// 0 where pdt_conv3x3s{1,2}_wgrad declines the shape. Host only.
+int pdt_conv3x3_wgrad_geo(int N, int H, int W, int Ci, int Co, int stride, int* geo5) {
+  Geo g;
+  int co_t = 0;
+  if ((stride != 1 && stride != 2) || plan(N, H, W, Ci, Co, stride, g, co_t) != 0) return 0;
+  geo5[0] = g.R; geo5[1] = g.ntiles; geo5[2] = g.tiles_per_split; geo5[3] = g.nsplit; geo5[4] = co_t;
+  return 1;
 }
 
 void pdt_conv3x3_wgrad_probe(int probe) { g_probe = probe; }

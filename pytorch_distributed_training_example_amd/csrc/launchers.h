@@ -160,6 +160,10 @@ int pdt_conv1x1_wgrad_seg(const uint16_t* x, const uint16_t* dy1, int co1, const
 void pdt_conv1x1_wgrad_tune(int target_wgs, int variant, int interleave);
 
 // kernels/conv3x3.hip
+// the stride-1 forward kernels, as pdt_conv3x3s1_variant names them: per-tap staging (128 / 64 channels wide),
+// halo staging (128 / 64), weight-stationary 64 -> 64, row-tile 64 -> 64 at W = 56
+enum { PDT_C3_TAP_WIDE = 0, PDT_C3_TAP_NARROW, PDT_C3_HALO_WIDE, PDT_C3_HALO_NARROW, PDT_C3_WST, PDT_C3_WSR };
+int pdt_conv3x3s1_variant(int N, int H, int W, int Ci, int Co);
 int pdt_conv3x3s1_fwd(const uint16_t* x, const uint16_t* w, uint16_t* y, int N, int H, int W, int Ci, int Co,
                       hipStream_t s);
 int pdt_conv3x3s1_stats_tile_rows(int N, int H, int W, int Ci, int Co);
@@ -188,6 +192,7 @@ int pdt_conv3x3s1_wgrad(const uint16_t* x, const uint16_t* dy, uint16_t* dw, flo
 int64_t pdt_conv3x3s2_wgrad_ws_floats(int N, int H, int W, int Ci, int Co, int* nsplit_out);
 int pdt_conv3x3s2_wgrad(const uint16_t* x, const uint16_t* dy, uint16_t* dw, float* ws, int N, int H, int W, int Ci,
                         int Co, hipStream_t s);
+int pdt_conv3x3_wgrad_geo(int N, int H, int W, int Ci, int Co, int stride, int* geo5);
 void pdt_conv3x3_wgrad_probe(int probe);
 void pdt_conv3x3_wgrad_tune(int target_wgs, int co_tile);
 
