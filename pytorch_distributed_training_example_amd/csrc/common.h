@@ -94,6 +94,27 @@ __device__ __forceinline__ void st8_bf16(uint16_t* p, const float (&v)[8]) {
   *reinterpret_cast<uint4*>(p) = t;
 }
 
+// 8 consecutive elements <-> 8 floats (16 B for bf16, 2 x 16 B for fp32).
+template <typename T> struct Vec8;
+template <> struct Vec8<uint16_t> {
+  __device__ __forceinline__ static void ld(const uint16_t* p, float (&v)[8]) { ld8_bf16(p, v); }
+  __device__ __forceinline__ static void st(uint16_t* p, const float (&v)[8]) { st8_bf16(p, v); }
+};
+template <> struct Vec8<float> {
+  __device__ __forceinline__ static void ld(const float* p, float (&v)[8]) {
+    const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+  }
+  __device__ __forceinline__ static void st(float* p, const float (&v)[8]) {
+    reinterpret_cast<float4*>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
+    reinterpret_cast<float4*>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
+  }
+};
+
+// v as storage type T would hold it: fp32 unchanged, bf16 rounded to nearest-even.
+template <typename T> __device__ __forceinline__ float round_to(float v) { return v; }
+template <> __device__ __forceinline__ float round_to<uint16_t>(float v) { return bf2f(f2bf(v)); }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -15,7 +15,10 @@
 //     workspace holds every split's partials, and the DMA source swizzle is a permutation of each
 //     LDS row's chunks (every staged byte lands exactly once);
 //   * batchnorm.hip reduce_geo3: the row blocks tile M exactly;
-//   * embedding.hip workspace arithmetic.
+//   * embedding.hip workspace arithmetic;
+//   * dispatch.h row_blocks: no workgroup for an empty input (the LayerNorm / RMSNorm backward once divided
+//     by zero there), otherwise the blocks tile N exactly and match the closed form; with_k / with_elem
+//     pick exactly the listed instantiation.
 // Build + run: python -m pytorch_distributed_training_example_amd._build --host-selftest
 // (tests/test_host_asan.py does this on every CPU test run).
 #include "../kernels/conv3x3_wgrad.hip"
@@ -25,6 +28,7 @@
 #include <random>
 #include <vector>
 
+#include "../dispatch.h"
 #include "../multi_tensor.h"
 
 namespace bn {
@@ -167,7 +171,68 @@ static void test_bn_geometry() {
       }
 }
 
+static void test_row_blocks() {
+  const auto ceil_div = [](int64_t a, int64_t b) { return a / b + (a % b != 0); };
+  const int64_t pairs[][2] = {{32, 512}, {4, 64}, {256, 4096}, {64, 1024}, {64, 256}};
+  std::vector<int64_t> Ns;
+  for (int64_t N = 0; N <= 20000; ++N) Ns.push_back(N);
+  for (int64_t N : {25216LL, 100000LL, 3211264LL}) Ns.push_back(N);
+  for (const auto& p : pairs) {
+    const int64_t min_rows = p[0], max_blocks = p[1];
+    for (int64_t N : Ns) {
+      int rpb = -1;
+      const int nblk = pdt::row_blocks(N, min_rows, max_blocks, rpb);
+      if (N == 0) {
+        EXPECT(nblk == 0 && rpb == 0, "empty input: %d blocks of %d rows", nblk, rpb);
+        continue;
+      }
+      EXPECT(nblk >= 1 && nblk <= max_blocks, "N=%lld: %d blocks", (long long)N, nblk);
+      EXPECT((int64_t)nblk * rpb >= N && (int64_t)(nblk - 1) * rpb < N, "N=%lld: %d blocks of %d rows", (long long)N,
+             nblk, rpb);
+      // closed form: as many blocks as min_rows allows, capped; rows evened out; empty tail blocks dropped
+      const int64_t want_rpb = ceil_div(N, std::min(max_blocks, ceil_div(N, min_rows)));
+      EXPECT(rpb == want_rpb && nblk == ceil_div(N, want_rpb), "N=%lld (%lld, %lld): %d x %d, want %lld x %lld",
+             (long long)N, (long long)min_rows, (long long)max_blocks, nblk, rpb, (long long)ceil_div(N, want_rpb),
+             (long long)want_rpb);
+    }
+  }
+  int rpb = -1;
+  EXPECT(pdt::row_blocks(-5, 32, 512, rpb) == 0 && rpb == 0, "negative N");
+}
+
+static void test_with_k_and_elem() {
+  for (int k = 0; k <= 17; ++k) {
+    int calls = 0, got = -1;
+    const bool ok = pdt::with_k<1, 2, 3, 4, 5, 6, 8, 10, 12, 16>(k, [&](auto kc) {
+      ++calls;
+      got = decltype(kc)::value;
+    });
+    const bool listed = (k >= 1 && k <= 6) || k == 8 || k == 10 || k == 12 || k == 16;
+    EXPECT(ok == listed && calls == (listed ? 1 : 0) && (!listed || got == k), "with_k(%d): ok %d calls %d K %d", k,
+           (int)ok, calls, got);
+  }
+  for (int k : {0, 1, 7, 8, 9, 17}) {  // the fp8 list: neither end is listed
+    int calls = 0;
+    const bool ok = pdt::with_k<2, 3, 4, 5, 6>(k, [&](auto) { ++calls; });
+    EXPECT(!ok && calls == 0, "with_k<2..6>(%d)", k);
+  }
+  for (int dtype : {0, 1}) {
+    int calls = 0;
+    bool is_float = false, is_u16 = false;
+    pdt::with_elem(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      ++calls;
+      is_float = std::is_same<T, float>::value;
+      is_u16 = std::is_same<T, uint16_t>::value;
+    });
+    EXPECT(calls == 1 && is_float == (dtype == 0) && is_u16 == (dtype == 1), "with_elem(%d): calls %d float %d u16 %d",
+           dtype, calls, (int)is_float, (int)is_u16);
+  }
+}
+
 int main() {
+  test_row_blocks();
+  test_with_k_and_elem();
   std::mt19937_64 rng(12345);
   test_mt_batches(rng);
   test_wgrad_geometry();

@@ -8,6 +8,7 @@
 //   dropout_mask_*        the bool mask itself, through the same device functions the fused kernels
 //                         (layernorm.hip, attention.hip) inline: what the tests compare with the CPU.
 #include "../common.h"
+#include "../dispatch.h"
 #include "../launchers.h"
 #include "../philox.h"
 
@@ -110,12 +111,10 @@ int pdt_dropout(const void* x, void* y, int dtype, int64_t n, const int64_t* tic
   if (n == 0) return 0;
   const int64_t nblk = (n + 15) / 16;
   const dim3 grid((unsigned)((nblk + 255) / 256));
-  if (dtype == 0)
-    hipLaunchKernelGGL(dropout_kernel<float>, grid, dim3(256), 0, s, (const float*)x, (float*)y, n, ticket, stream,
-                       thr);
-  else
-    hipLaunchKernelGGL(dropout_kernel<uint16_t>, grid, dim3(256), 0, s, (const uint16_t*)x, (uint16_t*)y, n, ticket,
-                       stream, thr);
+  with_elem(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(dropout_kernel<T>, grid, dim3(256), 0, s, (const T*)x, (T*)y, n, ticket, stream, thr);
+  });
   return 0;
 }
 

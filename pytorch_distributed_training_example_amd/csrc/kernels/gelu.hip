@@ -6,6 +6,8 @@
 // fixed order) and reduced by a small finalize kernel. The same column-strip kernel without the
 // GELU part is the bias gradient of every Linear layer (pdt_colsum, ops/linear.py).
 #include "../common.h"
+#include "../colsum_finalize.h"
+#include "../dispatch.h"
 #include "../launchers.h"
 #include "../gelu_math.h"
 
@@ -32,23 +34,6 @@ __global__ __launch_bounds__(256) void bias_gelu_fwd_kernel(const T* __restrict_
     Vec4<T>::st(y, i * 4, v);
   }
 }
-
-// 8 consecutive elements <-> 8 floats (16 B for bf16, 2 x 16 B for fp32).
-template <typename T> struct Vec8;
-template <> struct Vec8<uint16_t> {
-  __device__ __forceinline__ static void ld(const uint16_t* p, float (&v)[8]) { ld8_bf16(p, v); }
-  __device__ __forceinline__ static void st(uint16_t* p, const float (&v)[8]) { st8_bf16(p, v); }
-};
-template <> struct Vec8<float> {
-  __device__ __forceinline__ static void ld(const float* p, float (&v)[8]) {
-    const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  }
-  __device__ __forceinline__ static void st(float* p, const float (&v)[8]) {
-    reinterpret_cast<float4*>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
-    reinterpret_cast<float4*>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
-  }
-};
 
 // Column-strip kernel for [N, D] row-major tensors (D % 8 == 0):
 //   blockIdx.x = 512-column strip (a wave covers it with 8 columns per lane, 16-byte accesses),
@@ -180,41 +165,12 @@ __global__ __launch_bounds__(256) void gelu_fwd_strip_kernel(const T* __restrict
   }
 }
 
-// Fixed-order column sums of the per-chunk partials: 16 columns x 16 chunk-groups per workgroup.
-template <typename TO>
-__global__ __launch_bounds__(256) void colsum_finalize_kernel(const float* __restrict__ part, int nblk, int D,
-                                                              TO* __restrict__ out) {
-  __shared__ float red[16][17];
-  const int grp = threadIdx.x >> 4, cl = threadIdx.x & 15;
-  const int c = blockIdx.x * 16 + cl;
-  float a = 0.f;
-  if (c < D)
-    for (int blk = grp; blk < nblk; blk += 16) a += part[(int64_t)blk * D + c];
-  red[grp][cl] = a;
-  __syncthreads();
-  if (grp == 0 && c < D) {
-    float s = 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) s += red[q][cl];
-    Elt<TO>::st(out, c, s);
-  }
-}
-
 // Row chunks so that strips x chunks ~ 1024 workgroups (4 waves/CU, 2 rows in flight each) with
 // >= 64 rows per chunk: enough bytes in flight to stream at HBM rate while keeping the partial
 // slab (and its fixed-order finalize) small.
 inline int strip_chunks(int64_t N, int D, int& rpc) {
-  if (N <= 0) {
-    rpc = 0;
-    return 0;
-  }
   const int strips = (D + kStrip - 1) / kStrip;
-  int64_t nchunk = 1024 / strips;
-  const int64_t by_rows = (N + 63) / 64;
-  if (nchunk > by_rows) nchunk = by_rows;
-  if (nchunk < 1) nchunk = 1;
-  rpc = (int)((N + nchunk - 1) / nchunk);
-  return (int)((N + rpc - 1) / rpc);
+  return row_blocks(N, 64, strips > 0 ? 1024 / strips : 1, rpc);
 }
 
 template <typename T, bool GELU>
@@ -243,12 +199,11 @@ int pdt_bias_gelu_fwd(const void* x, int dtype, const void* bias, void* y, int64
     int rpc;
     const int nchunk = strip_chunks(N, D, rpc);
     const dim3 grid((D + kStrip - 1) / kStrip, nchunk);
-    if (dtype == 0)
-      hipLaunchKernelGGL(gelu_fwd_strip_kernel<float>, grid, dim3(256), 0, s, (const float*)x, bias, (float*)y, N, D,
-                         rpc, tanh_form, bias_bf16);
-    else
-      hipLaunchKernelGGL(gelu_fwd_strip_kernel<uint16_t>, grid, dim3(256), 0, s, (const uint16_t*)x, bias,
-                         (uint16_t*)y, N, D, rpc, tanh_form, bias_bf16);
+    with_elem(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      hipLaunchKernelGGL(gelu_fwd_strip_kernel<T>, grid, dim3(256), 0, s, (const T*)x, bias, (T*)y, N, D, rpc,
+                         tanh_form, bias_bf16);
+    });
     return 0;
   }
   if (D % 4 != 0 || bias_bf16) return -1;
@@ -256,12 +211,22 @@ int pdt_bias_gelu_fwd(const void* x, int dtype, const void* bias, void* y, int64
   if (nvec == 0) return 0;
   int64_t grid = (nvec + 255) / 256;
   if (grid > 2048) grid = 2048;
-  if (dtype == 0)
-    hipLaunchKernelGGL(bias_gelu_fwd_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)x, (const float*)bias,
-                       (float*)y, nvec, D, tanh_form);
-  else
-    hipLaunchKernelGGL(bias_gelu_fwd_kernel<uint16_t>, dim3(grid), dim3(256), 0, s, (const uint16_t*)x,
-                       (const float*)bias, (uint16_t*)y, nvec, D, tanh_form);
+  with_elem(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(bias_gelu_fwd_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)x, (const float*)bias, (T*)y,
+                       nvec, D, tanh_form);
+  });
+  return 0;
+}
+
+// Fixed-order sum of nblk per-chunk column partials [nblk, D] fp32 into out (odtype 0 fp32, 1 bf16).
+int pdt_colsum_finalize(const float* part, int nblk, int D, void* out, int odtype, hipStream_t s) {
+  if (D <= 0) return 0;
+  with_elem(odtype, [&](auto t) {
+    using TO = typename decltype(t)::type;
+    hipLaunchKernelGGL((colsum_finalize_kernel<1, TO>), dim3((D + 15) / 16), dim3(256), 0, s, part, nblk, D, (TO*)out,
+                       (TO*)nullptr);
+  });
   return 0;
 }
 
@@ -272,51 +237,24 @@ int pdt_bias_gelu_bwd(const void* dy, const void* x, int dtype, const void* bias
   if (N == 0) return 0;
   float* part = dbias ? ws : nullptr;
   int nchunk;
-  if (dtype == 0)
-    launch_strip<float, true>((const float*)dy, (const float*)x, bias, (float*)dx, part, N, D, tanh_form, nchunk, s,
-                              bias_bf16);
-  else
-    launch_strip<uint16_t, true>((const uint16_t*)dy, (const uint16_t*)x, bias, (uint16_t*)dx, part, N, D,
-                                 tanh_form, nchunk, s, bias_bf16);
-  if (dbias && bias_bf16)
-    hipLaunchKernelGGL(colsum_finalize_kernel<uint16_t>, dim3((D + 15) / 16), dim3(256), 0, s, ws, nchunk, D,
-                       (uint16_t*)dbias);
-  else if (dbias)
-    hipLaunchKernelGGL(colsum_finalize_kernel<float>, dim3((D + 15) / 16), dim3(256), 0, s, ws, nchunk, D,
-                       (float*)dbias);
-  return 0;
-}
-
-// Fixed-order sum of nblk per-chunk column partials [nblk, D] fp32 into out (odtype 0 fp32, 1 bf16).
-int pdt_colsum_finalize(const float* part, int nblk, int D, void* out, int odtype, hipStream_t s) {
-  if (D <= 0) return 0;
-  if (odtype == 0)
-    hipLaunchKernelGGL(colsum_finalize_kernel<float>, dim3((D + 15) / 16), dim3(256), 0, s, part, nblk, D, (float*)out);
-  else
-    hipLaunchKernelGGL(colsum_finalize_kernel<uint16_t>, dim3((D + 15) / 16), dim3(256), 0, s, part, nblk, D,
-                       (uint16_t*)out);
+  with_elem(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    launch_strip<T, true>((const T*)dy, (const T*)x, bias, (T*)dx, part, N, D, tanh_form, nchunk, s, bias_bf16);
+  });
+  if (dbias) pdt_colsum_finalize(ws, nchunk, D, dbias, bias_bf16 ? 1 : 0, s);
   return 0;
 }
 
 // Column sum of a [N, D] tensor (a Linear layer's bias gradient) into `out` (fp32 or bf16, odtype).
 int pdt_colsum(const void* x, int dtype, int64_t N, int D, void* out, int odtype, float* ws, hipStream_t s) {
   if (D % 8 != 0) return -1;
-  int nchunk = 1;
-  if (N > 0) {
-    if (dtype == 0)
-      launch_strip<float, false>((const float*)x, nullptr, nullptr, nullptr, ws, N, D, 0, nchunk, s);
-    else
-      launch_strip<uint16_t, false>((const uint16_t*)x, nullptr, nullptr, nullptr, ws, N, D, 0, nchunk, s);
-  } else {
-    nchunk = 0;
-  }
-  if (odtype == 0)
-    hipLaunchKernelGGL(colsum_finalize_kernel<float>, dim3((D + 15) / 16), dim3(256), 0, s, ws, nchunk, D,
-                       (float*)out);
-  else
-    hipLaunchKernelGGL(colsum_finalize_kernel<uint16_t>, dim3((D + 15) / 16), dim3(256), 0, s, ws, nchunk, D,
-                       (uint16_t*)out);
-  return 0;
+  int nchunk = 0;  // an empty input: the finalize alone, over no slabs, writes zeros
+  if (N > 0)
+    with_elem(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      launch_strip<T, false>((const T*)x, nullptr, nullptr, nullptr, ws, N, D, 0, nchunk, s);
+    });
+  return pdt_colsum_finalize(ws, nchunk, D, out, odtype, s);
 }
 
 }  // extern "C"

@@ -12,6 +12,8 @@
 // residual stream's own gradient, dx = LN'(dy) + ds. That removes the separate add kernels
 // (2 per block forward, 2 per block backward) and one full read of s.
 #include "../common.h"
+#include "../colsum_finalize.h"
+#include "../dispatch.h"
 #include "../launchers.h"
 #include "../fp8_pack.h"
 #include "../philox.h"
@@ -21,9 +23,6 @@ using namespace pdt;
 namespace {
 
 constexpr int kRowsPerBlock = 4;  // 4 waves, one row each
-
-template <typename T> __device__ __forceinline__ float round_to(float v) { return v; }
-template <> __device__ __forceinline__ float round_to<uint16_t>(float v) { return bf2f(f2bf(v)); }
 
 // Row statistics and the normalised value, shared by ln_fwd_kernel and ln_fwd_fp8_kernel with FP
 // contraction off, so both produce the same bits (the fp8 form quantizes exactly the bf16 y).
@@ -320,31 +319,6 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
   }
 }
 
-// Fixed-order column sums of the per-block partials: 16 columns x 16 row-groups per workgroup,
-// so each thread sums only nblk/16 independent values (latency-bound otherwise).
-__global__ __launch_bounds__(256) void ln_bwd_finalize_kernel(const float* __restrict__ part, int nblk, int D,
-                                                              float* __restrict__ dw, float* __restrict__ db) {
-  __shared__ float red[2][16][17];
-  const int grp = threadIdx.x >> 4, cl = threadIdx.x & 15;
-  const int c = blockIdx.x * 16 + cl;
-  float a = 0.f, b = 0.f;
-  if (c < D)
-    for (int blk = grp; blk < nblk; blk += 16) {
-      a += part[((int64_t)blk * 2 + 0) * D + c];
-      b += part[((int64_t)blk * 2 + 1) * D + c];
-    }
-  red[0][grp][cl] = a;
-  red[1][grp][cl] = b;
-  __syncthreads();
-  if (grp == 0 && c < D) {
-    float sa = 0.f, sb = 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) { sa += red[0][q][cl]; sb += red[1][q][cl]; }
-    dw[c] = sa;
-    db[c] = sb;
-  }
-}
-
 // Workgroup cap (PDT_LN_BWD_BLOCKS, read once; A/B): 512 = 2 workgroups per CU.
 inline int64_t ln_bwd_cap() {
   static int64_t cap = 0;
@@ -367,12 +341,52 @@ inline int64_t ln_bwd_min_rows() {
   return r;
 }
 
+// The backward's partition; the dgamma/dbeta slab is nblk x 2 x D floats.
 inline int ln_bwd_blocks(int64_t N, int& rows_per_block) {
-  int64_t nblk = (N + ln_bwd_min_rows() - 1) / ln_bwd_min_rows();
-  if (nblk > ln_bwd_cap()) nblk = ln_bwd_cap();  // the dgamma/dbeta slab is nblk x 2 x D floats
-  if (nblk < 1) nblk = 1;
-  rows_per_block = (int)((N + nblk - 1) / nblk);
-  return (int)((N + rows_per_block - 1) / rows_per_block);
+  return row_blocks(N, ln_bwd_min_rows(), ln_bwd_cap(), rows_per_block);
+}
+
+// pdt_ln_fwd (DROP = false: ticket = nullptr, dstream = thr = 0) and pdt_ln_fwd_drop.
+template <bool DROP>
+int ln_fwd(const void* x, const void* res, int dtype, const float* w, const float* b, void* y, void* sum_out,
+           float* mean, float* rstd, int64_t N, int D, float eps, const int64_t* ticket, int dstream, int thr,
+           hipStream_t s) {
+  if (D % 256 != 0) return -1;
+  if (N == 0) return 0;
+  const dim3 grid((unsigned)((N + kRowsPerBlock - 1) / kRowsPerBlock));
+  const auto launch = [&](auto kc) {
+    with_elem(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      hipLaunchKernelGGL((ln_fwd_kernel<T, decltype(kc)::value, DROP>), grid, dim3(256), 0, s, (const T*)x,
+                         (const T*)res, w, b, (T*)y, (T*)sum_out, mean, rstd, N, eps, ticket, dstream, thr);
+    });
+  };
+  // DROP stops at K = 8 as its backward does (ln_bwd below: the dropout form exists for training only)
+  if constexpr (DROP) return with_k<1, 2, 3, 4, 5, 6, 8>(D / 256, launch) ? 0 : -1;
+  else return with_k<1, 2, 3, 4, 5, 6, 8, 10, 12, 16>(D / 256, launch) ? 0 : -1;
+}
+
+// pdt_ln_bwd (DROP = false: dh = ticket = nullptr, dstream = thr = 0) and pdt_ln_bwd_drop. An empty input
+// launches only the finalize, over no slabs: dw = db = 0.
+template <bool DROP>
+int ln_bwd(const void* dy, const void* x, const void* dres, int dtype, const float* w, const float* mean,
+           const float* rstd, void* dx, void* dh, float* dw, float* db, int64_t N, int D, float* ws,
+           const int64_t* ticket, int dstream, int thr, hipStream_t s) {
+  if (D % 256 != 0 || D > 2048) return -1;
+  int rpb;
+  const int nblk = ln_bwd_blocks(N, rpb);
+  const auto launch = [&](auto kc) {
+    with_elem(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      hipLaunchKernelGGL((ln_bwd_kernel<T, decltype(kc)::value, DROP>), dim3(nblk), dim3(256), 0, s, (const T*)dy,
+                         (const T*)x, (const T*)dres, w, mean, rstd, (T*)dx, ws, N, rpb, (T*)dh, ticket, dstream,
+                         thr);
+    });
+  };
+  // K <= 8 (the forward goes to 16): the kernel's LDS is 2 x 4 x D floats, 64 KB at D = 2048
+  if (nblk > 0 && !with_k<1, 2, 3, 4, 5, 6, 8>(D / 256, launch)) return -1;
+  hipLaunchKernelGGL((colsum_finalize_kernel<2, float>), dim3((D + 15) / 16), dim3(256), 0, s, ws, nblk, D, dw, db);
+  return 0;
 }
 
 }  // namespace
@@ -384,42 +398,15 @@ int64_t pdt_ln_workspace_floats(int64_t N, int D) {
   return (int64_t)ln_bwd_blocks(N, rpb) * 2 * D;
 }
 
-#define PDT_LN_SWITCH(MACRO) \
-  switch (D / 256) {         \
-    case 1: MACRO(1); break; \
-    case 2: MACRO(2); break; \
-    case 3: MACRO(3); break; \
-    case 4: MACRO(4); break; \
-    case 5: MACRO(5); break; \
-    case 6: MACRO(6); break; \
-    case 8: MACRO(8); break; \
-    case 10: MACRO(10); break; \
-    case 12: MACRO(12); break; \
-    case 16: MACRO(16); break; \
-    default: return -1;      \
-  }
-
 // res / sum_out: optional residual branch h and the stored sum s = x + h (both or neither).
 int pdt_ln_fwd(const void* x, const void* res, int dtype, const float* w, const float* b, void* y, void* sum_out,
                float* mean, float* rstd, int64_t N, int D, float eps, hipStream_t s) {
   if ((res == nullptr) != (sum_out == nullptr)) return -2;
-  if (D % 256 != 0) return -1;
-  if (N == 0) return 0;
-  const dim3 grid((unsigned)((N + kRowsPerBlock - 1) / kRowsPerBlock));
-#define PDT_LNF(K)                                                                                           \
-  if (dtype == 0)                                                                                            \
-    hipLaunchKernelGGL((ln_fwd_kernel<float, K>), grid, dim3(256), 0, s, (const float*)x, (const float*)res, w, \
-                       b, (float*)y, (float*)sum_out, mean, rstd, N, eps);                                    \
-  else                                                                                                       \
-    hipLaunchKernelGGL((ln_fwd_kernel<uint16_t, K>), grid, dim3(256), 0, s, (const uint16_t*)x,               \
-                       (const uint16_t*)res, w, b, (uint16_t*)y, (uint16_t*)sum_out, mean, rstd, N, eps);
-  PDT_LN_SWITCH(PDT_LNF)
-#undef PDT_LNF
-  return 0;
+  return ln_fwd<false>(x, res, dtype, w, b, y, sum_out, mean, rstd, N, D, eps, nullptr, 0, 0, s);
 }
 
 // bf16 x (+ res -> sum_out) -> LayerNorm -> e4m3 yq [N, D] and yq^T [D, N] (scale / amax: the
-// consumer's fp8 state row). N % 16 == 0; D = 256 K, K in {2, .., 6} (K = 8 would spill).
+// consumer's fp8 state row). N % 16 == 0; D = 256 K.
 int pdt_ln_fwd_fp8(const uint16_t* x, const uint16_t* res, const float* w, const float* b, uint16_t* sum_out,
                    uint8_t* yq, uint8_t* yqt, float* mean, float* rstd, int64_t N, int D, float eps,
                    const float* scale, float* amax, int striped, hipStream_t s) {
@@ -427,19 +414,12 @@ int pdt_ln_fwd_fp8(const uint16_t* x, const uint16_t* res, const float* w, const
   if (D % 256 != 0 || N % 16 != 0) return -1;
   if (N == 0) return 0;
   const dim3 grid((unsigned)((N + 31) / 32));
-#define PDT_LNF8(K)                                                                                          \
-  hipLaunchKernelGGL((ln_fwd_fp8_kernel<K>), grid, dim3(512), 0, s, x, res, w, b, sum_out, yq, yqt, mean, rstd, N, \
-                     eps, scale, amax, striped);
-  switch (D / 256) {
-    case 2: PDT_LNF8(2); break;
-    case 3: PDT_LNF8(3); break;
-    case 4: PDT_LNF8(4); break;
-    case 5: PDT_LNF8(5); break;
-    case 6: PDT_LNF8(6); break;
-    default: return -1;
-  }
-#undef PDT_LNF8
-  return 0;
+  // K in {2, .., 6}, shorter than pdt_ln_fwd's list: K = 8 would spill (a wave holds 4 rows of x and h)
+  const bool ok = with_k<2, 3, 4, 5, 6>(D / 256, [&](auto kc) {
+    hipLaunchKernelGGL((ln_fwd_fp8_kernel<decltype(kc)::value>), grid, dim3(512), 0, s, x, res, w, b, sum_out, yq, yqt,
+                       mean, rstd, N, eps, scale, amax, striped);
+  });
+  return ok ? 0 : -1;
 }
 
 // Residual dropout inside add+LayerNorm: s = x + dropout(res), y = LN(s). thr in 1..255.
@@ -447,58 +427,13 @@ int pdt_ln_fwd_drop(const void* x, const void* res, int dtype, const float* w, c
                     void* sum_out, float* mean, float* rstd, int64_t N, int D, float eps, const int64_t* ticket,
                     int dstream, int thr, hipStream_t s) {
   if (res == nullptr || sum_out == nullptr || ticket == nullptr || thr < 1 || thr > 255) return -2;
-  if (D % 256 != 0) return -1;
-  if (N == 0) return 0;
-  const dim3 grid((unsigned)((N + kRowsPerBlock - 1) / kRowsPerBlock));
-#define PDT_LNFD(K)                                                                                            \
-  if (dtype == 0)                                                                                              \
-    hipLaunchKernelGGL((ln_fwd_kernel<float, K, true>), grid, dim3(256), 0, s, (const float*)x, (const float*)res, \
-                       w, b, (float*)y, (float*)sum_out, mean, rstd, N, eps, ticket, dstream, thr);             \
-  else                                                                                                         \
-    hipLaunchKernelGGL((ln_fwd_kernel<uint16_t, K, true>), grid, dim3(256), 0, s, (const uint16_t*)x,           \
-                       (const uint16_t*)res, w, b, (uint16_t*)y, (uint16_t*)sum_out, mean, rstd, N, eps, ticket, \
-                       dstream, thr);
-  switch (D / 256) {
-    case 1: PDT_LNFD(1); break;
-    case 2: PDT_LNFD(2); break;
-    case 3: PDT_LNFD(3); break;
-    case 4: PDT_LNFD(4); break;
-    case 5: PDT_LNFD(5); break;
-    case 6: PDT_LNFD(6); break;
-    case 8: PDT_LNFD(8); break;
-    default: return -1;
-  }
-#undef PDT_LNFD
-  return 0;
+  return ln_fwd<true>(x, res, dtype, w, b, y, sum_out, mean, rstd, N, D, eps, ticket, dstream, thr, s);
 }
 
 // dres: optional gradient added into dx (residual stream), same dtype/layout as dx.
 int pdt_ln_bwd(const void* dy, const void* x, const void* dres, int dtype, const float* w, const float* mean,
                const float* rstd, void* dx, float* dw, float* db, int64_t N, int D, float* ws, hipStream_t s) {
-  if (D % 256 != 0 || D > 2048) return -1;  // LDS: 2 x 4 x D floats
-  if (N == 0) return 0;
-  int rpb;
-  const int nblk = ln_bwd_blocks(N, rpb);
-#define PDT_LNB(K)                                                                                            \
-  if (dtype == 0)                                                                                             \
-    hipLaunchKernelGGL((ln_bwd_kernel<float, K>), dim3(nblk), dim3(256), 0, s, (const float*)dy, (const float*)x, \
-                       (const float*)dres, w, mean, rstd, (float*)dx, ws, N, rpb);                            \
-  else                                                                                                        \
-    hipLaunchKernelGGL((ln_bwd_kernel<uint16_t, K>), dim3(nblk), dim3(256), 0, s, (const uint16_t*)dy,         \
-                       (const uint16_t*)x, (const uint16_t*)dres, w, mean, rstd, (uint16_t*)dx, ws, N, rpb);
-  switch (D / 256) {
-    case 1: PDT_LNB(1); break;
-    case 2: PDT_LNB(2); break;
-    case 3: PDT_LNB(3); break;
-    case 4: PDT_LNB(4); break;
-    case 5: PDT_LNB(5); break;
-    case 6: PDT_LNB(6); break;
-    case 8: PDT_LNB(8); break;
-    default: return -1;
-  }
-#undef PDT_LNB
-  hipLaunchKernelGGL(ln_bwd_finalize_kernel, dim3((D + 15) / 16), dim3(256), 0, s, ws, nblk, D, dw, db);
-  return 0;
+  return ln_bwd<false>(dy, x, dres, dtype, w, mean, rstd, dx, nullptr, dw, db, N, D, ws, nullptr, 0, 0, s);
 }
 
 // The backward of pdt_ln_fwd_drop: dx as pdt_ln_bwd, and dh = dropout-backward of dx.
@@ -506,32 +441,7 @@ int pdt_ln_bwd_drop(const void* dy, const void* x, const void* dres, int dtype, 
                     const float* rstd, void* dx, void* dh, float* dw, float* db, int64_t N, int D, float* ws,
                     const int64_t* ticket, int dstream, int thr, hipStream_t s) {
   if (dh == nullptr || ticket == nullptr || thr < 1 || thr > 255) return -2;
-  if (D % 256 != 0 || D > 2048) return -1;
-  if (N == 0) return 0;
-  int rpb;
-  const int nblk = ln_bwd_blocks(N, rpb);
-#define PDT_LNBD(K)                                                                                           \
-  if (dtype == 0)                                                                                             \
-    hipLaunchKernelGGL((ln_bwd_kernel<float, K, true>), dim3(nblk), dim3(256), 0, s, (const float*)dy,         \
-                       (const float*)x, (const float*)dres, w, mean, rstd, (float*)dx, ws, N, rpb, (float*)dh, \
-                       ticket, dstream, thr);                                                                 \
-  else                                                                                                        \
-    hipLaunchKernelGGL((ln_bwd_kernel<uint16_t, K, true>), dim3(nblk), dim3(256), 0, s, (const uint16_t*)dy,   \
-                       (const uint16_t*)x, (const uint16_t*)dres, w, mean, rstd, (uint16_t*)dx, ws, N, rpb,    \
-                       (uint16_t*)dh, ticket, dstream, thr);
-  switch (D / 256) {
-    case 1: PDT_LNBD(1); break;
-    case 2: PDT_LNBD(2); break;
-    case 3: PDT_LNBD(3); break;
-    case 4: PDT_LNBD(4); break;
-    case 5: PDT_LNBD(5); break;
-    case 6: PDT_LNBD(6); break;
-    case 8: PDT_LNBD(8); break;
-    default: return -1;
-  }
-#undef PDT_LNBD
-  hipLaunchKernelGGL(ln_bwd_finalize_kernel, dim3((D + 15) / 16), dim3(256), 0, s, ws, nblk, D, dw, db);
-  return 0;
+  return ln_bwd<true>(dy, x, dres, dtype, w, mean, rstd, dx, dh, dw, db, N, D, ws, ticket, dstream, thr, s);
 }
 
 }  // extern "C"

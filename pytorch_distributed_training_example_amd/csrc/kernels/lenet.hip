@@ -23,6 +23,7 @@
 //     and with the eval metrics (sum loss, correct count accumulated on device — no per-batch
 //     .item() like train.py:68-70).
 #include "../common.h"
+#include "../dispatch.h"
 #include "../launchers.h"
 
 using namespace pdt;
@@ -333,12 +334,11 @@ int pdt_softmax_nll_small(const void* logits, int dtype, const int64_t* target, 
   if (V > 64 * kVPL) return 1;
   if (N == 0) return 0;
   const unsigned grid = (unsigned)((N + 3) / 4);
-  if (dtype == 0)
-    hipLaunchKernelGGL(softmax_nll_small_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)logits, target, N,
-                       V, mode, smoothing, loss, (float*)dlogits, dscale, acc);
-  else
-    hipLaunchKernelGGL(softmax_nll_small_kernel<uint16_t>, dim3(grid), dim3(256), 0, s, (const uint16_t*)logits,
-                       target, N, V, mode, smoothing, loss, (uint16_t*)dlogits, dscale, acc);
+  with_elem(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(softmax_nll_small_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)logits, target, N, V, mode,
+                       smoothing, loss, (T*)dlogits, dscale, acc);
+  });
   return 0;
 }
 

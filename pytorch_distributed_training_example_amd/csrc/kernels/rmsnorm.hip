@@ -12,6 +12,8 @@
 // branch first, s = round_T(x + h) (exactly what a separate add would store), writes s (the new residual
 // stream) and normalises it; the backward optionally adds the residual stream's own gradient ds.
 #include "../common.h"
+#include "../colsum_finalize.h"
+#include "../dispatch.h"
 #include "../launchers.h"
 
 using namespace pdt;
@@ -19,9 +21,6 @@ using namespace pdt;
 namespace {
 
 constexpr int kRowsPerBlock = 4;  // 4 waves, one row each
-
-template <typename T> __device__ __forceinline__ float round_to(float v) { return v; }
-template <> __device__ __forceinline__ float round_to<uint16_t>(float v) { return bf2f(f2bf(v)); }
 
 // K = D / 256: 4-element groups per lane (D = 256*K)
 template <typename T, int K>
@@ -141,37 +140,13 @@ __global__ __launch_bounds__(256) void rms_bwd_kernel(const T* __restrict__ dy, 
     part[(int64_t)blockIdx.x * D + c] = sdw[0][c] + sdw[1][c] + sdw[2][c] + sdw[3][c];
 }
 
-// Fixed-order column sums of the per-workgroup partials: 16 columns x 16 slab groups per workgroup,
-// so each thread sums only nblk/16 independent values (latency-bound otherwise).
-__global__ __launch_bounds__(256) void rms_bwd_finalize_kernel(const float* __restrict__ part, int nblk, int D,
-                                                               float* __restrict__ dw) {
-  __shared__ float red[16][17];
-  const int grp = threadIdx.x >> 4, cl = threadIdx.x & 15;
-  const int c = blockIdx.x * 16 + cl;
-  float a = 0.f;
-  if (c < D)
-    for (int blk = grp; blk < nblk; blk += 16) a += part[(int64_t)blk * D + c];
-  red[grp][cl] = a;
-  __syncthreads();
-  if (grp == 0 && c < D) {
-    float sa = 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) sa += red[q][cl];
-    dw[c] = sa;
-  }
-}
-
 // The backward's partition: at least kBwdMinRows rows per workgroup (8 per wave), at most kBwdMaxBlocks
 // workgroups (2 per CU; the dw slab is nblk x D floats). Past kBwdMinRows * kBwdMaxBlocks rows a
 // workgroup owns more than kBwdMinRows.
 constexpr int64_t kBwdMinRows = 32, kBwdMaxBlocks = 512;
 
 inline int rms_bwd_blocks(int64_t N, int& rows_per_block) {
-  int64_t nblk = (N + kBwdMinRows - 1) / kBwdMinRows;
-  if (nblk > kBwdMaxBlocks) nblk = kBwdMaxBlocks;
-  if (nblk < 1) nblk = 1;
-  rows_per_block = (int)((N + nblk - 1) / nblk);
-  return (int)((N + rows_per_block - 1) / rows_per_block);
+  return row_blocks(N, kBwdMinRows, kBwdMaxBlocks, rows_per_block);
 }
 
 }  // namespace
@@ -183,17 +158,7 @@ int64_t pdt_rms_workspace_floats(int64_t N, int D) {
   return (int64_t)rms_bwd_blocks(N, rpb) * D;
 }
 
-#define PDT_RMS_SWITCH(MACRO) \
-  switch (D / 256) {          \
-    case 1: MACRO(1); break;  \
-    case 2: MACRO(2); break;  \
-    case 3: MACRO(3); break;  \
-    case 4: MACRO(4); break;  \
-    case 5: MACRO(5); break;  \
-    case 6: MACRO(6); break;  \
-    case 8: MACRO(8); break;  \
-    default: return -1;       \
-  }
+// Forward and backward take the same widths, K = D / 256 in {1, .., 6, 8}: every forward has its backward.
 
 // res / sum_out: optional residual branch h and the stored sum s = x + h (both or neither).
 int pdt_rms_fwd(const void* x, const void* res, int dtype, const float* w, void* y, void* sum_out, float* rstd,
@@ -202,36 +167,34 @@ int pdt_rms_fwd(const void* x, const void* res, int dtype, const float* w, void*
   if (D <= 0 || D % 256 != 0) return -1;
   if (N == 0) return 0;
   const dim3 grid((unsigned)((N + kRowsPerBlock - 1) / kRowsPerBlock));
-#define PDT_RMSF(K)                                                                                             \
-  if (dtype == 0)                                                                                               \
-    hipLaunchKernelGGL((rms_fwd_kernel<float, K>), grid, dim3(256), 0, s, (const float*)x, (const float*)res, w, \
-                       (float*)y, (float*)sum_out, rstd, N, eps);                                               \
-  else                                                                                                          \
-    hipLaunchKernelGGL((rms_fwd_kernel<uint16_t, K>), grid, dim3(256), 0, s, (const uint16_t*)x,                 \
-                       (const uint16_t*)res, w, (uint16_t*)y, (uint16_t*)sum_out, rstd, N, eps);
-  PDT_RMS_SWITCH(PDT_RMSF)
-#undef PDT_RMSF
-  return 0;
+  const bool ok = with_k<1, 2, 3, 4, 5, 6, 8>(D / 256, [&](auto kc) {
+    with_elem(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      hipLaunchKernelGGL((rms_fwd_kernel<T, decltype(kc)::value>), grid, dim3(256), 0, s, (const T*)x, (const T*)res,
+                         w, (T*)y, (T*)sum_out, rstd, N, eps);
+    });
+  });
+  return ok ? 0 : -1;
 }
 
 // dres: optional gradient added into dx (residual stream), same dtype/layout as dx. ws: pdt_rms_workspace_floats.
+// An empty input launches only the finalize, over no slabs: dw = 0.
 int pdt_rms_bwd(const void* dy, const void* x, const void* dres, int dtype, const float* w, const float* rstd,
                 void* dx, float* dw, int64_t N, int D, float* ws, hipStream_t s) {
   if (D <= 0 || D % 256 != 0) return -1;
   int rpb;
-  const int nblk = N > 0 ? rms_bwd_blocks(N, rpb) : 0;
-#define PDT_RMSB(K)                                                                                              \
-  if (N > 0) {                                                                                                   \
-    if (dtype == 0)                                                                                              \
-      hipLaunchKernelGGL((rms_bwd_kernel<float, K>), dim3(nblk), dim3(256), 0, s, (const float*)dy,               \
-                         (const float*)x, (const float*)dres, w, rstd, (float*)dx, ws, N, rpb);                  \
-    else                                                                                                         \
-      hipLaunchKernelGGL((rms_bwd_kernel<uint16_t, K>), dim3(nblk), dim3(256), 0, s, (const uint16_t*)dy,         \
-                         (const uint16_t*)x, (const uint16_t*)dres, w, rstd, (uint16_t*)dx, ws, N, rpb);         \
-  }
-  PDT_RMS_SWITCH(PDT_RMSB)
-#undef PDT_RMSB
-  hipLaunchKernelGGL(rms_bwd_finalize_kernel, dim3((D + 15) / 16), dim3(256), 0, s, ws, nblk, D, dw);
+  const int nblk = rms_bwd_blocks(N, rpb);
+  const bool ok = with_k<1, 2, 3, 4, 5, 6, 8>(D / 256, [&](auto kc) {
+    if (nblk == 0) return;
+    with_elem(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      hipLaunchKernelGGL((rms_bwd_kernel<T, decltype(kc)::value>), dim3(nblk), dim3(256), 0, s, (const T*)dy,
+                         (const T*)x, (const T*)dres, w, rstd, (T*)dx, ws, N, rpb);
+    });
+  });
+  if (!ok) return -1;
+  hipLaunchKernelGGL((colsum_finalize_kernel<1, float>), dim3((D + 15) / 16), dim3(256), 0, s, ws, nblk, D, dw,
+                     (float*)nullptr);
   return 0;
 }
 

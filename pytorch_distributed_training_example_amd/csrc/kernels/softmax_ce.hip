@@ -11,6 +11,7 @@
 // -inf logits (masked vocabulary columns) are allowed off the target column when smoothing == 0:
 // they carry zero probability and zero gradient, as in F.cross_entropy.
 #include "../common.h"
+#include "../dispatch.h"
 #include "../launchers.h"
 
 using namespace pdt;
@@ -113,12 +114,11 @@ extern "C" {
 int pdt_ce_fwd(const void* logits, int dtype, const int64_t* target, int64_t N, int64_t V, float smoothing,
                int64_t ignore_index, float* loss, float* lse, hipStream_t s) {
   if (N == 0) return 0;
-  if (dtype == 0)
-    hipLaunchKernelGGL(ce_fwd_kernel<float>, dim3(N), dim3(256), 0, s, (const float*)logits, target, V, smoothing,
+  with_elem(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(ce_fwd_kernel<T>, dim3(N), dim3(256), 0, s, (const T*)logits, target, V, smoothing,
                        ignore_index, loss, lse);
-  else
-    hipLaunchKernelGGL(ce_fwd_kernel<uint16_t>, dim3(N), dim3(256), 0, s, (const uint16_t*)logits, target, V,
-                       smoothing, ignore_index, loss, lse);
+  });
   return 0;
 }
 
@@ -126,12 +126,11 @@ int pdt_ce_bwd(const void* logits, int dtype, const int64_t* target, const float
                float dloss_scale, int64_t N, int64_t V, float smoothing, int64_t ignore_index, void* dlogits,
                hipStream_t s) {
   if (N == 0) return 0;
-  if (dtype == 0)
-    hipLaunchKernelGGL(ce_bwd_kernel<float>, dim3(N), dim3(256), 0, s, (const float*)logits, target, lse, dloss,
-                       dloss_scale, V, smoothing, ignore_index, (float*)dlogits);
-  else
-    hipLaunchKernelGGL(ce_bwd_kernel<uint16_t>, dim3(N), dim3(256), 0, s, (const uint16_t*)logits, target, lse,
-                       dloss, dloss_scale, V, smoothing, ignore_index, (uint16_t*)dlogits);
+  with_elem(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(ce_bwd_kernel<T>, dim3(N), dim3(256), 0, s, (const T*)logits, target, lse, dloss, dloss_scale,
+                       V, smoothing, ignore_index, (T*)dlogits);
+  });
   return 0;
 }
 

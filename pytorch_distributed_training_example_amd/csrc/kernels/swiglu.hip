@@ -8,29 +8,13 @@
 // packed multiplies / FMAs, one v_exp_f32 + one v_rcp_f32 per value). 1 - sg is formed as e^-g sg for
 // g > 0, where the subtraction would cancel. F % 8 == 0: a lane owns 8 columns of one row, 16-byte accesses.
 #include "../common.h"
+#include "../dispatch.h"
 #include "../launchers.h"
 #include "../gelu_math.h"
 
 using namespace pdt;
 
 namespace {
-
-// 8 consecutive elements <-> 8 floats (16 B for bf16, 2 x 16 B for fp32).
-template <typename T> struct Vec8;
-template <> struct Vec8<uint16_t> {
-  __device__ __forceinline__ static void ld(const uint16_t* p, float (&v)[8]) { ld8_bf16(p, v); }
-  __device__ __forceinline__ static void st(uint16_t* p, const float (&v)[8]) { st8_bf16(p, v); }
-};
-template <> struct Vec8<float> {
-  __device__ __forceinline__ static void ld(const float* p, float (&v)[8]) {
-    const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  }
-  __device__ __forceinline__ static void st(float* p, const float (&v)[8]) {
-    reinterpret_cast<float4*>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
-    reinterpret_cast<float4*>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
-  }
-};
 
 // e^-g and sigma(g) of a pair. e^-g = 2^(-g log2 e) overflows to inf below g ~ -88.7: sigma = 0, cleanly.
 // (Just above that, down from g ~ -87.3, sigma is subnormal and v_rcp_f32 may return 0 for it: |g sigma| < 1e-35.)
@@ -109,11 +93,10 @@ int pdt_swiglu_fwd(const void* gu, int dtype, void* y, int64_t N, int F, hipStre
   dim3 grid;
   if (swiglu_grid(N, F, items, grid) != 0) return -1;
   if (items == 0) return 0;
-  if (dtype == 0)
-    hipLaunchKernelGGL(swiglu_fwd_kernel<float>, grid, dim3(256), 0, s, (const float*)gu, (float*)y, items, F / 8);
-  else
-    hipLaunchKernelGGL(swiglu_fwd_kernel<uint16_t>, grid, dim3(256), 0, s, (const uint16_t*)gu, (uint16_t*)y, items,
-                       F / 8);
+  with_elem(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(swiglu_fwd_kernel<T>, grid, dim3(256), 0, s, (const T*)gu, (T*)y, items, F / 8);
+  });
   return 0;
 }
 
@@ -123,12 +106,10 @@ int pdt_swiglu_bwd(const void* dy, const void* gu, int dtype, void* dgu, int64_t
   dim3 grid;
   if (swiglu_grid(N, F, items, grid) != 0) return -1;
   if (items == 0) return 0;
-  if (dtype == 0)
-    hipLaunchKernelGGL(swiglu_bwd_kernel<float>, grid, dim3(256), 0, s, (const float*)dy, (const float*)gu,
-                       (float*)dgu, items, F / 8);
-  else
-    hipLaunchKernelGGL(swiglu_bwd_kernel<uint16_t>, grid, dim3(256), 0, s, (const uint16_t*)dy, (const uint16_t*)gu,
-                       (uint16_t*)dgu, items, F / 8);
+  with_elem(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(swiglu_bwd_kernel<T>, grid, dim3(256), 0, s, (const T*)dy, (const T*)gu, (T*)dgu, items, F / 8);
+  });
   return 0;
 }
 

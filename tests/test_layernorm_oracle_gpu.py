@@ -121,6 +121,29 @@ def test_capped_partition(N, D, dtype, fused):
                          f"{'add' if fused else 'plain'} N={N} probe")
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("D", [256, 768])
+def test_empty_input(D, dtype):
+    """x of shape [0, D] straight into the launchers (an empty micro-batch reaches them: the op's native-path
+    test does not look at numel): empty y / s / dx, no statistics, and dgamma = dbeta = 0 exactly, with and
+    without the residual branch. The backward's partition once divided by zero here, on the host."""
+    from pytorch_distributed_training_example_amd.ops._native import native
+    ln = _ln(D)
+    w, b = ln.weight.detach(), ln.bias.detach()
+    x = torch.empty(0, D, device=DEV, dtype=dtype)
+    for fused in (False, True):
+        other = torch.empty_like(x) if fused else None
+        y, mean, rstd, s = native().ln_fwd(x, w, b, EPS, other)
+        assert y.shape == (0, D) and y.dtype == dtype
+        assert mean.shape == (0,) and rstd.shape == (0,) and mean.dtype == rstd.dtype == torch.float32
+        assert (s.shape == (0, D) and s.dtype == dtype) if fused else s is None
+        dx, dw, db = native().ln_bwd(torch.empty_like(x), x, w, mean, rstd, other)
+        torch.cuda.synchronize()
+        assert dx.shape == (0, D) and dx.dtype == dtype
+        for g in (dw, db):
+            assert g.shape == (D,) and g.dtype == torch.float32 and not bool(g.any()), "dgamma / dbeta of no rows"
+
+
 @pytest.mark.parametrize("D", WIDTHS)
 def test_large_mean_fp32(D):
     """x = 50 + 0.1 randn: the same bounds. A one-pass variance E[x^2] - mean^2 loses ~4 digits here and

@@ -115,6 +115,28 @@ def test_dw_repeats_bit_for_bit(N, D, dtype):
         assert torch.equal(again[1], first[1]) and torch.equal(again[0], first[0])
 
 
+@pytest.mark.parametrize("dtype", list(DTYPES))
+@pytest.mark.parametrize("D", [256, 768])
+def test_empty_input(D, dtype):
+    """x of shape [0, D] straight into the launchers (an empty micro-batch reaches them: the op's native-path
+    test does not look at numel): empty y / s / dx, no rstd, and dw = 0 exactly, with and without the residual
+    branch. The workspace size's partition once divided by zero here, on the host."""
+    from pytorch_distributed_training_example_amd.ops._native import native
+    dt = DTYPES[dtype]
+    w = lo.rms_inputs(1, D, dt, False)[-1].to(DEV)
+    x = torch.empty(0, D, device=DEV, dtype=dt)
+    for fused in (False, True):
+        other = torch.empty_like(x) if fused else None
+        y, rstd, s = native().rms_fwd(x, w, lo.EPS, other)
+        assert y.shape == (0, D) and y.dtype == dt
+        assert rstd.shape == (0,) and rstd.dtype == torch.float32
+        assert (s.shape == (0, D) and s.dtype == dt) if fused else s is None
+        dx, dw = native().rms_bwd(torch.empty_like(x), x, w, rstd, other)
+        torch.cuda.synchronize()
+        assert dx.shape == (0, D) and dx.dtype == dt
+        assert dw.shape == (D,) and dw.dtype == torch.float32 and not bool(dw.any()), "dw of no rows"
+
+
 GUARD = 64
 
 
