@@ -104,8 +104,9 @@ MODEL_DEFAULTS = {
     **{name: dict(optimizer="sgd", loss="cross_entropy") for name in ("llama_tiny", "llama_tiny_gqa", "llama_small", "llama_medium")},
 }
 
-FP8_LLAMA_MSG = ("--precision fp8: the Llama-style models have no fp8 path (RMSNorm and SwiGLU have no fp8-emitting "
-                 "forms, so the GEMMs would silently run in bf16); use --precision bf16")
+FP8_LLAMA_MSG = ("--precision fp8: the Llama-style models run their fp8 path on the GPU only (the e4m3 RMSNorm, "
+                 "SwiGLU and GEMM forms are HIP kernels; on the CPU the GEMMs would silently run in bf16); use "
+                 "--precision bf16")
 
 
 def _llama_heads(model_name: str):
@@ -369,7 +370,7 @@ def main(argv: Optional[list] = None) -> int:
         raise SystemExit(f"--dropout must be in [0, 1), got {args.dropout}")
     if args.dropout > 0 and not has_dropout_sites(args.model):
         raise SystemExit(dropout_unsupported_msg(args.model))
-    if args.precision == "fp8" and args.model.startswith("llama"):
+    if args.precision == "fp8" and args.model.startswith("llama") and (args.no_cuda or not torch.cuda.is_available()):
         raise SystemExit(FP8_LLAMA_MSG)
     if args.kv_heads is not None and not kv_heads_ok(args.model, args.kv_heads):
         raise SystemExit(kv_heads_msg(args.model, args.kv_heads))

@@ -95,7 +95,13 @@ PDT_FP8_FUSED_GELU          1            fp8 MLPs: bias+GELU (and its backward) 
 PDT_FP8_WEIGHT_MULTI        1            fp8: every Linear weight cast in one launch per forward (fp8_cast_multi)
 PDT_FP8_CAST_COLSUM         1            fp8: a Linear's output-gradient cast also yields its bias gradient
 PDT_FP8_LN                  1            fp8: the add+LayerNorm in front of qkv / fc1 writes its output as e4m3 +
-                                         transpose for that GEMM (layernorm.hip ln_fwd_fp8_kernel): no bf16 y
+                                         transpose for that GEMM (layernorm.hip ln_fwd_fp8_kernel): no bf16 y.
+                                         Also the Llama decoder's add+RMSNorm in front of c_attn / c_fc
+                                         (rmsnorm.hip rms_fwd_fp8_kernel)
+PDT_FP8_SWIGLU              1            fp8 Llama MLPs: SwiGLU (and its backward) emit e4m3 + transpose directly
+                                         (fp8.hip fp8_swiglu_cast_kernel): no bf16 activation, no cast pass. With
+                                         this and PDT_FP8_LN off, the per-Linear fp8 path (bf16 RMSNorm / SwiGLU
+                                         plus a cast pass): the unfused reference of the tests
 PDT_WGRAD_STREAM_M          0            conv weight gradients with <= this many output pixels run on a side
                                          stream, concurrent with their data gradient (0 = in-stream)
 PDT_DROPOUT_FUSED           1            GPT-2 / ViT dropout from counter-generated masks inside our kernels
@@ -113,7 +119,7 @@ class _Switches:
                  "conv_bn_stats", "bn_bwd_stats", "res_masked", "stem_bwd_fused", "stem_bn_wgrad", "stem_bn_stats", "stem_pool_wgrad", "wgrad_splitk", "slice_sum",
                  "subsample_native", "linear_splitk", "fused_addln", "embedding_native", "linear_epilogue",
                  "bwd_fused", "bwd_fused_shapes", "bwd_alg", "alg_glo", "bwd_alg_min_m", "z3_virtual", "bwd_alg_first", "ds_alg", "bn2_defer", "bn_apply_gemm_k", "strided_bstats", "gap_native", "sub_out",
-                 "fp8_fused_gelu", "fp8_weight_multi", "fp8_cast_colsum", "fp8_ln", "wgrad_stream_m",
+                 "fp8_fused_gelu", "fp8_weight_multi", "fp8_cast_colsum", "fp8_ln", "fp8_swiglu", "wgrad_stream_m",
                  "dropout_fused")
 
     def __init__(self):
@@ -181,6 +187,7 @@ class _Switches:
         self.fp8_weight_multi = on("PDT_FP8_WEIGHT_MULTI")
         self.fp8_cast_colsum = on("PDT_FP8_CAST_COLSUM")
         self.fp8_ln = on("PDT_FP8_LN")
+        self.fp8_swiglu = on("PDT_FP8_SWIGLU")
         # conv weight gradients of at most this many output pixels run on a side stream, concurrent
         # with their data gradient (0 = off): small-batch grids leave CUs idle (ops/conv.py _WgradFork)
         self.wgrad_stream_m = int(e("PDT_WGRAD_STREAM_M", "0"))

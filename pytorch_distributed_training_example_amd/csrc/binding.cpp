@@ -84,6 +84,13 @@ uint8_t* opt_u8_ptr(const Op& op, const char* name, const c10::optional<Tensor>&
 }
 // fp8 state rows (ops/fp8.py Fp8State) of at least pdt::kAmaxRowMin floats carry the 16 amax stripes.
 int fp8_striped(const Tensor& row) { return row.numel() >= pdt::kAmaxRowMin ? 1 : 0; }
+// A producer's fp8 state row (amax, scale, scale_inv, ...): its pointer; the scale is element 1.
+float* fp8_row_ptr(const Op& op, const Tensor& row) {
+  TORCH_CHECK(row.defined() && row.scalar_type() == at::kFloat && row.numel() >= 3 && row.is_contiguous() &&
+                  row.device() == op.dev,
+              op.name, ": state_row must be a contiguous fp32 row (amax, scale, scale_inv, ...) on ", op.dev);
+  return row.data_ptr<float>();
+}
 
 // A device-side scalar (learning rate, loss scale, step count): the kernel reads element 0.
 const float* opt_scalar_ptr(const Op& op, const char* name, const c10::optional<Tensor>& t) {
@@ -1727,6 +1734,35 @@ std::vector<Tensor> rms_fwd(Tensor x, Tensor w, double eps, c10::optional<Tensor
   return {y, rstd, sum};
 }
 
+// RMSNorm straight to fp8 for an fp8 GEMM (rmsnorm.hip rms_fwd_fp8_kernel): x bf16 [..., D] (+ res: s = x + res
+// stored). Returns {yq [N, D], yq^T [D, N], rstd, s}; state_row is the consuming GEMM's input-operand row.
+// D = 256 K with K <= 6 and N % 16 == 0; anything else is refused.
+std::vector<Tensor> rms_fwd_fp8(Tensor x, Tensor w, double eps, c10::optional<Tensor> res, Tensor state_row) {
+  const Op op("rms_fwd_fp8", x);
+  TORCH_CHECK(x.is_contiguous() && x.dim() >= 1 && x.scalar_type() == at::kBFloat16 && aligned16(x),
+              "rms_fwd_fp8: x must be contiguous, 16-byte aligned bf16");
+  const int64_t D = x.size(-1), N = D > 0 ? x.numel() / D : 0;
+  TORCH_CHECK(D > 0 && D % 256 == 0 && D / 256 <= 6 && N % 16 == 0,
+              "rms_fwd_fp8: unsupported N=", N, " D=", D, " (D = 256 K with K <= 6, N % 16 == 0)");
+  const bool hr = has(res);
+  if (hr)
+    TORCH_CHECK(res->is_contiguous() && res->sizes() == x.sizes() && res->scalar_type() == x.scalar_type() &&
+                    res->device() == op.dev && aligned16(*res),
+                "rms_fwd_fp8: residual must match x (contiguous, same shape/dtype/device)");
+  const float* wp = f32_ptr(op, "w", w, D);
+  float* st = fp8_row_ptr(op, state_row);
+  auto o8 = x.options().dtype(at::kFloat8_e4m3fn);
+  auto yq = at::empty({N, D}, o8), yqt = at::empty({D, N}, o8);
+  Tensor sum;
+  if (hr) sum = at::empty_like(x);
+  auto rstd = at::empty({N}, x.options().dtype(at::kFloat));
+  int rc = pdt_rms_fwd_fp8(bf16_ptr(x), hr ? bf16_ptr(*res) : nullptr, wp, ptr_or_null<uint16_t>(sum), byte_ptr(yq),
+                           byte_ptr(yqt), rstd.data_ptr<float>(), N, (int)D, (float)eps, st + 1, st,
+                           fp8_striped(state_row), stream());
+  TORCH_CHECK(rc == 0, "pdt_rms_fwd_fp8: unsupported N=", N, " D=", D);
+  return {yq, yqt, rstd, sum};
+}
+
 // dres: optional gradient added into dx (the residual stream's own gradient). {dx, dw}
 std::vector<Tensor> rms_bwd(Tensor dy, Tensor x, Tensor w, Tensor rstd, c10::optional<Tensor> dres,
                             c10::optional<Tensor> dx_out, c10::optional<Tensor> dw_out) {
@@ -2202,6 +2238,33 @@ std::vector<Tensor> fp8_cast_colsum(Tensor x, Tensor state_row, at::ScalarType d
   TORCH_CHECK(nchunk > 0, "pdt_fp8_cast_colsum failed: ", nchunk);
   pdt_colsum_finalize(part.data_ptr<float>(), nchunk, (int)D, db.data_ptr(), db_dtype == at::kFloat ? 0 : 1, stream());
   return {out, out_t, db};
+}
+
+// The Llama MLP activation straight to fp8 (fp8.hip fp8_swiglu_cast_kernel). gu: bf16 [M, 2F] = [gate | up]
+// (c_fc's output). Forward (dy undefined): {fp8(silu(gate) up) [M, F], its transpose [F, M]}. Backward (dy bf16
+// [M, F]): {fp8([dgate | dup]) [M, 2F], its transpose [2F, M]}. F % 64 == 0 and M % 16 == 0; anything else is
+// refused. state_row as fp8_cast_transpose.
+std::vector<Tensor> fp8_swiglu_cast(Tensor gu, c10::optional<Tensor> dy, Tensor state_row) {
+  const Op op("fp8_swiglu_cast", gu);
+  TORCH_CHECK(gu.scalar_type() == at::kBFloat16 && gu.dim() == 2 && gu.is_contiguous() && aligned16(gu) &&
+                  gu.size(1) % 2 == 0,
+              "fp8_swiglu_cast: gu must be a contiguous, 16-byte aligned bf16 [M, 2F] tensor");
+  const int64_t M = gu.size(0), F = gu.size(1) / 2;
+  TORCH_CHECK(M > 0 && M % 16 == 0 && F > 0 && F % 64 == 0 && F <= 0x7fffffffLL,
+              "fp8_swiglu_cast: unsupported M=", M, " F=", F, " (M % 16 == 0 and F % 64 == 0)");
+  const bool bwd = has(dy);
+  if (bwd)
+    TORCH_CHECK(dy->scalar_type() == at::kBFloat16 && dy->dim() == 2 && dy->size(0) == M && dy->size(1) == F &&
+                    dy->is_contiguous() && dy->device() == op.dev && aligned16(*dy),
+                "fp8_swiglu_cast: dy must be a contiguous, 16-byte aligned bf16 [M, F] tensor on gu's device");
+  float* st = fp8_row_ptr(op, state_row);
+  auto o8 = gu.options().dtype(at::kFloat8_e4m3fn);
+  const int64_t W = bwd ? 2 * F : F;
+  auto out = at::empty({M, W}, o8), out_t = at::empty({W, M}, o8);
+  const int nchunk = pdt_fp8_swiglu_cast(bf16_ptr(gu), bwd ? bf16_ptr(*dy) : nullptr, M, (int)F, st + 1, byte_ptr(out),
+                                         byte_ptr(out_t), st, fp8_striped(state_row), stream());
+  TORCH_CHECK(nchunk > 0, "pdt_fp8_swiglu_cast failed: ", nchunk);
+  return {out, out_t};
 }
 
 // Every tensor of xs (bf16 [M_i, K_i] contiguous) cast with its state row in one launch (<= 64 per
@@ -2686,6 +2749,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("y_out") = py::none(), py::arg("rstd_out") = py::none(), py::arg("sum_out") = py::none());
   m.def("rms_bwd", &rms_bwd, py::arg("dy"), py::arg("x"), py::arg("w"), py::arg("rstd"),
         py::arg("dres") = py::none(), py::arg("dx_out") = py::none(), py::arg("dw_out") = py::none());
+  m.def("rms_fwd_fp8", &rms_fwd_fp8, py::arg("x"), py::arg("w"), py::arg("eps"), py::arg("res"), py::arg("state_row"));
   m.def("rope_qkv", &rope_qkv, py::arg("qkv"), py::arg("cos"), py::arg("sin"), py::arg("heads"),
         py::arg("conj") = false);
   m.def("rope_qkv_gqa", &rope_qkv_gqa, py::arg("qkv"), py::arg("cos"), py::arg("sin"), py::arg("heads"),
@@ -2703,6 +2767,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fp8_update_scales", &fp8_update_scales);
   m.def("fp8_gelu_cast", &fp8_gelu_cast, py::arg("h"), py::arg("dg") = py::none(), py::arg("bias") = py::none(),
         py::arg("state_row"), py::arg("tanh_form") = false, py::arg("db_dtype") = at::kFloat);
+  m.def("fp8_swiglu_cast", &fp8_swiglu_cast, py::arg("gu"), py::arg("dy") = py::none(), py::arg("state_row"));
   m.def("fp8_cast_multi", &fp8_cast_multi);
   m.def("fp8_cast_colsum", &fp8_cast_colsum);
   m.def("lenet_stem_fwd", &lenet_stem_fwd);

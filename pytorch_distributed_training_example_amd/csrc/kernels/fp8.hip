@@ -18,6 +18,7 @@
 #include "../launchers.h"
 #include "../fp8_pack.h"
 #include "../gelu_math.h"
+#include "../swiglu_math.h"
 
 using namespace pdt;
 
@@ -39,26 +40,51 @@ constexpr int kTM = 128;
 __device__ __forceinline__ int t8(int r, int g) { return r * 16 + (g ^ ((r >> 3) & 15)); }
 
 struct Pre {
-  uint4 x[2][2], g[2][2];  // [row half][16-B piece]: the operand and (GELU backward) its gradient
+  // [row half][16-B piece]: the operand, (GELU / SwiGLU backward) its gradient, (SwiGLU) the up projection
+  uint4 x[2][2], g[2][2], u[2][2];
 };
 
-enum { M_CAST = 0, M_GELU = 1, M_GELU_BWD = 2, M_CAST_SUM = 3 };  // M_CAST_SUM: cast + column sums
+// M_CAST_SUM: cast + column sums. M_SWIGLU / M_SWIGLU_BWD: the operand is the gate half of a packed [rows, 2K]
+// gate/up tensor (the up half K columns further on), the outputs are K (forward) or 2K (backward) wide.
+enum { M_CAST = 0, M_GELU = 1, M_GELU_BWD = 2, M_CAST_SUM = 3, M_SWIGLU = 4, M_SWIGLU_BWD = 5 };
 
 template <int MODE>
 __device__ __forceinline__ void tile_load(Pre& p, const uint16_t* __restrict__ x, const uint16_t* __restrict__ dg,
                                           int64_t rows, int64_t K, int64_t m0, int64_t k0, int ra, int cc) {
   if (k0 + cc >= K) return;
+  constexpr bool GLU = MODE == M_SWIGLU || MODE == M_SWIGLU_BWD;
 #pragma unroll
   for (int hh = 0; hh < 2; ++hh) {
     const int64_t row = m0 + ra + 64 * hh;
     if (row < rows) {
       const int64_t off = row * K + k0 + cc;
-      p.x[hh][0] = *reinterpret_cast<const uint4*>(x + off);
-      p.x[hh][1] = *reinterpret_cast<const uint4*>(x + off + 8);
-      if (MODE == M_GELU_BWD) {
+      const int64_t xoff = GLU ? off + row * K : off;  // row pitch 2K
+      p.x[hh][0] = *reinterpret_cast<const uint4*>(x + xoff);
+      p.x[hh][1] = *reinterpret_cast<const uint4*>(x + xoff + 8);
+      if (GLU) {
+        p.u[hh][0] = *reinterpret_cast<const uint4*>(x + xoff + K);
+        p.u[hh][1] = *reinterpret_cast<const uint4*>(x + xoff + K + 8);
+      }
+      if (MODE == M_GELU_BWD || MODE == M_SWIGLU_BWD) {
         p.g[hh][0] = *reinterpret_cast<const uint4*>(dg + off);
         p.g[hh][1] = *reinterpret_cast<const uint4*>(dg + off + 8);
       }
+    }
+  }
+}
+
+// The transposed phase: the LDS image of a 128 x 64 tile of fp8 bytes -> out_t [K, M] (see above).
+__device__ __forceinline__ void tile_store_t(const uint32_t* lds, int64_t rows, int64_t M, int64_t K, int64_t m0,
+                                             int64_t k0, uint8_t* __restrict__ out_t, int probe) {
+  const int rb = threadIdx.x & 15, gq = threadIdx.x >> 4;
+  if (!(probe & 1) && m0 + rb * 8 < rows && k0 + 4 * gq < K) {  // rows and K are multiples of 8 / 16: whole blocks
+    uint32_t wv[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) wv[i] = lds[t8(rb * 8 + i, gq)];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t lo = byte_col(wv[0], wv[1], wv[2], wv[3], j), hi = byte_col(wv[4], wv[5], wv[6], wv[7], j);
+      *reinterpret_cast<uint2*>(out_t + (k0 + 4 * gq + j) * M + m0 + rb * 8) = make_uint2(lo, hi);
     }
   }
 }
@@ -82,6 +108,10 @@ __device__ __forceinline__ void tile_emit(const Pre& p, const float* bl, float s
         ld8_bf16(reinterpret_cast<const uint16_t*>(&p.g[hh][0]), *reinterpret_cast<float(*)[8]>(g));
         ld8_bf16(reinterpret_cast<const uint16_t*>(&p.g[hh][1]), *reinterpret_cast<float(*)[8]>(g + 8));
       }
+      if (MODE == M_SWIGLU) {  // g: the up projection
+        ld8_bf16(reinterpret_cast<const uint16_t*>(&p.u[hh][0]), *reinterpret_cast<float(*)[8]>(g));
+        ld8_bf16(reinterpret_cast<const uint16_t*>(&p.u[hh][1]), *reinterpret_cast<float(*)[8]>(g + 8));
+      }
       float b[16];  // the strip's bias (GELU modes), from LDS: 16 VGPRs fewer through the tile loop
       if (MODE == M_GELU || MODE == M_GELU_BWD) {
 #pragma unroll
@@ -89,7 +119,11 @@ __device__ __forceinline__ void tile_emit(const Pre& p, const float* bl, float s
       }
 #pragma unroll
       for (int j = 0; j < 16; j += 2) {
-        if (MODE == M_GELU) {
+        if (MODE == M_SWIGLU) {
+          const gf2 r = swiglu_fwd2(gf2{v[j], v[j + 1]}, gf2{g[j], g[j + 1]});
+          v[j] = bf2f(f2bf(r.x));
+          v[j + 1] = bf2f(f2bf(r.y));
+        } else if (MODE == M_GELU) {
           const gf2 r = gelu2(gf2{v[j] + b[j], v[j + 1] + b[j + 1]}, tanh_form);
           v[j] = bf2f(f2bf(r.x));
           v[j + 1] = bf2f(f2bf(r.y));
@@ -115,18 +149,61 @@ __device__ __forceinline__ void tile_emit(const Pre& p, const float* bl, float s
     for (int q = 0; q < 4; ++q) lds[t8(ra + 64 * hh, (cc >> 2) + q)] = w[q];
   }
   __syncthreads();
-  const int rb = threadIdx.x & 15, gq = threadIdx.x >> 4;
-  if (!(probe & 1) && m0 + rb * 8 < rows && k0 + 4 * gq < K) {  // rows and K are multiples of 8 / 16: whole blocks
-    uint32_t wv[8];
+  tile_store_t(lds, rows, M, K, m0, k0, out_t, probe);
+  __syncthreads();  // the LDS image is rewritten by the next tile
+}
+
+// The SwiGLU backward's tile: (dy, g, u) -> the dg tile at column k0 and the du tile at column F + k0 of the
+// packed [M, 2F] gradient and of its transpose [2F, M]; lds holds the two tile images one after the other.
+// F % 64 == 0: no column edge.
+__device__ __forceinline__ void tile_emit_swiglu_bwd(const Pre& p, float s, int64_t rows, int64_t M, int64_t F,
+                                                     int64_t m0, int64_t k0, int ra, int cc,
+                                                     uint8_t* __restrict__ out, uint8_t* __restrict__ out_t,
+                                                     uint32_t* lds, float& am, int probe) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) wv[i] = lds[t8(rb * 8 + i, gq)];
+  for (int hh = 0; hh < 2; ++hh) {
+    const int64_t row = m0 + ra + 64 * hh;
+    uint32_t wg[4] = {0u, 0u, 0u, 0u}, wu[4] = {0u, 0u, 0u, 0u};
+    if (row < rows) {
+      float g[16], u[16], d[16];
+      ld8_bf16(reinterpret_cast<const uint16_t*>(&p.x[hh][0]), *reinterpret_cast<float(*)[8]>(g));
+      ld8_bf16(reinterpret_cast<const uint16_t*>(&p.x[hh][1]), *reinterpret_cast<float(*)[8]>(g + 8));
+      ld8_bf16(reinterpret_cast<const uint16_t*>(&p.u[hh][0]), *reinterpret_cast<float(*)[8]>(u));
+      ld8_bf16(reinterpret_cast<const uint16_t*>(&p.u[hh][1]), *reinterpret_cast<float(*)[8]>(u + 8));
+      ld8_bf16(reinterpret_cast<const uint16_t*>(&p.g[hh][0]), *reinterpret_cast<float(*)[8]>(d));
+      ld8_bf16(reinterpret_cast<const uint16_t*>(&p.g[hh][1]), *reinterpret_cast<float(*)[8]>(d + 8));
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const uint32_t lo = byte_col(wv[0], wv[1], wv[2], wv[3], j), hi = byte_col(wv[4], wv[5], wv[6], wv[7], j);
-      *reinterpret_cast<uint2*>(out_t + (k0 + 4 * gq + j) * M + m0 + rb * 8) = make_uint2(lo, hi);
+      for (int j = 0; j < 16; j += 2) {
+        gf2 rg, ru;
+        swiglu_bwd2(gf2{d[j], d[j + 1]}, gf2{g[j], g[j + 1]}, gf2{u[j], u[j + 1]}, rg, ru);
+        g[j] = bf2f(f2bf(rg.x));  // g, u: dg, du from here on
+        g[j + 1] = bf2f(f2bf(rg.y));
+        u[j] = bf2f(f2bf(ru.x));
+        u[j + 1] = bf2f(f2bf(ru.y));
+        am = fmaxf(fmaxf(am, fabsf(g[j])), fabsf(g[j + 1]));
+        am = fmaxf(fmaxf(am, fabsf(u[j])), fabsf(u[j + 1]));
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        wg[q] = pack4_fp8(g[4 * q] * s, g[4 * q + 1] * s, g[4 * q + 2] * s, g[4 * q + 3] * s);
+        wu[q] = pack4_fp8(u[4 * q] * s, u[4 * q + 1] * s, u[4 * q + 2] * s, u[4 * q + 3] * s);
+      }
+      if (!(probe & 2)) {
+        uint8_t* o = out + row * 2 * F + k0 + cc;
+        *reinterpret_cast<uint4*>(o) = make_uint4(wg[0], wg[1], wg[2], wg[3]);
+        *reinterpret_cast<uint4*>(o + F) = make_uint4(wu[0], wu[1], wu[2], wu[3]);
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      lds[t8(ra + 64 * hh, (cc >> 2) + q)] = wg[q];
+      lds[kTM * 16 + t8(ra + 64 * hh, (cc >> 2) + q)] = wu[q];
     }
   }
-  __syncthreads();  // the LDS image is rewritten by the next tile
+  __syncthreads();
+  tile_store_t(lds, rows, M, F, m0, k0, out_t, probe);
+  tile_store_t(lds + kTM * 16, rows, M, F, m0, k0, out_t + F * M, probe);
+  __syncthreads();  // the LDS images are rewritten by the next tile
 }
 
 // amax: the state row. Striped rows (Fp8State, fp8_pack.h kAmaxStripes) take workgroup b's maximum
@@ -237,17 +314,59 @@ __global__ __launch_bounds__(256) void fp8_gelu_cast_kernel(const uint16_t* __re
 // Row chunks of whole 128-row tiles so that strips x chunks ~ one resident wave of workgroups: 1024
 // for the forward (4 per CU), 768 for the backward (162 VGPRs: 3 per CU) — a second partial round
 // of workgroups would run at a fraction of the occupancy.
-inline int gelu_cast_chunks(int64_t M, int D, bool bwd, int& rpc) {
+inline int cast_chunks(int64_t M, int D, int resident, int& rpc) {
   const int64_t tiles = (M + kTM - 1) / kTM, strips = D / kTile;
-  int64_t n = (bwd ? 768 : 1024) / strips;
+  int64_t n = resident / strips;
   if (n > tiles) n = tiles;
   if (n < 1) n = 1;
   rpc = (int)(((tiles + n - 1) / n) * kTM);
   return (int)((M + rpc - 1) / rpc);
 }
+inline int gelu_cast_chunks(int64_t M, int D, bool bwd, int& rpc) { return cast_chunks(M, D, bwd ? 768 : 1024, rpc); }
+// The SwiGLU modes, re-derived by the same rule for their register counts (not measured): the forward holds
+// 130 VGPRs (3 workgroups per CU: 768), the backward 186 (2 per CU: 512).
+inline int swiglu_cast_chunks(int64_t M, int F, bool bwd, int& rpc) { return cast_chunks(M, F, bwd ? 512 : 768, rpc); }
 
 // (the same kernel with MODE = M_CAST_SUM is the cast of a Linear's output gradient dy that also
 // yields the bias gradient sum_m dy: the separate column-strip pass over dy is gone.)
+
+// The Llama MLP's activation in fp8, produced where it is computed (fp8.py _Fp8SwigluMlpFn), from the packed
+// gate/up GEMM output gu [M, 2F] = [g | u]:
+//   forward  (MODE = M_SWIGLU):     a = g sigma(g) u              -> a as e4m3 [M, F] + its transpose [F, M]
+//   backward (MODE = M_SWIGLU_BWD): [dg | du] from (dy, gu)       -> e4m3 [M, 2F] + its transpose [2F, M]
+// sigma(g) is recomputed from gu; both halves of the gradient take one scale and one amax (c_fc's
+// output-gradient row). The values quantized are the bf16-rounded results of swiglu_math.h's pair formulas,
+// exactly what swiglu.hip stores, so the bytes equal swiglu_fwd / swiglu_bwd followed by fp8_cast_transpose.
+// No biases, so no column sums. A workgroup owns one 64-column strip of F and a chunk of 128-row tiles, as
+// fp8_gelu_cast_kernel; the backward emits its strip twice, at column k0 and at column F + k0.
+// F % 64 == 0, M % 16 == 0.
+template <int MODE>
+__global__ __launch_bounds__(256) void fp8_swiglu_cast_kernel(const uint16_t* __restrict__ gu,
+                                                              const uint16_t* __restrict__ dy, int64_t M, int F,
+                                                              int rows_per_chunk, const float* __restrict__ scale,
+                                                              uint8_t* __restrict__ out, uint8_t* __restrict__ out_t,
+                                                              float* __restrict__ amax, int striped) {
+  constexpr bool BWD = MODE == M_SWIGLU_BWD;
+  __shared__ uint32_t lds[(BWD ? 2 : 1) * kTM * 16];
+  __shared__ float red[4];
+  const int ra = threadIdx.x >> 2, cc = (threadIdx.x & 3) * 16;
+  const int64_t k0 = (int64_t)blockIdx.x * kTile;
+  const int64_t mbeg = (int64_t)blockIdx.y * rows_per_chunk;
+  const int64_t mend = min(M, mbeg + rows_per_chunk);
+  const float s = *scale;
+  float am = 0.f, cs[16];  // cs: unused by these modes
+  Pre p;
+  tile_load<MODE>(p, gu, dy, mend, F, mbeg, k0, ra, cc);
+  for (int64_t m0 = mbeg; m0 < mend; m0 += kTM) {
+    const Pre cur = p;
+    if (m0 + kTM < mend) tile_load<MODE>(p, gu, dy, mend, F, m0 + kTM, k0, ra, cc);
+    if constexpr (BWD)
+      tile_emit_swiglu_bwd(cur, s, mend, M, F, m0, k0, ra, cc, out, out_t, lds, am, striped >> 1);
+    else
+      tile_emit<MODE>(cur, nullptr, s, 0, mend, M, F, m0, k0, ra, cc, out, out_t, lds, am, cs, striped >> 1);
+  }
+  amax_commit(am, red, amax, striped & 1, blockIdx.y * gridDim.x + blockIdx.x);
+}
 
 // Weight casts of a whole model in one launch: a table of tensors, one workgroup range per tensor
 // (each runs the cast tile loop over its own tiles). A step casts every fp8 Linear's weight once
@@ -380,6 +499,24 @@ int pdt_fp8_cast_colsum(const uint16_t* x, int64_t M, int D, const float* scale,
   const int nchunk = gelu_cast_chunks(M, D, true, rpc);
   hipLaunchKernelGGL(fp8_gelu_cast_kernel<M_CAST_SUM>, dim3(D / kTile, nchunk), dim3(256), 0, s, x, nullptr, nullptr,
                      M, D, rpc, 0, scale, out, out_t, amax_probe() ? nullptr : amax, part, striped | store_probe());
+  return nchunk;
+}
+
+// gu bf16 [M, 2F] = [g | u]. dy == nullptr (forward): out [M, F] = fp8(g sigma(g) u), out_t [F, M]. With dy
+// bf16 [M, F] (backward): out [M, 2F] = fp8([dg | du]), out_t [2F, M]. Scale / amax as pdt_fp8_cast_transpose.
+// Returns the chunk count (>= 1), or < 0 when the shape is not served (F % 64, M % 16).
+int pdt_fp8_swiglu_cast(const uint16_t* gu, const uint16_t* dy, int64_t M, int F, const float* scale, uint8_t* out,
+                        uint8_t* out_t, float* amax, int striped, hipStream_t s) {
+  if (F <= 0 || F % kTile != 0 || M <= 0 || M % 16 != 0) return -1;
+  int rpc;
+  const int nchunk = swiglu_cast_chunks(M, F, dy != nullptr, rpc);
+  const dim3 grid(F / kTile, nchunk);
+  if (dy)
+    hipLaunchKernelGGL(fp8_swiglu_cast_kernel<M_SWIGLU_BWD>, grid, dim3(256), 0, s, gu, dy, M, F, rpc, scale, out,
+                       out_t, amax_probe() ? nullptr : amax, striped | store_probe());
+  else
+    hipLaunchKernelGGL(fp8_swiglu_cast_kernel<M_SWIGLU>, grid, dim3(256), 0, s, gu, dy, M, F, rpc, scale, out, out_t,
+                       amax_probe() ? nullptr : amax, striped | store_probe());
   return nchunk;
 }
 

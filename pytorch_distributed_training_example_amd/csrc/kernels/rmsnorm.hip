@@ -15,12 +15,33 @@
 #include "../colsum_finalize.h"
 #include "../dispatch.h"
 #include "../launchers.h"
+#include "../fp8_pack.h"
 
 using namespace pdt;
 
 namespace {
 
 constexpr int kRowsPerBlock = 4;  // 4 waves, one row each
+
+// The row arithmetic shared by rms_fwd_kernel and rms_fwd_fp8_kernel, so both produce the same bits (the
+// fp8 form quantizes exactly the bf16 y). The contraction is pinned to what rms_fwd_kernel has always
+// compiled to: each square rounded on its own and added in (k, j) order (never fused: the squares issue as
+// packed multiplies), one fused multiply-add for mean + eps.
+template <int K>
+__device__ __forceinline__ float rms_rstd(const float (&v)[K][4], float eps) {
+#pragma clang fp contract(off)
+  constexpr int D = 256 * K;
+  float q = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) q += v[k][j] * v[k][j];
+  return rsqrtf(__builtin_fmaf(wave_sum(q), 1.f / D, eps));
+}
+__device__ __forceinline__ float rms_val(float v, float rstd, float w) {
+#pragma clang fp contract(off)
+  return v * rstd * w;
+}
 
 // K = D / 256: 4-element groups per lane (D = 256*K)
 template <typename T, int K>
@@ -45,12 +66,7 @@ __global__ __launch_bounds__(256) void rms_fwd_kernel(const T* __restrict__ x, c
       Vec4<T>::st(sum_out + row * D, (int64_t)(k * 256 + lane * 4), v[k]);
     }
   }
-  float q = 0.f;
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) q += v[k][j] * v[k][j];
-  const float rstd = rsqrtf(wave_sum(q) * (1.f / D) + eps);
+  const float rstd = rms_rstd<K>(v, eps);
   T* yr = y + row * D;
 #pragma unroll
   for (int k = 0; k < K; ++k) {
@@ -58,10 +74,107 @@ __global__ __launch_bounds__(256) void rms_fwd_kernel(const T* __restrict__ x, c
     float wv[4], o[4];
     Vec4<float>::ld(w, c, wv);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = v[k][j] * rstd * wv[j];
+    for (int j = 0; j < 4; ++j) o[j] = rms_val(v[k][j], rstd, wv[j]);
     Vec4<T>::st(yr, (int64_t)c, o);
   }
   if (lane == 0) rstd_out[row] = rstd;
+}
+
+// RMSNorm (+ residual add) whose output goes straight to e4m3 for the fp8 GEMM that consumes it (ops/fp8.py
+// Fp8Act: a Llama block's c_attn and c_fc inputs), the twin of layernorm.hip's ln_fwd_fp8_kernel. Unfused, the
+// bf16 y was written here and read back by a cast-transpose pass; this kernel writes y as fp8 row-major AND
+// transposed, scaled by the consumer's delayed scale, with |y|max folded into its amax slot. y is rounded to
+// bf16 before quantizing and s, rstd come from rms_rstd / rms_val, so the bytes equal the unfused chain's.
+// A workgroup owns 32 rows (8 waves x 4 rows, every row's loads issued before any row's math); the fp8 rows
+// also go to an LDS image (row pitch D + 4 bytes: the transposed readers' 8-row blocks hit distinct banks)
+// from which the transposed 32-B row segments are written. Tiles are placed XCD-aware so the four tiles
+// sharing a 128-B line of y^T write it through one L2. N % 16 == 0 keeps the 8-row blocks whole.
+template <int K>
+__global__ __launch_bounds__(512) void rms_fwd_fp8_kernel(const uint16_t* __restrict__ x,
+                                                          const uint16_t* __restrict__ res,
+                                                          const float* __restrict__ w,
+                                                          uint16_t* __restrict__ sum_out, uint8_t* __restrict__ yq,
+                                                          uint8_t* __restrict__ yqt, float* __restrict__ rstd_out,
+                                                          int64_t N, float eps, const float* __restrict__ scale,
+                                                          float* __restrict__ amax, int striped) {
+  constexpr int D = 256 * K, kRows = 32, kPitch = D + 4;
+  __shared__ __attribute__((aligned(16))) uint8_t tile[kRows * kPitch];
+  __shared__ float red[8];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t m0 = (int64_t)xcd_remap(blockIdx.x, gridDim.x) * kRows;
+  const float s8 = *scale;
+  float wr[K][4];
+#pragma unroll
+  for (int k = 0; k < K; ++k) Vec4<float>::ld(w, k * 256 + lane * 4, wr[k]);
+  float am = 0.f;
+  uint2 xv[4][K], hv[4][K];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int64_t row = m0 + wv * 4 + q;
+    if (row < N) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        xv[q][k] = *reinterpret_cast<const uint2*>(x + row * D + k * 256 + lane * 4);
+        if (res != nullptr) hv[q][k] = *reinterpret_cast<const uint2*>(res + row * D + k * 256 + lane * 4);
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int tr = wv * 4 + q;
+    const int64_t row = m0 + tr;
+    if (row >= N) continue;  // wave-uniform
+    float v[K][4];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      v[k][0] = __uint_as_float(xv[q][k].x << 16); v[k][1] = __uint_as_float(xv[q][k].x & 0xffff0000u);
+      v[k][2] = __uint_as_float(xv[q][k].y << 16); v[k][3] = __uint_as_float(xv[q][k].y & 0xffff0000u);
+      if (res != nullptr) {  // s = x + h, stored and normalised at storage precision (as rms_fwd_kernel)
+        const float hh[4] = {__uint_as_float(hv[q][k].x << 16), __uint_as_float(hv[q][k].x & 0xffff0000u),
+                             __uint_as_float(hv[q][k].y << 16), __uint_as_float(hv[q][k].y & 0xffff0000u)};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[k][j] = round_to<uint16_t>(v[k][j] + hh[j]);
+        Vec4<uint16_t>::st(sum_out + row * D, (int64_t)(k * 256 + lane * 4), v[k]);
+      }
+    }
+    const float rstd = rms_rstd<K>(v, eps);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      float o[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        o[j] = round_to<uint16_t>(rms_val(v[k][j], rstd, wr[k][j]));
+        am = fmaxf(am, fabsf(o[j]));
+      }
+      const uint32_t pk = pack4_fp8(o[0] * s8, o[1] * s8, o[2] * s8, o[3] * s8);
+      *reinterpret_cast<uint32_t*>(yq + row * D + k * 256 + lane * 4) = pk;
+      *reinterpret_cast<uint32_t*>(tile + tr * kPitch + k * 256 + lane * 4) = pk;
+    }
+    if (lane == 0) rstd_out[row] = rstd;
+  }
+  __syncthreads();
+  // y^T: item (word column g, 8-row block rb) -> 4 rows of y^T, 8 bytes each
+  for (int it = threadIdx.x; it < (D / 4) * 4; it += 512) {
+    const int rb = it & 3, g = it >> 2;
+    if (m0 + rb * 8 < N) {
+      uint32_t t8[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) t8[i] = *reinterpret_cast<const uint32_t*>(tile + (rb * 8 + i) * kPitch + g * 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        *reinterpret_cast<uint2*>(yqt + (int64_t)(g * 4 + j) * N + m0 + rb * 8) =
+            make_uint2(byte_col(t8[0], t8[1], t8[2], t8[3], j), byte_col(t8[4], t8[5], t8[6], t8[7], j));
+    }
+  }
+  am = wave_max(am);
+  if (lane == 0) red[wv] = am;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float bm = red[0];
+#pragma unroll
+    for (int i = 1; i < 8; ++i) bm = fmaxf(bm, red[i]);
+    if (bm > 0.f) atomicMax(reinterpret_cast<int*>(amax_slot(amax, striped, blockIdx.x)), __float_as_int(bm));
+  }
 }
 
 // Backward: dx per row; per-workgroup partial dw written to part[blk][D]. A workgroup owns the rows
@@ -173,6 +286,25 @@ int pdt_rms_fwd(const void* x, const void* res, int dtype, const float* w, void*
       hipLaunchKernelGGL((rms_fwd_kernel<T, decltype(kc)::value>), grid, dim3(256), 0, s, (const T*)x, (const T*)res,
                          w, (T*)y, (T*)sum_out, rstd, N, eps);
     });
+  });
+  return ok ? 0 : -1;
+}
+
+// bf16 x (+ res -> sum_out) -> RMSNorm -> e4m3 yq [N, D] and yq^T [D, N] (scale / amax: the consumer's fp8
+// state row). N % 16 == 0; D = 256 K with K in {1, .., 6}: the 32-row LDS image at pitch D + 4 passes 64 KB at
+// K = 8, which keeps rms_fwd + the cast pass.
+int pdt_rms_fwd_fp8(const uint16_t* x, const uint16_t* res, const float* w, uint16_t* sum_out, uint8_t* yq,
+                    uint8_t* yqt, float* rstd, int64_t N, int D, float eps, const float* scale, float* amax,
+                    int striped, hipStream_t s) {
+  if ((res == nullptr) != (sum_out == nullptr)) return -2;
+  if (D <= 0 || D % 256 != 0 || N < 0 || N % 16 != 0) return -1;
+  const int64_t nblk = (N + 31) / 32;
+  if (nblk > 0x7fffffffLL) return -1;
+  bool launch = N > 0;
+  const bool ok = with_k<1, 2, 3, 4, 5, 6>(D / 256, [&](auto kc) {
+    if (!launch) return;
+    hipLaunchKernelGGL((rms_fwd_fp8_kernel<decltype(kc)::value>), dim3((unsigned)nblk), dim3(512), 0, s, x, res, w,
+                       sum_out, yq, yqt, rstd, N, eps, scale, amax, striped);
   });
   return ok ? 0 : -1;
 }

@@ -4,24 +4,18 @@
 // [2F, D] weight). With sg = sigma(g) = 1 / (1 + e^-g):
 //   forward   y[n, f] = round_T(g sg u)                                   [N, F]
 //   backward  dg = dy u sg (1 + g (1 - sg)),   du = dy g sg               packed dgu [N, 2F], one pass
-// sg is recomputed from gu in the backward; nothing but gu is saved. fp32 math on value pairs (gelu_math.h:
-// packed multiplies / FMAs, one v_exp_f32 + one v_rcp_f32 per value). 1 - sg is formed as e^-g sg for
-// g > 0, where the subtraction would cancel. F % 8 == 0: a lane owns 8 columns of one row, 16-byte accesses.
+// sg is recomputed from gu in the backward; nothing but gu is saved. fp32 math on value pairs (swiglu_math.h,
+// shared with the fp8-emitting forms in fp8.hip: packed multiplies / FMAs, one v_exp_f32 + one v_rcp_f32 per
+// value). 1 - sg is formed as e^-g sg for g > 0, where the subtraction would cancel. F % 8 == 0: a lane owns
+// 8 columns of one row, 16-byte accesses.
 #include "../common.h"
 #include "../dispatch.h"
 #include "../launchers.h"
-#include "../gelu_math.h"
+#include "../swiglu_math.h"
 
 using namespace pdt;
 
 namespace {
-
-// e^-g and sigma(g) of a pair. e^-g = 2^(-g log2 e) overflows to inf below g ~ -88.7: sigma = 0, cleanly.
-// (Just above that, down from g ~ -87.3, sigma is subnormal and v_rcp_f32 may return 0 for it: |g sigma| < 1e-35.)
-__device__ __forceinline__ void sigmoid2(gf2 g, gf2& e, gf2& sg) {
-  e = exp2_2(g2(-1.4426950408889634f) * g);
-  sg = rcp2(g2(1.f) + e);
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void swiglu_fwd_kernel(const T* __restrict__ gu, T* __restrict__ y, int64_t items,
@@ -36,10 +30,7 @@ __global__ __launch_bounds__(256) void swiglu_fwd_kernel(const T* __restrict__ g
   Vec8<T>::ld(gu + n * 2 * F + F + c, u);
 #pragma unroll
   for (int j = 0; j < 8; j += 2) {
-    const gf2 gv{g[j], g[j + 1]};
-    gf2 e, sg;
-    sigmoid2(gv, e, sg);
-    const gf2 r = gv * sg * gf2{u[j], u[j + 1]};
+    const gf2 r = swiglu_fwd2(gf2{g[j], g[j + 1]}, gf2{u[j], u[j + 1]});
     o[j] = r.x;
     o[j + 1] = r.y;
   }
@@ -60,13 +51,8 @@ __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const T* __restrict__ d
   Vec8<T>::ld(gu + n * 2 * F + F + c, u);
 #pragma unroll
   for (int j = 0; j < 8; j += 2) {
-    const gf2 gv{g[j], g[j + 1]}, dv{d[j], d[j + 1]};
-    gf2 e, sg;
-    sigmoid2(gv, e, sg);
-    const gf2 a = e * sg, b = g2(1.f) - sg;  // 1 - sg two ways
-    const gf2 oms{gv.x > 0.f ? a.x : b.x, gv.y > 0.f ? a.y : b.y};
-    const gf2 rg = dv * gf2{u[j], u[j + 1]} * sg * fma2(gv, oms, g2(1.f));
-    const gf2 ru = dv * gv * sg;
+    gf2 rg, ru;
+    swiglu_bwd2(gf2{d[j], d[j + 1]}, gf2{g[j], g[j + 1]}, gf2{u[j], u[j + 1]}, rg, ru);
     og[j] = rg.x; og[j + 1] = rg.y;
     ou[j] = ru.x; ou[j + 1] = ru.y;
   }

@@ -235,6 +235,8 @@ int pdt_fp8_gelu_cast(const uint16_t* h, const uint16_t* dg, const float* bias, 
                       hipStream_t s);
 int pdt_fp8_cast_colsum(const uint16_t* x, int64_t M, int D, const float* scale, uint8_t* out, uint8_t* out_t,
                         float* amax, float* part, int striped, hipStream_t s);
+int pdt_fp8_swiglu_cast(const uint16_t* gu, const uint16_t* dy, int64_t M, int F, const float* scale, uint8_t* out,
+                        uint8_t* out_t, float* amax, int striped, hipStream_t s);
 int pdt_fp8_cast_multi(int n, const uint16_t* const* x, const int* M, const int* K, float* const* st,
                        const int* striped, uint8_t* const* out, uint8_t* const* out_t, hipStream_t s);
 int pdt_fp8_update_scales(float* state, int n, int L, float margin_scale, int striped, hipStream_t s);
@@ -332,6 +334,9 @@ int pdt_p2p_allreduce(const void* in, void* out, int64_t n, int dtype, char* con
 int64_t pdt_rms_workspace_floats(int64_t N, int D);
 int pdt_rms_fwd(const void* x, const void* res, int dtype, const float* w, void* y, void* sum_out, float* rstd,
                 int64_t N, int D, float eps, hipStream_t s);
+int pdt_rms_fwd_fp8(const uint16_t* x, const uint16_t* res, const float* w, uint16_t* sum_out, uint8_t* yq,
+                    uint8_t* yqt, float* rstd, int64_t N, int D, float eps, const float* scale, float* amax,
+                    int striped, hipStream_t s);
 int pdt_rms_bwd(const void* dy, const void* x, const void* dres, int dtype, const float* w, const float* rstd,
                 void* dx, float* dw, int64_t N, int D, float* ws, hipStream_t s);
 

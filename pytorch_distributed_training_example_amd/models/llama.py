@@ -8,7 +8,14 @@ one kernel per residual step each way.
 
 Multi-head or grouped-query attention (``n_kv_head`` K/V heads, each shared by ``n_head / n_kv_head``
 consecutive query heads, HF's ``repeat_kv`` order; the flash kernels read the shared heads in place),
-head dim 64, no dropout sites, no fp8 forms, sequence length at most ``block_size`` (the RoPE table).
+head dim 64, no dropout sites, sequence length at most ``block_size`` (the RoPE table).
+
+fp8 (``--precision fp8``, ops/fp8.py ``enable_fp8``): the four Linears of every block run their three GEMMs on
+e4m3 operands, and the operations in front of them write e4m3 where the value is computed: the add+RMSNorm
+in front of ``c_attn`` / ``c_fc`` (``add_rms_norm_fp8``) and SwiGLU in front of ``mlp.c_proj``
+(``fp8_swiglu_mlp``, which also emits the packed gate/up gradient in e4m3 for ``c_fc``'s backward GEMMs). The
+first ``ln_1`` stays the plain kernel plus ``c_attn``'s own cast, the LM head stays bf16. An untagged model,
+``eval()``, fp32, the CPU and ``PDT_DISABLE_NATIVE=1`` take the bf16 path above unchanged.
 Parameter names follow the nanoGPT-style layout of models/gpt2.py: ``transformer.wte``,
 ``transformer.h.{i}.ln_1``, ``.attn.c_attn`` (packed q, k, v rows: ``(n_head + 2·n_kv_head)·64`` of them),
 ``.attn.c_proj``, ``.ln_2``, ``.mlp.c_fc`` (packed [gate; up] rows), ``.mlp.c_proj``, ``transformer.ln_f``,
@@ -26,6 +33,7 @@ from torch import nn
 from ..config import SW
 from ..ops.attention import attention_qkv
 from ..ops.cross_entropy import cross_entropy
+from ..ops.fp8 import Fp8Act, add_rms_norm_fp8, fp8_input_slot, fp8_linear, fp8_ok, fp8_swiglu_mlp, rms_fp8_ok
 from ..ops.linear import linear
 from ..ops.rmsnorm import RMSNorm, add_rms_norm
 from ..ops.rope import RotaryTable, rope_qkv_
@@ -52,6 +60,20 @@ class LlamaConfig:
         return self.n_head if self.n_kv_head is None else self.n_kv_head
 
 
+def _fp8_tag(mod: nn.Linear):
+    """``mod``'s (state, slot) when ``enable_fp8`` tagged it and it is training; else None (the bf16 path)."""
+    return getattr(mod, "_fp8", None) if mod.training else None
+
+
+def _linear(x, mod: nn.Linear) -> torch.Tensor:
+    """``mod``'s bias-free GEMM: fp8 when ``enable_fp8`` tagged it and the shape is served (ops/fp8.py; ``x``
+    may then be an ``Fp8Act``, already e4m3 from ``add_rms_norm_fp8``), else bf16 (ops/linear.py)."""
+    t = _fp8_tag(mod)
+    if t is not None and (isinstance(x, Fp8Act) or fp8_ok(x, mod.weight)):
+        return fp8_linear(x, mod.weight, None, t[0], t[1])
+    return linear(x, mod.weight)
+
+
 class LlamaAttention(nn.Module):
     def __init__(self, dim: int, heads: int, kv_heads: int | None = None):
         super().__init__()
@@ -64,10 +86,10 @@ class LlamaAttention(nn.Module):
         self.c_proj = nn.Linear(dim, dim, bias=False)
 
     def forward(self, x: torch.Tensor, rope: RotaryTable) -> torch.Tensor:
-        qkv = linear(x, self.c_attn.weight)  # [B, T, (H + 2 Hkv) 64]; its backward needs x and W only, so
+        qkv = _linear(x, self.c_attn)  # [B, T, (H + 2 Hkv) 64]; its backward needs x and W only, so
         qkv = rope_qkv_(qkv, rope.cos, rope.sin, self.heads, self.kv_heads)  # Q and K are rotated in place
         y = attention_qkv(qkv, self.heads, causal=True, kv_heads=self.kv_heads)
-        return linear(y, self.c_proj.weight)
+        return _linear(y, self.c_proj)
 
 
 class LlamaMLP(nn.Module):
@@ -77,7 +99,11 @@ class LlamaMLP(nn.Module):
         self.c_proj = nn.Linear(hidden, dim, bias=False)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return linear(swiglu(linear(x, self.c_fc.weight)), self.c_proj.weight)
+        if _fp8_tag(self.c_fc) is not None:
+            y = fp8_swiglu_mlp(x, self.c_fc, self.c_proj)  # SwiGLU emits e4m3 for c_proj (PDT_FP8_SWIGLU)
+            if y is not None:
+                return y
+        return _linear(swiglu(_linear(x, self.c_fc)), self.c_proj)
 
 
 class LlamaBlock(nn.Module):
@@ -108,9 +134,21 @@ def run_llama_blocks(blocks, x: torch.Tensor, final_norm: RMSNorm, rope: RotaryT
         return final_norm(x)
     y = blocks[0].ln_1(x)
     for i, blk in enumerate(blocks):
-        x, y = add_rms_norm(x, blk.attn(y, rope), blk.ln_2)
-        x, y = add_rms_norm(x, blk.mlp(y), blocks[i + 1].ln_1 if i + 1 < len(blocks) else final_norm)
+        x, y = _add_norm(x, blk.attn(y, rope), blk.ln_2, blk.mlp)
+        nxt, cons = (blocks[i + 1].ln_1, blocks[i + 1].attn.c_attn) if i + 1 < len(blocks) else (final_norm, None)
+        x, y = _add_norm(x, blk.mlp(y), nxt, cons)
     return y
+
+
+def _add_norm(x, h, norm: RMSNorm, consumer):
+    """add_rms_norm, or its fp8-emitting form when ``consumer`` (the module the normalised output feeds: a
+    block's MLP, the next block's ``c_attn``, None for the final norm) runs an fp8 GEMM on it in training
+    (ops/fp8.py fp8_input_slot; PDT_FP8_LN)."""
+    if consumer is not None and consumer.training:
+        t = fp8_input_slot(consumer, x)
+        if t is not None and rms_fp8_ok(x, h, norm):
+            return add_rms_norm_fp8(x, h, norm, t[0], t[1])
+    return add_rms_norm(x, h, norm)
 
 
 class Llama(nn.Module):

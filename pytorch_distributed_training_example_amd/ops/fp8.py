@@ -1,8 +1,8 @@
 """FP8 (OCP e4m3fn) Linear layers with delayed per-tensor scaling — BASELINE.json config 3
 ("ViT-B/16 DDP + AMP (bf16/fp8)").
 
-Every Linear inside the transformer blocks runs its three GEMMs on fp8 operands through
-hipBLASLt (``torch._scaled_mm``; 1.4-2.3x the bf16 rate on these shapes on gfx950,
+Every Linear inside the transformer blocks (GPT-2 / ViT ``Block``, ``LlamaBlock``) runs its three
+GEMMs on fp8 operands through hipBLASLt (``torch._scaled_mm``; 1.4-2.3x the bf16 rate on these shapes on gfx950,
 tools/fp8_bench.py) with fp32 accumulation and bf16 outputs:
 
     fwd    Y  = Xq · Wqᵀ              (+ bias in the GEMM epilogue)
@@ -99,7 +99,9 @@ class _Fp8LinearFn(torch.autograd.Function):
                              out_dtype=torch.bfloat16)
         ctx.save_for_backward(xqt, wqt, state)
         ctx.slot, ctx.has_b, ctx.xshape = slot, b is not None, x.shape
-        return y.reshape(*x.shape[:-1], w.shape[0])
+        # (not .reshape: autograd refuses an in-place op, ops/rope.py, on a view made inside a Function; y is
+        # this call's own tensor, which is what _unsafe_view is for, as ops/linear.py does)
+        return torch.ops.aten._unsafe_view(y, [*x.shape[:-1], w.shape[0]])
 
     @staticmethod
     def backward(ctx, dy):
@@ -245,17 +247,88 @@ def fp8_mlp(x, fc1: nn.Linear, fc2: nn.Linear, approximate: str) -> Optional[tor
                            approximate == "tanh", x.q if pre else None, x.qt if pre else None)
 
 
+class _Fp8SwigluMlpFn(torch.autograd.Function):
+    """The Llama MLP, c_fc -> SwiGLU -> c_proj (no biases), with the activation produced in fp8 where it
+    is computed: ``fp8_swiglu_cast`` turns c_fc's packed bf16 output gu = [g | u] into silu(g) u as e4m3
+    (+ transpose) in one pass, and its backward form turns (dA, gu) into [dg | du] as e4m3 (+ transpose),
+    both halves on c_fc's output-gradient scale. Neither the bf16 activation nor its gradient is ever
+    written (unfused: a SwiGLU kernel writing them + a cast-transpose reading them back, each way)."""
+
+    @staticmethod
+    def forward(ctx, x, w1, w2, state, s1, s2, st, xq=None, xqt=None):
+        C = native()
+        D = x.shape[-1]
+        if xq is None:
+            x2 = x.reshape(-1, D)
+            if not x2.is_contiguous():
+                x2 = x2.contiguous()
+            xq, xqt = C.fp8_cast_transpose(x2, state[s1], True)
+        w1q, w1qt = st.weight_fp8(w1, s1)
+        gu = torch._scaled_mm(xq, w1q.t(), scale_a=state[s1, 2], scale_b=state[s1 + 1, 2], out_dtype=torch.bfloat16)
+        aq, aqt = C.fp8_swiglu_cast(gu, None, state[s2])
+        w2q, w2qt = st.weight_fp8(w2, s2)
+        y = torch._scaled_mm(aq, w2q.t(), scale_a=state[s2, 2], scale_b=state[s2 + 1, 2], out_dtype=torch.bfloat16)
+        ctx.save_for_backward(xqt, w1qt, gu, aqt, w2qt, state)
+        ctx.s1, ctx.s2, ctx.xshape = s1, s2, x.shape
+        return torch.ops.aten._unsafe_view(y, [*x.shape[:-1], w2.shape[0]])
+
+    @staticmethod
+    def backward(ctx, dy):
+        xqt, w1qt, gu, aqt, w2qt, state = ctx.saved_tensors
+        s1, s2 = ctx.s1, ctx.s2
+        C = native()
+        dy2 = dy.reshape(-1, dy.shape[-1])
+        if not dy2.is_contiguous():
+            dy2 = dy2.contiguous()
+        dyq, dyqt = C.fp8_cast_transpose(dy2, state[s2 + 2], True)  # no bias: the plain cast
+        da = torch._scaled_mm(dyq, w2qt.t(), scale_a=state[s2 + 2, 2], scale_b=state[s2 + 1, 2],
+                              out_dtype=torch.bfloat16)
+        dw2 = torch._scaled_mm(dyqt, aqt.t(), scale_a=state[s2 + 2, 2], scale_b=state[s2, 2], out_dtype=torch.bfloat16)
+        dguq, dguqt = C.fp8_swiglu_cast(gu, da, state[s1 + 2])
+        dx = torch._scaled_mm(dguq, w1qt.t(), scale_a=state[s1 + 2, 2], scale_b=state[s1 + 1, 2],
+                              out_dtype=torch.bfloat16).reshape(ctx.xshape)
+        dw1 = torch._scaled_mm(dguqt, xqt.t(), scale_a=state[s1 + 2, 2], scale_b=state[s1, 2], out_dtype=torch.bfloat16)
+        return dx, dw1, dw2, None, None, None, None, None, None
+
+
+def _is_swiglu_mlp(fc1, fc2) -> bool:
+    """c_fc packs [gate; up] (2F rows) for a c_proj of F inputs: the Llama MLP, not the GELU one."""
+    return (isinstance(fc1, nn.Linear) and isinstance(fc2, nn.Linear) and fc1.bias is None and fc2.bias is None
+            and fc1.weight.shape[0] == 2 * fc2.weight.shape[1])
+
+
+def _swiglu_mlp_ok(x: torch.Tensor, fc1: nn.Linear, fc2: nn.Linear) -> bool:
+    a, b = getattr(fc1, "_fp8", None), getattr(fc2, "_fp8", None)
+    if a is None or b is None or a[0] is not b[0] or not SW.fp8_swiglu or not _is_swiglu_mlp(fc1, fc2):
+        return False
+    return (fp8_ok(x, fc1.weight) and fc2.weight.dtype == torch.bfloat16 and fc2.weight.shape[1] % 64 == 0
+            and fc2.weight.shape[0] % 16 == 0 and fc1.weight.is_contiguous() and fc2.weight.is_contiguous())
+
+
+def fp8_swiglu_mlp(x, c_fc: nn.Linear, c_proj: nn.Linear) -> Optional[torch.Tensor]:
+    """The Llama MLP on fp8 with the fused SwiGLU casts, or None when a shape / dtype is not served or
+    ``PDT_FP8_SWIGLU=0`` (the caller then runs the per-Linear path). ``x`` may be an ``Fp8Act`` (then it
+    is always served)."""
+    pre = isinstance(x, Fp8Act)
+    if not pre and not _swiglu_mlp_ok(x, c_fc, c_proj):
+        return None
+    st, s1, s2 = c_fc._fp8[0], c_fc._fp8[1], c_proj._fp8[1]
+    return _Fp8SwigluMlpFn.apply(x.token if pre else x, c_fc.weight, c_proj.weight, st.state, s1, s2, st,
+                                 x.q if pre else None, x.qt if pre else None)
+
+
 def fp8_input_slot(consumer: nn.Module, x: torch.Tensor):
-    """(state, slot) when ``consumer`` — an fp8-tagged Linear, or an MLP whose fused fp8 path
-    will run — takes ``x`` as an fp8 GEMM operand and can be handed an ``Fp8Act``; else None."""
+    """(state, slot) when ``consumer`` — an fp8-tagged Linear, or an MLP (GELU or SwiGLU) whose fused fp8
+    path will run — takes ``x`` as an fp8 GEMM operand and can be handed an ``Fp8Act``; else None."""
     if not SW.fp8_ln:
         return None
     if isinstance(consumer, nn.Linear):
         t = getattr(consumer, "_fp8", None)
         return (t[0], t[1]) if t is not None and fp8_ok(x, consumer.weight) else None
     fc1, fc2 = getattr(consumer, "c_fc", None), getattr(consumer, "c_proj", None)
-    if isinstance(fc1, nn.Linear) and isinstance(fc2, nn.Linear) and _mlp_ok(x, fc1, fc2):
-        return fc1._fp8[0], fc1._fp8[1]
+    if isinstance(fc1, nn.Linear) and isinstance(fc2, nn.Linear):
+        if _swiglu_mlp_ok(x, fc1, fc2) if _is_swiglu_mlp(fc1, fc2) else _mlp_ok(x, fc1, fc2):
+            return fc1._fp8[0], fc1._fp8[1]
     return None
 
 
@@ -293,13 +366,58 @@ def add_layer_norm_fp8(x: torch.Tensor, h: torch.Tensor, ln: nn.Module, state: "
     return s, Fp8Act(token, q, qt)
 
 
+class _AddRMSFp8Fn(torch.autograd.Function):
+    """(s, y) = (x + h, RMSNorm(x + h)) with y emitted as e4m3 (+ transpose) for the consumer's fp8 GEMM
+    (rmsnorm.hip rms_fwd_fp8_kernel): returns s, the zero-storage token standing for y, and the fp8
+    copies. Backward: the token's gradient is dy; dx = dh = RMS'(dy) + ds, as the bf16 add+RMSNorm
+    Function (the same rms_bwd kernel, the same weight gradient)."""
+
+    @staticmethod
+    def forward(ctx, x, h, weight, eps, state_row):
+        D = x.shape[-1]
+        yq, yqt, rstd, s = native().rms_fwd_fp8(x.reshape(-1, D), weight, eps, h.reshape(-1, D), state_row)
+        s = s.view(x.shape)
+        token = torch.empty((), dtype=x.dtype, device=x.device).expand(x.shape)  # never read
+        ctx.mark_non_differentiable(yq, yqt)
+        ctx.set_materialize_grads(False)  # no zero-filled gradients for the fp8 copies
+        ctx.save_for_backward(s, weight, rstd)
+        return s, token, yq, yqt
+
+    @staticmethod
+    def backward(ctx, ds, dy, _dq, _dqt):
+        s, weight, rstd = ctx.saved_tensors
+        if dy is None:
+            dy = torch.zeros_like(s)
+        dres = ds.contiguous() if ds is not None else None
+        dx, dw = native().rms_bwd(dy.contiguous(), s, weight, rstd, dres)
+        return dx, dx, dw, None, None
+
+
+def rms_fp8_ok(x: torch.Tensor, h: torch.Tensor, norm: nn.Module) -> bool:
+    """The shapes and dtypes ``add_rms_norm_fp8`` serves: bf16 rows of width 256 K, K <= 6 (K = 8 keeps
+    the bf16 kernel plus the cast), a multiple of 16 of them, fp32 weight."""
+    w = getattr(norm, "weight", None)
+    D = x.shape[-1]
+    return (use_native(x) and x.dtype == torch.bfloat16 and h.dtype == x.dtype and h.shape == x.shape
+            and w is not None and w.dtype == torch.float32 and w.dim() == 1 and w.shape[0] == D
+            and D % 256 == 0 and 1 <= D // 256 <= 6 and (x.numel() // D) % 16 == 0 and x.numel() > 0)
+
+
+def add_rms_norm_fp8(x: torch.Tensor, h: torch.Tensor, norm: nn.Module, state: "Fp8State", slot: int):
+    """``(s, Fp8Act(norm(s)))`` with ``s = x + h``; the caller checked ``fp8_input_slot`` and ``rms_fp8_ok``."""
+    s, token, q, qt = _AddRMSFp8Fn.apply(x.contiguous(), h.contiguous(), norm.weight, float(norm.eps),
+                                         state.state[slot])
+    return s, Fp8Act(token, q, qt)
+
+
 def enable_fp8(model: nn.Module, history: int = 16, margin: float = 0.0, blocks_only: bool = True) -> Fp8State:
     """Route ``nn.Linear`` layers through fp8 GEMMs (3 scaling slots each: input, weight,
-    output-gradient) — by default those inside transformer ``Block``s (the classifier / LM heads
-    stay bf16). Registers the state on the model and a forward pre-hook that refreshes all scales
-    once per training forward. Returns the state."""
+    output-gradient) — by default those inside transformer ``Block``s and ``LlamaBlock``s (the
+    classifier / LM heads stay bf16). Registers the state on the model and a forward pre-hook that
+    refreshes all scales once per training forward. Returns the state."""
+    from ..models.llama import LlamaBlock
     from ..models.transformer import Block
-    roots = [m for m in model.modules() if isinstance(m, Block)] if blocks_only else [model]
+    roots = [m for m in model.modules() if isinstance(m, (Block, LlamaBlock))] if blocks_only else [model]
     lins = [m for r in roots for m in r.modules() if isinstance(m, nn.Linear)]
     state = Fp8State(3 * len(lins), history, margin)
     p = next(model.parameters(), None)

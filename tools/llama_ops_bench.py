@@ -10,7 +10,12 @@ result written once; the weight, rstd and table are left out) over the measured 
 Whole step: forward + backward + AdamW of llama_medium, bf16 parameters, batch 8 x 1024, native against
 PDT_DISABLE_NATIVE=1, again alternating in one process.
 
-    python tools/llama_ops_bench.py [--rounds 5] [--iters 20] [--steps 5] [--no-step] [--out FILE]
+``--fp8``: instead, the two fp8-emitting producers (rms_fwd_fp8, fp8_swiglu_cast forward and backward)
+against their unfused chains (the bf16 kernel, then fp8_cast_transpose) at the same shapes, and the
+llama_medium step in three configurations alternating in one process: bf16, fp8 with PDT_FP8_LN and
+PDT_FP8_SWIGLU on, fp8 with both off (the per-Linear fp8 path).
+
+    python tools/llama_ops_bench.py [--fp8] [--rounds 5] [--iters 20] [--steps 5] [--no-step] [--out FILE]
 """
 from __future__ import annotations
 
@@ -116,6 +121,91 @@ def bench_kernels(rounds, iters, emit):
          "aten": lambda: torch.autograd.grad(ya, ga, dyf, retain_graph=True)}, rounds, iters)))
 
 
+def _line2(label, nbytes_fused, nbytes_chain, times):
+    fu, ch = times["fused"], times["chain"]
+    mf, mc = statistics.median(fu), statistics.median(ch)
+    return (f"{label:<28} fused {mf * 1e3:8.1f} us ({min(fu) * 1e3:.1f}-{max(fu) * 1e3:.1f})  "
+            f"{nbytes_fused / mf / 1e6:7.0f} GB/s | chain {mc * 1e3:8.1f} us ({min(ch) * 1e3:.1f}-{max(ch) * 1e3:.1f})  "
+            f"{nbytes_chain / mc / 1e6:7.0f} GB/s | chain/fused {mc / mf:5.2f}x")
+
+
+def bench_fp8_producers(rounds, iters, emit):
+    """The fp8-emitting producers against bf16 kernel + fp8_cast_transpose. Bytes: bf16 operands read once,
+    the two e4m3 copies written once (1 B each); the chain also writes and re-reads the bf16 result."""
+    from pytorch_distributed_training_example_amd.ops._native import native
+    nat = native()
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    r = lambda *s: torch.randn(*s, device=dev, generator=g).bfloat16()  # noqa: E731
+    row = torch.zeros(3 + 4, device=dev)
+    row[1], row[2] = 16.0, 1 / 16.0
+    x, h = r(N, D), r(N, D)
+    w = (torch.rand(D, device=dev, generator=g) + 0.5)
+
+    def rms_chain():
+        y, _, _ = nat.rms_fwd(x, w, 1e-5, h)
+        return nat.fp8_cast_transpose(y, row, True)
+    nd = N * D
+    emit(_line2("rmsnorm+add -> e4m3", nd * (3 * ELT + 2), nd * (3 * ELT + 2 * ELT + 2), _alternate(
+        {"fused": lambda: nat.rms_fwd_fp8(x, w, 1e-5, h, row), "chain": rms_chain}, rounds, iters)))
+    gu, dyf = r(N, 2 * F), r(N, F)
+
+    def fwd_chain():
+        return nat.fp8_cast_transpose(nat.swiglu_fwd(gu), row, True)
+
+    def bwd_chain():
+        return nat.fp8_cast_transpose(nat.swiglu_bwd(dyf, gu), row, True)
+    nf = N * F
+    emit(_line2("swiglu fwd -> e4m3", nf * (2 * ELT + 2), nf * (2 * ELT + 2 * ELT + 2), _alternate(
+        {"fused": lambda: nat.fp8_swiglu_cast(gu, None, row), "chain": fwd_chain}, rounds, iters)))
+    emit(_line2("swiglu bwd -> e4m3", nf * (3 * ELT + 4), nf * (3 * ELT + 4 * ELT + 4), _alternate(
+        {"fused": lambda: nat.fp8_swiglu_cast(gu, dyf, row), "chain": bwd_chain}, rounds, iters)))
+
+
+def bench_fp8_step(rounds, steps, emit):
+    """llama_medium, 8 x 1024 tokens, AdamW, eager: bf16 | fp8 fused producers | fp8 per-Linear casts."""
+    from pytorch_distributed_training_example_amd.config import SW
+    from pytorch_distributed_training_example_amd.models import get_model
+    from pytorch_distributed_training_example_amd.models.precision import apply_precision
+    from pytorch_distributed_training_example_amd.optim import FusedAdamW
+
+    def make(precision, fused):
+        torch.manual_seed(0)
+        m = apply_precision(get_model("llama_medium").cuda(), precision)
+        opt = FusedAdamW(m.parameters(), lr=1e-4, weight_decay=0.01)
+        g = torch.Generator().manual_seed(1)
+        x = torch.randint(0, m.cfg.vocab_size, (B, T), generator=g).cuda()
+        y = torch.randint(0, m.cfg.vocab_size, (B, T), generator=g).cuda()
+
+        def step():
+            SW.fp8_ln = SW.fp8_swiglu = fused
+            opt.zero_grad(set_to_none=True)
+            loss = m(x, y)
+            loss.backward()
+            opt.step()
+            return loss
+        return step
+
+    saved = (SW.fp8_ln, SW.fp8_swiglu)
+    cands = {"bf16": make("bf16", True), "fp8 fused": make("fp8", True), "fp8 per-Linear": make("fp8", False)}
+    try:
+        for fn in cands.values():  # warm-up: GEMM algorithm choices, the delayed scales, allocator
+            for _ in range(4):
+                fn()
+        torch.cuda.synchronize()
+        out = {k: [] for k in cands}
+        for _ in range(rounds):
+            for k, fn in cands.items():
+                out[k].append(_time_ms(fn, steps))
+    finally:
+        SW.fp8_ln, SW.fp8_swiglu = saved
+    med = {k: statistics.median(v) for k, v in out.items()}
+    tok = B * T
+    for k, v in out.items():
+        emit(f"llama_medium step AdamW {B}x{T} {k:<15} {med[k]:7.1f} ms ({min(v):.1f}-{max(v):.1f}) "
+             f"{tok / med[k] * 1e3:8.0f} tok/s | bf16 / this {med['bf16'] / med[k]:5.2f}x")
+
+
 def bench_step(rounds, steps, emit):
     from pytorch_distributed_training_example_amd.config import SW
     from pytorch_distributed_training_example_amd.models import get_model
@@ -169,6 +259,8 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=20, help="kernel calls per timed window")
     ap.add_argument("--steps", type=int, default=5, help="training steps per timed window")
     ap.add_argument("--no-step", action="store_true", help="kernels only")
+    ap.add_argument("--fp8", action="store_true", help="the fp8 producers against their unfused chains, and the "
+                    "step in bf16 / fp8 fused / fp8 per-Linear")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -181,9 +273,14 @@ def main(argv=None):
 
     emit(f"# {torch.cuda.get_device_name(0)}; N={N} D={D} F={F} H={H} bf16; median of {a.rounds} alternating rounds "
          f"(min-max), {a.iters} calls / {a.steps} steps per window, device events")
-    bench_kernels(a.rounds, a.iters, emit)
-    if not a.no_step:
-        bench_step(a.rounds, a.steps, emit)
+    if a.fp8:
+        bench_fp8_producers(a.rounds, a.iters, emit)
+        if not a.no_step:
+            bench_fp8_step(a.rounds, a.steps, emit)
+    else:
+        bench_kernels(a.rounds, a.iters, emit)
+        if not a.no_step:
+            bench_step(a.rounds, a.steps, emit)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
