@@ -89,6 +89,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--kv-heads", type=int, default=None, metavar="N",
                    help="llama_* only: N K/V heads shared by groups of query heads (grouped-query attention); N must "
                         "divide the model's head count. Default: the model's own (multi-head for llama_medium / _small)")
+    p.add_argument("--sample-tokens", type=int, default=0, metavar="N",
+                   help="llama_* only: after the last epoch rank 0 generates N tokens on the KV cache and prints "
+                        "'Sample: [ids]' (with --resume and a finished checkpoint: sample it without training)")
+    p.add_argument("--sample-prompt", default="1", metavar="IDS", help="comma-separated prompt token ids (default: 1)")
+    p.add_argument("--sample-temperature", type=float, default=0.0, metavar="T",
+                   help="0 (default): greedy; otherwise sample from softmax(logits / T), seeded from --seed")
+    p.add_argument("--sample-top-k", type=int, default=None, metavar="K", help="sample among the K likeliest tokens")
     p.add_argument("--profile", default=None, metavar="DIR",
                    help="torch.profiler trace of a few steps of epoch 1 into DIR (rank 0), roctx ranges on")
     return p
@@ -124,6 +131,36 @@ def kv_heads_msg(model_name: str, n: int) -> str:
 def kv_heads_ok(model_name: str, n: int) -> bool:
     heads = _llama_heads(model_name)
     return heads is not None and n > 0 and heads % n == 0
+
+
+def sample_args_error(args) -> Optional[str]:
+    """Why the --sample-* flags cannot be served, or None: checked before any process is spawned."""
+    if args.sample_tokens == 0:
+        return None
+    if _llama_heads(args.model) is None:
+        return (f"--sample-tokens: generation runs on the llama_* models' KV cache (model {args.model} has none); "
+                "drop the flag or choose one of them")
+    try:
+        prompt = parse_prompt(args.sample_prompt)
+    except ValueError:
+        return f"--sample-prompt {args.sample_prompt!r}: expected comma-separated token ids, e.g. 1,2,3"
+    from .models.llama import PRESETS, LlamaConfig
+    cfg = LlamaConfig(**PRESETS[args.model])
+    if args.sample_tokens < 0 or len(prompt) + args.sample_tokens > cfg.block_size:
+        return (f"--sample-tokens {args.sample_tokens} after a prompt of {len(prompt)} must be positive and fit "
+                f"{args.model}'s block_size {cfg.block_size}")
+    if not all(0 <= t < cfg.vocab_size for t in prompt):
+        return f"--sample-prompt: token ids must be in [0, {cfg.vocab_size}) for {args.model}"
+    if args.sample_temperature < 0 or (args.sample_top_k is not None and args.sample_top_k < 1):
+        return "--sample-temperature must be >= 0 and --sample-top-k >= 1"
+    return None
+
+
+def parse_prompt(text: str) -> list:
+    ids = [int(t) for t in text.split(",") if t.strip()]
+    if not ids:
+        raise ValueError("empty prompt")
+    return ids
 
 
 def is_token_model(model_name: str) -> bool:
@@ -318,6 +355,13 @@ def run(rank: int, world: int, args) -> dict:
         print(f"profiler trace written to {args.profile}", flush=True)
     if args.save_model:
         save_model(model, args.save_path, rank)
+    if getattr(args, "sample_tokens", 0) and rank == 0:
+        gen = torch.Generator(device=device).manual_seed(args.seed)
+        prompt = torch.tensor([parse_prompt(args.sample_prompt)], device=device)
+        toks = model.generate(prompt, args.sample_tokens, temperature=args.sample_temperature,
+                              top_k=args.sample_top_k, generator=gen)
+        result["sample"] = toks[0].tolist()
+        print(f"Sample: {result['sample']}", flush=True)
     metrics.close()
     return result
 
@@ -374,6 +418,9 @@ def main(argv: Optional[list] = None) -> int:
         raise SystemExit(FP8_LLAMA_MSG)
     if args.kv_heads is not None and not kv_heads_ok(args.model, args.kv_heads):
         raise SystemExit(kv_heads_msg(args.model, args.kv_heads))
+    msg = sample_args_error(args)
+    if msg:
+        raise SystemExit(msg)
     if args.hipgraph:
         # MIOpen reads its solver switches once per process: set before any convolution
         from .engine.graph import make_miopen_capture_safe

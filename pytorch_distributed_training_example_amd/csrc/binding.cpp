@@ -1834,6 +1834,107 @@ void rope_qkv_gqa(Tensor qkv, Tensor cos, Tensor sin, int64_t heads, int64_t kv_
   TORCH_CHECK(rc == 0, "pdt_rope_qkv_gqa failed: ", rc);
 }
 
+// ----------------------------------------------------------------------------- KV-cache decoding (attn_decode.hip)
+// The checks the cache append and the decode attention share: qkv [B, Tn, (heads + 2 kv_heads) * 64] bf16,
+// caches [B, kv_heads, capacity, 64] bf16 contiguous, lens int32 [B], all on the op's device.
+struct DecodeDims {
+  int B, Tn, H, Hkv, cap;
+};
+DecodeDims decode_dims(const Op& op, const Tensor& qkv, const Tensor& k_cache, const Tensor& v_cache,
+                       const Tensor& lens, int64_t heads, int64_t kv_heads) {
+  TORCH_CHECK(qkv.scalar_type() == at::kBFloat16, op.name, ": qkv must be bf16, got ", qkv.scalar_type());
+  TORCH_CHECK(qkv.dim() == 3 && qkv.is_contiguous() && aligned16(qkv), op.name,
+              ": qkv must be a contiguous, 16-byte aligned [B, Tn, (heads + 2 * kv_heads) * 64] tensor");
+  TORCH_CHECK(heads > 0 && kv_heads > 0 && heads % kv_heads == 0, op.name, ": heads = ", heads,
+              " is not a positive multiple of kv_heads = ", kv_heads);
+  TORCH_CHECK(qkv.size(2) == (heads + 2 * kv_heads) * 64, op.name, ": head dim must be 64: last dim ", qkv.size(2),
+              " is not (heads + 2 * kv_heads) * 64 with heads = ", heads, ", kv_heads = ", kv_heads);
+  for (const Tensor* c : {&k_cache, &v_cache}) {
+    TORCH_CHECK(c->defined() && c->device() == op.dev && c->scalar_type() == at::kBFloat16, op.name,
+                ": the caches must be bf16 tensors on ", op.dev);
+    TORCH_CHECK(c->dim() == 4 && c->size(3) == 64, op.name, ": the caches must be [B, kv_heads, capacity, 64] ",
+                "(head dim 64), got ", c->sizes());
+    TORCH_CHECK(c->is_contiguous() && aligned16(*c), op.name, ": the caches must be contiguous and 16-byte aligned");
+  }
+  TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), op.name, ": k_cache and v_cache must have equal sizes");
+  TORCH_CHECK(k_cache.size(0) == qkv.size(0) && k_cache.size(1) == kv_heads && k_cache.size(2) > 0, op.name,
+              ": caches ", k_cache.sizes(), " do not match B = ", qkv.size(0), ", kv_heads = ", kv_heads);
+  TORCH_CHECK(k_cache.size(2) * 128 <= 0x7fffffffLL, op.name, ": capacity too large");
+  TORCH_CHECK(lens.defined() && lens.device() == op.dev && lens.scalar_type() == at::kInt && lens.is_contiguous() &&
+                  lens.dim() == 1 && lens.size(0) == qkv.size(0),
+              op.name, ": lens must be a contiguous int32 [B] tensor on ", op.dev);
+  return {(int)qkv.size(0), (int)qkv.size(1), (int)heads, (int)kv_heads, (int)k_cache.size(2)};
+}
+
+// Rotate the query heads of qkv in place at positions lens[b] + t and write the rotated keys and the values
+// of the Tn new tokens to the caches at those positions (a position outside the cache or the table writes nothing).
+void rope_kv_append(Tensor qkv, Tensor cos, Tensor sin, int64_t heads, int64_t kv_heads, Tensor k_cache,
+                    Tensor v_cache, Tensor lens) {
+  const Op op("rope_kv_append", qkv);
+  const DecodeDims d = decode_dims(op, qkv, k_cache, v_cache, lens, heads, kv_heads);
+  TORCH_CHECK(cos.dim() == 2 && cos.size(1) == 32 && sin.sizes() == cos.sizes(),
+              "rope_kv_append: cos and sin must be [T_max, 32] tables");
+  const int64_t Tmax = cos.size(0);
+  const float* cp = f32_ptr(op, "cos", cos, Tmax * 32);
+  const float* sp = f32_ptr(op, "sin", sin, Tmax * 32);
+  TORCH_CHECK(Tmax > 0 && aligned16(cos) && aligned16(sin), "rope_kv_append: cos / sin must be 16-byte aligned");
+  int rc = pdt_rope_kv_append(bf16_out(qkv), cp, sp, bf16_out(k_cache), bf16_out(v_cache), lens.data_ptr<int>(), d.B,
+                              d.Tn, d.H, d.Hkv, d.cap, (int)Tmax, stream());
+  TORCH_CHECK(rc == 0, "pdt_rope_kv_append failed: ", rc);
+}
+
+// (S, C) of the decode attention for a cache: S splits of C keys (attn_decode.hip pdt_attn_decode_geo).
+// splits = 0: the default rule; group = heads / kv_heads.
+std::vector<int64_t> attn_decode_geo(int64_t B, int64_t kv_heads, int64_t capacity, int64_t splits, int64_t group) {
+  int g[2] = {0, 0};
+  for (int64_t v : {B, kv_heads, capacity, splits, group})
+    TORCH_CHECK(v >= 0 && v <= 0x7fffffffLL, "attn_decode_geo: argument ", v, " outside [0, 2^31)");
+  int rc = pdt_attn_decode_geo((int)B, (int)kv_heads, (int)capacity, (int)splits, (int)group, g);
+  TORCH_CHECK(rc == 0, "attn_decode_geo: bad arguments B = ", B, ", kv_heads = ", kv_heads, ", capacity = ", capacity,
+              ", splits = ", splits, ", group = ", group);
+  return {g[0], g[1]};
+}
+
+// Decode attention of one new token per sequence: qkv [B, 1, (heads + 2 kv_heads) * 64] with Q rotated, the
+// caches already holding the token at position lens[b]. out [B, 1, heads * 64] bf16; lse (optional) fp32
+// [B, heads]; o_part / ml_part: fp32 scratch of at least B * heads * S * 64 and B * heads * S * 2 elements (needed
+// when S > 1). Returns (S, C), the geometry that ran.
+std::vector<int64_t> attn_decode(Tensor qkv, Tensor k_cache, Tensor v_cache, Tensor lens, int64_t heads,
+                                 int64_t kv_heads, double scale, int64_t splits, Tensor out,
+                                 c10::optional<Tensor> o_part, c10::optional<Tensor> ml_part,
+                                 c10::optional<Tensor> lse) {
+  const Op op("attn_decode", qkv);
+  const DecodeDims d = decode_dims(op, qkv, k_cache, v_cache, lens, heads, kv_heads);
+  TORCH_CHECK(d.Tn == 1, "attn_decode: one new token per sequence, got Tn = ", d.Tn);
+  TORCH_CHECK(scale > 0 && splits >= 0, "attn_decode: scale must be positive and splits >= 0");
+  TORCH_CHECK(out.defined() && out.device() == op.dev && out.scalar_type() == at::kBFloat16 && out.is_contiguous() &&
+                  out.numel() == (int64_t)d.B * d.H * 64 && aligned16(out),
+              "attn_decode: out must be a contiguous bf16 [B, 1, heads * 64] tensor on ", op.dev);
+  const std::vector<int64_t> geo = attn_decode_geo(d.B, d.Hkv, d.cap, splits, d.H / d.Hkv);
+  const int64_t S = geo[0], rows = (int64_t)d.B * d.H;
+  float* lp = opt_f32_ptr(op, "lse", lse, rows);
+  float *op_ptr = nullptr, *ml_ptr = nullptr;
+  if (S > 1) {
+    TORCH_CHECK(has(o_part) && has(ml_part), "attn_decode: S = ", S, " splits need the o_part / ml_part scratch");
+    for (const Tensor* t : {&*o_part, &*ml_part})
+      TORCH_CHECK(t->device() == op.dev && t->scalar_type() == at::kFloat && t->is_contiguous() && aligned16(*t),
+                  "attn_decode: the scratch must be contiguous, 16-byte aligned fp32 on ", op.dev);
+    TORCH_CHECK(o_part->numel() >= rows * S * 64 && ml_part->numel() >= rows * S * 2, "attn_decode: scratch too small for S = ",
+                S, ": o_part ", o_part->numel(), " < ", rows * S * 64, " or ml_part ", ml_part->numel(), " < ", rows * S * 2);
+    op_ptr = o_part->data_ptr<float>();
+    ml_ptr = ml_part->data_ptr<float>();
+  }
+  int rc = pdt_attn_decode(bf16_ptr(qkv), qkv.stride(0), bf16_ptr(k_cache), bf16_ptr(v_cache), lens.data_ptr<int>(),
+                           op_ptr, ml_ptr, bf16_out(out), lp, d.B, d.H, d.Hkv, d.cap, (int)S, (int)geo[1], (float)scale,
+                           stream());
+  TORCH_CHECK(rc == 0, "pdt_attn_decode failed: ", rc);
+  if (S > 1) {
+    rc = pdt_attn_decode_combine(op_ptr, ml_ptr, bf16_out(out), lp, d.B, d.H, (int)S, stream());
+    TORCH_CHECK(rc == 0, "pdt_attn_decode_combine failed: ", rc);
+  }
+  return geo;
+}
+
 // y = silu(gu[:, :F]) * gu[:, F:] for gu [..., 2F] (swiglu.hip)
 Tensor swiglu_fwd(Tensor gu, c10::optional<Tensor> y_out) {
   const Op op("swiglu_fwd", gu);
@@ -2754,6 +2855,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("conj") = false);
   m.def("rope_qkv_gqa", &rope_qkv_gqa, py::arg("qkv"), py::arg("cos"), py::arg("sin"), py::arg("heads"),
         py::arg("kv_heads"), py::arg("conj") = false);
+  m.def("rope_kv_append", &rope_kv_append, py::arg("qkv"), py::arg("cos"), py::arg("sin"), py::arg("heads"),
+        py::arg("kv_heads"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"));
+  m.def("attn_decode_geo", &attn_decode_geo, py::arg("B"), py::arg("kv_heads"), py::arg("capacity"),
+        py::arg("splits") = 0, py::arg("group") = 1);
+  m.def("attn_decode", &attn_decode, py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"),
+        py::arg("heads"), py::arg("kv_heads"), py::arg("scale"), py::arg("splits"), py::arg("out"),
+        py::arg("o_part") = py::none(), py::arg("ml_part") = py::none(), py::arg("lse") = py::none());
   m.def("swiglu_fwd", &swiglu_fwd, py::arg("gu"), py::arg("y_out") = py::none());
   m.def("swiglu_bwd", &swiglu_bwd, py::arg("dy"), py::arg("gu"), py::arg("dgu_out") = py::none());
   py::class_<P2PComm>(m, "P2PComm")

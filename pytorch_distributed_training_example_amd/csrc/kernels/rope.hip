@@ -15,6 +15,7 @@
 // those 16 elements, so the update is safe in place.
 #include "../common.h"
 #include "../launchers.h"
+#include "../rope_math.h"
 
 using namespace pdt;
 
@@ -31,22 +32,11 @@ __global__ __launch_bounds__(256) void rope_qkv_kernel(uint16_t* __restrict__ qk
   const int head = r >> 2, q = r & 3;
   const int t = (int)(tok % T);
   uint16_t* p = qkv + tok * (int64_t)64 * AH + head * 64 + q * 8;
-  float lo[8], hi[8], c[8], s[8];
+  float lo[8], hi[8];
   ld8_bf16(p, lo);
   ld8_bf16(p + 32, hi);
-  const float* cr = cs + (int64_t)t * 32 + q * 8;
-  const float* sr = sn + (int64_t)t * 32 + q * 8;
-  Vec4<float>::ld(cr, 0, *reinterpret_cast<float(*)[4]>(c));
-  Vec4<float>::ld(cr, 4, *reinterpret_cast<float(*)[4]>(c + 4));
-  Vec4<float>::ld(sr, 0, *reinterpret_cast<float(*)[4]>(s));
-  Vec4<float>::ld(sr, 4, *reinterpret_cast<float(*)[4]>(s + 4));
-  float olo[8], ohi[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float sj = s[j] * sign;
-    olo[j] = lo[j] * c[j] - hi[j] * sj;
-    ohi[j] = hi[j] * c[j] + lo[j] * sj;
-  }
+  float olo[8], ohi[8];  // the arithmetic is rope_math.h's, shared with the cache append (attn_decode.hip)
+  rope_rotate8(lo, hi, cs + (int64_t)t * 32 + q * 8, sn + (int64_t)t * 32 + q * 8, sign, olo, ohi);
   st8_bf16(p, olo);
   st8_bf16(p + 32, ohi);
 }

@@ -48,6 +48,17 @@ int pdt_attn_bwd_gqa(const uint16_t* dout, const int64_t* dos, const uint16_t* q
                      const int64_t* os, const float* lse, float* delta, uint16_t* dq, uint16_t* dk, uint16_t* dv,
                      const int64_t* gs, int B, int H, int Hkv, int T, int Dh, int causal, float scale, hipStream_t s);
 
+// kernels/attn_decode.hip: KV-cache decoding. k_cache, v_cache [B, Hkv, capacity, 64] bf16; lens int32 [B] on
+// the device (valid positions per sequence), never read on the host.
+int pdt_rope_kv_append(uint16_t* qkv, const float* cos, const float* sin, uint16_t* k_cache, uint16_t* v_cache,
+                       const int* lens, int B, int Tn, int H, int Hkv, int capacity, int Tmax, hipStream_t s);
+int pdt_attn_decode_geo(int B, int Hkv, int capacity, int splits_override, int G, int* geo2);
+int pdt_attn_decode(const uint16_t* qkv, int64_t q_sb, const uint16_t* k_cache, const uint16_t* v_cache,
+                    const int* lens, float* o_part, float* ml_part, uint16_t* out, float* lse, int B, int H, int Hkv,
+                    int capacity, int S, int C, float scale, hipStream_t s);
+int pdt_attn_decode_combine(const float* o_part, const float* ml_part, uint16_t* out, float* lse, int B, int H, int S,
+                            hipStream_t s);
+
 // kernels/batchnorm.hip
 int64_t pdt_bn_workspace_floats(int64_t M, int C);
 void pdt_bn_tiles_fused(int on);

@@ -31,12 +31,13 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..config import SW
-from ..ops.attention import attention_qkv
+from ..ops.attention import attention_decode, attention_qkv
 from ..ops.cross_entropy import cross_entropy
 from ..ops.fp8 import Fp8Act, add_rms_norm_fp8, fp8_input_slot, fp8_linear, fp8_ok, fp8_swiglu_mlp, rms_fp8_ok
+from ..ops.kv_cache import KVCache
 from ..ops.linear import linear
 from ..ops.rmsnorm import RMSNorm, add_rms_norm
-from ..ops.rope import RotaryTable, rope_qkv_
+from ..ops.rope import RotaryTable, rope_append_, rope_qkv_
 from ..ops.swiglu import swiglu
 from .transformer import init_weights
 
@@ -85,10 +86,31 @@ class LlamaAttention(nn.Module):
         self.c_attn = nn.Linear(dim, (heads + 2 * kv_heads) * HEAD_DIM, bias=False)  # q, then k, then v rows
         self.c_proj = nn.Linear(dim, dim, bias=False)
 
-    def forward(self, x: torch.Tensor, rope: RotaryTable) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, rope: RotaryTable, cache: KVCache | None = None, layer: int = 0) -> torch.Tensor:
+        if cache is not None:
+            return self._forward_cached(x, rope, cache, layer)
         qkv = _linear(x, self.c_attn)  # [B, T, (H + 2 Hkv) 64]; its backward needs x and W only, so
         qkv = rope_qkv_(qkv, rope.cos, rope.sin, self.heads, self.kv_heads)  # Q and K are rotated in place
         y = attention_qkv(qkv, self.heads, causal=True, kv_heads=self.kv_heads)
+        return _linear(y, self.c_proj)
+
+    def _forward_cached(self, x, rope, cache: KVCache, layer: int):
+        """Inference on a KV cache: the Tn new rows are rotated at positions lens[b] + t and appended (one
+        kernel); a prefill (Tn > 1, empty cache) then runs the causal flash forward on them, a decode step
+        (Tn == 1) the split-KV kernel on the cache. ``cache.lens`` is advanced by the caller after the last layer."""
+        Tn = x.shape[1]
+        if Tn > 1 and cache.bound > 0:
+            raise ValueError(f"{Tn} new tokens onto a cache that may hold {cache.bound} positions: chunked prefill "
+                             "is not supported (prefill an empty cache, then decode one token at a time)")
+        cache.require(Tn, rope.cos.shape[0])
+        qkv = _linear(x, self.c_attn)
+        qkv = rope_append_(qkv, rope.cos, rope.sin, self.heads, self.kv_heads, cache.k[layer], cache.v[layer],
+                           cache.lens)
+        if Tn > 1:
+            y = attention_qkv(qkv, self.heads, causal=True, kv_heads=self.kv_heads)
+        else:
+            y = attention_decode(qkv, cache.k[layer], cache.v[layer], cache.lens, self.heads, self.kv_heads,
+                                 cache=cache)
         return _linear(y, self.c_proj)
 
 
@@ -116,25 +138,26 @@ class LlamaBlock(nn.Module):
         self.ln_2 = RMSNorm(cfg.n_embd, eps=cfg.eps)
         self.mlp = LlamaMLP(cfg.n_embd, cfg.ffn)
 
-    def forward(self, x: torch.Tensor, rope: RotaryTable) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, rope: RotaryTable, cache: KVCache | None = None, layer: int = 0) -> torch.Tensor:
         """Unfused path (PDT_FUSED_ADDLN=0, or a block called on its own)."""
-        x = x + self.attn(self.ln_1(x), rope)
+        x = x + self.attn(self.ln_1(x), rope, cache, layer)
         return x + self.mlp(self.ln_2(x))
 
 
-def run_llama_blocks(blocks, x: torch.Tensor, final_norm: RMSNorm, rope: RotaryTable) -> torch.Tensor:
+def run_llama_blocks(blocks, x: torch.Tensor, final_norm: RMSNorm, rope: RotaryTable,
+                     cache: KVCache | None = None) -> torch.Tensor:
     """``final_norm(blocks(x))`` with every residual add fused into the RMSNorm that follows it (the
     block's ln_2, the next block's ln_1, finally ``final_norm``), as ``transformer.run_blocks`` does
     with LayerNorm: one add+RMSNorm kernel per residual step forward, one backward kernel that also
     accumulates the residual stream's gradient."""
     blocks = list(blocks)
     if not blocks or not SW.fused_addln:
-        for blk in blocks:
-            x = blk(x, rope)
+        for i, blk in enumerate(blocks):
+            x = blk(x, rope, cache, i)
         return final_norm(x)
     y = blocks[0].ln_1(x)
     for i, blk in enumerate(blocks):
-        x, y = _add_norm(x, blk.attn(y, rope), blk.ln_2, blk.mlp)
+        x, y = _add_norm(x, blk.attn(y, rope, cache, i), blk.ln_2, blk.mlp)
         nxt, cons = (blocks[i + 1].ln_1, blocks[i + 1].attn.c_attn) if i + 1 < len(blocks) else (final_norm, None)
         x, y = _add_norm(x, blk.mlp(y), nxt, cons)
     return y
@@ -174,6 +197,107 @@ class Llama(nn.Module):
         if targets is None:
             return logits
         return cross_entropy(logits.reshape(-1, logits.shape[-1]), targets.reshape(-1))
+
+    # ------------------------------------------------------------------ generation on a KV cache
+    def new_cache(self, batch: int, capacity: int | None = None) -> KVCache:
+        """A KV cache for ``batch`` sequences of up to ``capacity`` (default ``block_size``) positions, on the
+        model's device and in its dtype."""
+        w = self.lm_head.weight
+        return KVCache(self.cfg.n_layer, batch, self.cfg.kv_heads, capacity or self.cfg.block_size, w.device, w.dtype)
+
+    def _check_cache(self, cache: KVCache, batch: int) -> None:
+        if (cache.n_layer, cache.kv_heads) != (self.cfg.n_layer, self.cfg.kv_heads) or cache.batch != batch:
+            raise ValueError(f"cache for {cache.n_layer} layers x {cache.kv_heads} K/V heads x batch {cache.batch} "
+                             f"does not fit this model ({self.cfg.n_layer} x {self.cfg.kv_heads}) at batch {batch}")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise RuntimeError("the KV-cache path is inference only: call it under torch.no_grad()")
+
+    def prefill(self, idx: torch.Tensor, cache: KVCache, prompt_lens=None) -> torch.Tensor:
+        """Run the prompts ``idx`` [B, T0] into an empty ``cache``; returns the logits [B, V] of every
+        sequence's last prompt position (the LM head runs on those B rows only). Ragged prompts are
+        right-padded and ``prompt_lens`` (B lengths in [1, T0]: a sequence, a CPU tensor, or a device tensor,
+        which is clamped to that range rather than read) gives their lengths: all T0 rows are appended,
+        then ``cache.lens = prompt_lens``; causality keeps the padding out of the real positions and the next
+        append overwrites it."""
+        B, T0 = idx.shape
+        self._check_cache(cache, B)
+        x = F.embedding(idx, self.transformer.wte.weight)
+        x = run_llama_blocks(self.transformer.h, x, self.transformer.ln_f, self.rope, cache)
+        if prompt_lens is None:
+            cache.advance(T0)
+            last = x[:, -1]
+        else:
+            if not isinstance(prompt_lens, torch.Tensor):
+                prompt_lens = torch.as_tensor(prompt_lens, dtype=torch.int32)
+            if prompt_lens.device.type == "cpu":
+                if prompt_lens.shape != (B,) or int(prompt_lens.min()) < 1 or int(prompt_lens.max()) > T0:
+                    raise ValueError(f"prompt_lens must be {B} lengths in [1, {T0}], got {prompt_lens.tolist()}")
+                prompt_lens = prompt_lens.to(idx.device)
+            else:
+                prompt_lens = prompt_lens.clamp(1, T0)
+            cache.set_lens(prompt_lens.to(torch.int32), bound=T0)
+            last = x.gather(1, (prompt_lens.long() - 1)[:, None, None].expand(B, 1, x.shape[-1]))[:, 0]
+        return linear(last, self.lm_head.weight)
+
+    def decode_step(self, tok: torch.Tensor, cache: KVCache) -> torch.Tensor:
+        """One token per sequence: ``tok`` [B] sits at position ``cache.lens[b]``; returns the logits [B, V]
+        of the next one and advances ``cache.lens`` on the device after the last layer. Nothing here reads
+        the device, so the step can be captured with ``torch.cuda.graph`` and replayed."""
+        self._check_cache(cache, tok.shape[0])
+        x = F.embedding(tok[:, None], self.transformer.wte.weight)
+        x = run_llama_blocks(self.transformer.h, x, self.transformer.ln_f, self.rope, cache)
+        cache.advance(1)
+        return linear(x[:, 0], self.lm_head.weight)
+
+    @torch.no_grad()
+    def generate(self, idx: torch.Tensor, max_new_tokens: int, temperature: float = 0.0, top_k: int | None = None,
+                 eos_token: int | None = None, generator: torch.Generator | None = None, prompt_lens=None,
+                 return_logits: bool = False):
+        """Sample ``max_new_tokens`` tokens after the prompts ``idx`` [B, T0] (right-padded when
+        ``prompt_lens`` is given); returns them as [B, max_new_tokens] on the device, with ``return_logits``
+        also the logits [B, max_new_tokens, V] each was drawn from. Greedy at ``temperature`` 0, otherwise
+        ``torch.multinomial`` of softmax(logits / temperature) (restricted to the ``top_k`` largest) on
+        ``generator``. With ``eos_token`` everything after a sequence's first EOS is EOS (a device-side mask:
+        no step reads a token on the host). Runs in ``eval()`` and restores the mode."""
+        B, T0 = idx.shape
+        if max_new_tokens < 1:
+            raise ValueError(f"max_new_tokens must be positive, got {max_new_tokens}")
+        if T0 + max_new_tokens > self.cfg.block_size:
+            raise ValueError(f"prompt of {T0} + {max_new_tokens} new tokens exceeds block_size {self.cfg.block_size} "
+                             "(the RoPE table)")
+        was_training = self.training
+        self.eval()
+        try:
+            cache = self.new_cache(B, T0 + max_new_tokens)
+            logits = self.prefill(idx, cache, prompt_lens)
+            toks, all_logits = [], []
+            done = torch.zeros(B, dtype=torch.bool, device=idx.device)
+            for i in range(max_new_tokens):
+                tok = _sample(logits, temperature, top_k, generator)
+                if eos_token is not None:
+                    tok = torch.where(done, torch.full_like(tok, eos_token), tok)
+                    done = done | (tok == eos_token)
+                toks.append(tok)
+                if return_logits:
+                    all_logits.append(logits)
+                if i + 1 < max_new_tokens:
+                    logits = self.decode_step(tok, cache)
+        finally:
+            self.train(was_training)
+        out = torch.stack(toks, 1)
+        return (out, torch.stack(all_logits, 1)) if return_logits else out
+
+
+def _sample(logits: torch.Tensor, temperature: float, top_k: int | None, generator) -> torch.Tensor:
+    """One token id per row of ``logits`` [B, V]: the argmax at temperature 0, else a draw from
+    softmax(logits / temperature) over the ``top_k`` largest logits (all of them when None)."""
+    if temperature <= 0.0:
+        return logits.argmax(-1)
+    z = logits.float() / temperature
+    if top_k is not None and top_k < z.shape[-1]:
+        kth = z.topk(top_k, dim=-1).values[:, -1:]
+        z = z.masked_fill(z < kth, float("-inf"))
+    return torch.multinomial(torch.softmax(z, -1), 1, generator=generator)[:, 0]
 
 
 def from_hf_state_dict(sd: Dict[str, torch.Tensor], n_kv_head: int | None = None) -> Dict[str, torch.Tensor]:

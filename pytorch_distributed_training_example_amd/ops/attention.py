@@ -192,6 +192,77 @@ def attention_qkv(qkv: torch.Tensor, heads: int, causal: bool = False, dropout_p
     return y.transpose(1, 2).reshape(B, T, heads * dh)
 
 
+# ----------------------------------------------------------------------------- decoding on a KV cache
+DECODE_STATS = {"native_calls": 0, "geo": None}  # launches of the decode kernel and the last (S, C) it ran with
+
+
+def attention_decode_geo(batch: int, kv_heads: int, capacity: int, splits: int | None = None, group: int = 1):
+    """(S, C) of the split-KV decode kernel for a cache: S splits of C keys each (C % 64 == 0, S =
+    ceil(capacity / C)). A function of the cache's shape, never of ``lens``. ``splits``: ask for that many
+    instead of the default rule; ``group`` = heads / kv_heads."""
+    S, C = native().attn_decode_geo(batch, kv_heads, capacity, int(splits or 0), group)
+    return int(S), int(C)
+
+
+def _decode_reference(qkv, k_cache, v_cache, lens, heads, kv_heads, scale):
+    B, _, _ = qkv.shape
+    cap, dh = k_cache.shape[2], k_cache.shape[3]
+    G = heads // kv_heads
+    q = qkv[:, 0, :heads * dh].reshape(B, heads, dh).float()
+    valid = torch.arange(cap, device=qkv.device)[None, :] <= lens[:, None]  # [B, cap]: keys 0 .. lens[b]
+    k = k_cache.float().repeat_interleave(G, dim=1)
+    # rows past lens[b] may hold anything, NaN included: they are taken out, not multiplied by zero
+    v = torch.where(valid[:, None, :, None], v_cache.float(), torch.zeros((), device=qkv.device))
+    s = torch.einsum("bhd,bhkd->bhk", q, k) * scale
+    s = s.masked_fill(~valid[:, None, :], float("-inf"))
+    lse = torch.logsumexp(s, -1)
+    p = torch.exp(s - lse[..., None])
+    o = torch.einsum("bhk,bhkd->bhd", p, v.repeat_interleave(G, dim=1))
+    return o.to(qkv.dtype).reshape(B, 1, heads * dh), lse
+
+
+def attention_decode(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, lens: torch.Tensor,
+                     heads: int, kv_heads: int | None = None, scale: float | None = None,
+                     splits: int | None = None, cache=None, return_lse: bool = False):
+    """Attention of one new token per sequence on a KV cache: ``qkv`` [B, 1, (H + 2·Hkv)·64] with Q rotated
+    (``rope_append_`` has already written the token's K and V at position ``lens[b]``), ``k_cache`` /
+    ``v_cache`` [B, Hkv, capacity, 64], ``lens`` int32 [B] on qkv's device, read there. Returns [B, 1, H·64]
+    (and the LSE [B, H] with ``return_lse``). Inference only: raises when a gradient is required.
+
+    bf16 GPU tensors run the split-KV kernel (csrc/kernels/attn_decode.hip); ``splits`` overrides its number
+    of splits and ``cache`` (a ``KVCache``) lends the scratch of the partials, so that no step allocates it.
+    CPU, fp32 and ``PDT_DISABLE_NATIVE=1`` take the PyTorch reference."""
+    kv_heads = heads if kv_heads is None else kv_heads
+    if kv_heads <= 0 or heads % kv_heads != 0:
+        raise ValueError(f"attention_decode: heads = {heads} is not a positive multiple of kv_heads = {kv_heads}")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (qkv, k_cache, v_cache)):
+        raise RuntimeError("attention_decode: inference only (run it under torch.no_grad())")
+    if qkv.dim() != 3 or qkv.shape[1] != 1 or qkv.shape[2] % (heads + 2 * kv_heads) != 0:
+        raise ValueError(f"attention_decode: qkv {tuple(qkv.shape)} is not [B, 1, (heads + 2·kv_heads)·Dh]")
+    dh = qkv.shape[2] // (heads + 2 * kv_heads)
+    scale = scale if scale is not None else 1.0 / math.sqrt(dh)
+    if use_native(qkv) and qkv.dtype == torch.bfloat16:  # head dim 64 and the layouts: the binding's checks
+        B, cap = qkv.shape[0], k_cache.shape[2] if k_cache.dim() == 4 else 0
+        out = torch.empty(B, 1, heads * dh, device=qkv.device, dtype=qkv.dtype)
+        lse = torch.empty(B, heads, device=qkv.device, dtype=torch.float32) if return_lse else None
+        o_part = ml_part = None
+        if cap > 0 and k_cache.dim() == 4 and dh == 64:
+            S, _ = attention_decode_geo(B, kv_heads, cap, splits, heads // kv_heads)
+            if S > 1:
+                if cache is not None:
+                    o_part, ml_part = cache.scratch(heads, S)
+                else:
+                    o_part = torch.empty(B, heads, S, 64, device=qkv.device, dtype=torch.float32)
+                    ml_part = torch.empty(B, heads, S, 2, device=qkv.device, dtype=torch.float32)
+        geo = native().attn_decode(qkv, k_cache, v_cache, lens, heads, kv_heads, scale, int(splits or 0), out,
+                                   o_part, ml_part, lse)
+        DECODE_STATS["native_calls"] += 1
+        DECODE_STATS["geo"] = (int(geo[0]), int(geo[1]))
+        return (out, lse) if return_lse else out
+    out, lse = _decode_reference(qkv, k_cache, v_cache, lens, heads, kv_heads, scale)
+    return (out, lse) if return_lse else out
+
+
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False,
               dropout_p: float = 0.0, scale: float | None = None) -> torch.Tensor:
     """Unpacked [B, H, T, Dh] interface (SDPA-compatible)."""

@@ -111,3 +111,64 @@ def rope_qkv_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, heads: in
     if torch.is_grad_enabled() and qkv.requires_grad:
         return _RopeQKVFn.apply(qkv, cos, sin, heads, kv_heads)
     return _rotate_(qkv, cos, sin, heads, kv_heads, False)
+
+
+# ----------------------------------------------------------------------------- decoding: rotate at an offset + cache write
+APPEND_STATS = {"native_calls": 0}  # launches of the append kernel
+
+
+def _append_reference_(qkv, cos, sin, heads, kv_heads, k_cache, v_cache, lens):
+    """The kernel's contract in tensor ops, without a host read of ``lens``: row (b, t) sits at position
+    p = lens[b] + t; a row whose p is outside the cache or the table changes nothing."""
+    B, Tn, C = qkv.shape
+    dh = C // (heads + 2 * kv_heads)
+    half = dh // 2
+    cap = k_cache.shape[2]
+    limit = min(cap, cos.shape[0])
+    pos = lens.long()[:, None] + torch.arange(Tn, device=qkv.device)[None, :]  # [B, Tn]
+    ok = (pos >= 0) & (pos < limit)
+    pc = pos.clamp(0, limit - 1)
+    x = qkv.view(B, Tn, heads + 2 * kv_heads, dh)
+    qk = x[:, :, :heads + kv_heads]
+    lo, hi = qk[..., :half].float(), qk[..., half:].float()
+    c, s = cos.float()[pc][:, :, None, :], sin.float()[pc][:, :, None, :]
+    rot = torch.cat([lo * c - hi * s, hi * c + lo * s], -1).to(qkv.dtype)  # [B, Tn, H + Hkv, dh]
+    x[:, :, :heads + kv_heads] = torch.where(ok[:, :, None, None], rot, x[:, :, :heads + kv_heads])
+    # cache position j of sequence b takes new row t = j - lens[b] when 0 <= t < Tn (a gather: no write races)
+    t = torch.arange(cap, device=qkv.device)[None, :] - lens.long()[:, None]  # [B, cap]
+    take = (t >= 0) & (t < Tn) & (torch.arange(cap, device=qkv.device)[None, :] < limit)
+    idx = t.clamp(0, Tn - 1)[:, None, :, None].expand(B, kv_heads, cap, dh)
+    for cache_t, new in ((k_cache, rot[:, :, heads:]), (v_cache, x[:, :, heads + kv_heads:])):
+        rows = new.permute(0, 2, 1, 3).gather(2, idx)  # [B, Hkv, cap, dh]
+        cache_t.copy_(torch.where(take[:, None, :, None], rows.to(cache_t.dtype), cache_t))
+    return qkv
+
+
+def rope_append_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, heads: int, kv_heads: int | None,
+                 k_cache: torch.Tensor, v_cache: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+    """The rotary embedding at a per-sequence offset, fused with the KV-cache write. ``qkv`` [B, Tn,
+    (heads + 2·kv_heads)·Dh] holds ``c_attn``'s output for Tn new tokens; row (b, t) sits at position
+    p = lens[b] + t (``lens`` int32 [B] on qkv's device, read there). The query and key heads are rotated in
+    place with cos/sin[p], as ``rope_qkv_`` rotates row p of a full sequence; the rotated key heads and the
+    untouched value heads also go to ``k_cache[b, :, p]`` / ``v_cache[b, :, p]`` ([B, kv_heads, capacity, Dh],
+    contiguous).
+    A row whose p falls outside the cache or the table writes nothing. Returns ``qkv``; ``lens`` is not
+    advanced. Inference only: raises when a gradient is required."""
+    kv_heads = heads if kv_heads is None else kv_heads
+    if kv_heads <= 0 or heads % kv_heads != 0:
+        raise ValueError(f"rope_append_: heads = {heads} is not a positive multiple of kv_heads = {kv_heads}")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (qkv, k_cache, v_cache)):
+        raise RuntimeError("rope_append_: inference only (run it under torch.no_grad())")
+    if qkv.dim() != 3 or qkv.shape[-1] % (heads + 2 * kv_heads) != 0 or not qkv.is_contiguous():
+        raise ValueError(f"rope_append_: qkv {tuple(qkv.shape)} is not a contiguous [B, Tn, (heads + 2·kv_heads)·Dh] "
+                         f"with heads = {heads}, kv_heads = {kv_heads}")
+    if use_native(qkv) and qkv.dtype == torch.bfloat16:  # head dim 64, layouts, lens: the binding's checks
+        native().rope_kv_append(qkv, cos, sin, heads, kv_heads, k_cache, v_cache, lens)
+        APPEND_STATS["native_calls"] += 1
+        return qkv
+    dh = qkv.shape[-1] // (heads + 2 * kv_heads)
+    if k_cache.shape != v_cache.shape or k_cache.dim() != 4 or k_cache.shape[0] != qkv.shape[0] \
+            or k_cache.shape[1] != kv_heads or k_cache.shape[3] != dh:
+        raise ValueError(f"rope_append_: caches {tuple(k_cache.shape)}, {tuple(v_cache.shape)} are not "
+                         f"[{qkv.shape[0]}, {kv_heads}, capacity, {dh}]")
+    return _append_reference_(qkv, cos, sin, heads, kv_heads, k_cache, v_cache, lens)
