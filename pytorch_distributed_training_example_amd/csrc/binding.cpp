@@ -1935,6 +1935,63 @@ std::vector<int64_t> attn_decode(Tensor qkv, Tensor k_cache, Tensor v_cache, Ten
   return geo;
 }
 
+// (S, C, NB, NT) of the multi-token append attention (attn_decode.hip pdt_attn_extend_geo): NB blocks of NT
+// 16-column tiles over the group * Tn query columns of a K/V head, S splits of C keys. splits = 0: the default rule.
+std::vector<int64_t> attn_extend_geo(int64_t B, int64_t kv_heads, int64_t capacity, int64_t Tn, int64_t group,
+                                     int64_t splits) {
+  int g[4] = {0, 0, 0, 0};
+  for (int64_t v : {B, kv_heads, capacity, Tn, group, splits})
+    TORCH_CHECK(v >= 0 && v <= 0x7fffffffLL, "attn_extend_geo: argument ", v, " outside [0, 2^31)");
+  int rc = pdt_attn_extend_geo((int)B, (int)kv_heads, (int)capacity, (int)Tn, (int)group, (int)splits, g);
+  TORCH_CHECK(rc == 0, "attn_extend_geo: ", rc == -2 ? "too many column blocks for one launch" : "bad arguments", ": B = ",
+              B, ", kv_heads = ", kv_heads, ", capacity = ", capacity, ", Tn = ", Tn, ", group = ", group,
+              ", splits = ", splits);
+  return {g[0], g[1], g[2], g[3]};
+}
+
+// Attention of Tn new tokens per sequence: qkv [B, Tn, (heads + 2 kv_heads) * 64] with Q rotated, the caches
+// already holding the tokens at positions lens[b] + t; query (b, t) sees keys 0 .. lens[b] + t. out [B, Tn,
+// heads * 64] bf16; lse (optional) fp32 [B, Tn, heads]; o_part / ml_part: fp32 scratch of at least B * Tn * heads *
+// S * 64 and B * Tn * heads * S * 2 elements (needed when S > 1). Returns (S, C, NB, NT), the geometry that ran.
+std::vector<int64_t> attn_extend(Tensor qkv, Tensor k_cache, Tensor v_cache, Tensor lens, int64_t heads,
+                                 int64_t kv_heads, double scale, int64_t splits, Tensor out,
+                                 c10::optional<Tensor> o_part, c10::optional<Tensor> ml_part,
+                                 c10::optional<Tensor> lse) {
+  const Op op("attn_extend", qkv);
+  const DecodeDims d = decode_dims(op, qkv, k_cache, v_cache, lens, heads, kv_heads);
+  TORCH_CHECK(d.Tn >= 1, "attn_extend: at least one new token per sequence, got Tn = ", d.Tn);
+  TORCH_CHECK(scale > 0 && splits >= 0, "attn_extend: scale must be positive and splits >= 0");
+  const int64_t rows = (int64_t)d.B * d.Tn * d.H;
+  TORCH_CHECK((int64_t)d.B * d.Tn <= 0x7fffffffLL, "attn_extend: B * Tn = ", (int64_t)d.B * d.Tn, " is too large");
+  TORCH_CHECK(out.defined() && out.device() == op.dev && out.scalar_type() == at::kBFloat16 && out.is_contiguous() &&
+                  out.numel() == rows * 64 && aligned16(out),
+              "attn_extend: out must be a contiguous bf16 [B, Tn, heads * 64] tensor on ", op.dev);
+  const std::vector<int64_t> geo = attn_extend_geo(d.B, d.Hkv, d.cap, d.Tn, d.H / d.Hkv, splits);
+  const int64_t S = geo[0];
+  float* lp = opt_f32_ptr(op, "lse", lse, rows);
+  float *op_ptr = nullptr, *ml_ptr = nullptr;
+  if (S > 1) {
+    TORCH_CHECK(has(o_part) && has(ml_part), "attn_extend: S = ", S, " splits need the o_part / ml_part scratch");
+    for (const Tensor* t : {&*o_part, &*ml_part})
+      TORCH_CHECK(t->device() == op.dev && t->scalar_type() == at::kFloat && t->is_contiguous() && aligned16(*t),
+                  "attn_extend: the scratch must be contiguous, 16-byte aligned fp32 on ", op.dev);
+    TORCH_CHECK(o_part->numel() >= rows * S * 64 && ml_part->numel() >= rows * S * 2, "attn_extend: scratch too small for S = ",
+                S, ", Tn = ", d.Tn, ": o_part ", o_part->numel(), " < ", rows * S * 64, " or ml_part ", ml_part->numel(),
+                " < ", rows * S * 2);
+    op_ptr = o_part->data_ptr<float>();
+    ml_ptr = ml_part->data_ptr<float>();
+  }
+  int rc = pdt_attn_extend(bf16_ptr(qkv), qkv.stride(0), qkv.stride(1), bf16_ptr(k_cache), bf16_ptr(v_cache),
+                           lens.data_ptr<int>(), op_ptr, ml_ptr, bf16_out(out), lp, d.B, d.Tn, d.H, d.Hkv, d.cap, (int)S,
+                           (int)geo[1], (int)geo[2], (int)geo[3], (float)scale, stream());
+  TORCH_CHECK(rc == 0, "pdt_attn_extend failed: ", rc);
+  if (S > 1) {
+    rc = pdt_attn_decode_combine(op_ptr, ml_ptr, bf16_out(out), lp, d.B * d.Tn, d.H, (int)S, stream());
+    TORCH_CHECK(rc == 0, "pdt_attn_decode_combine failed: ", rc);
+  }
+  return geo;
+}
+
 // y = silu(gu[:, :F]) * gu[:, F:] for gu [..., 2F] (swiglu.hip)
 Tensor swiglu_fwd(Tensor gu, c10::optional<Tensor> y_out) {
   const Op op("swiglu_fwd", gu);
@@ -2860,6 +2917,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode_geo", &attn_decode_geo, py::arg("B"), py::arg("kv_heads"), py::arg("capacity"),
         py::arg("splits") = 0, py::arg("group") = 1);
   m.def("attn_decode", &attn_decode, py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"),
+        py::arg("heads"), py::arg("kv_heads"), py::arg("scale"), py::arg("splits"), py::arg("out"),
+        py::arg("o_part") = py::none(), py::arg("ml_part") = py::none(), py::arg("lse") = py::none());
+  m.def("attn_extend_geo", &attn_extend_geo, py::arg("B"), py::arg("kv_heads"), py::arg("capacity"), py::arg("Tn"),
+        py::arg("group") = 1, py::arg("splits") = 0);
+  m.def("attn_extend", &attn_extend, py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"),
         py::arg("heads"), py::arg("kv_heads"), py::arg("scale"), py::arg("splits"), py::arg("out"),
         py::arg("o_part") = py::none(), py::arg("ml_part") = py::none(), py::arg("lse") = py::none());
   m.def("swiglu_fwd", &swiglu_fwd, py::arg("gu"), py::arg("y_out") = py::none());

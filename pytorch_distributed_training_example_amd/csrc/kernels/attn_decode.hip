@@ -370,3 +370,266 @@ int pdt_attn_decode_combine(const float* o_part, const float* ml_part, uint16_t*
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------- multi-token append attention
+// pdt_attn_extend: Tn new tokens per sequence, already appended at positions lens[b] .. lens[b] + Tn - 1.
+// Query (b, t, h) sees keys 0 .. n(b, t) - 1 of K/V head h / G, n(b, t) = clamp(lens[b] + t + 1, 0, cap): the
+// one-token problem at lens[b] + t, for every t at once. The MFMA columns, which the one-token kernel fills
+// with the G heads of a group, hold (token, head) pairs here: column q = t G + hq, q < R = G Tn, token-major,
+// each with the key limit of its token. A workgroup owns a block of 16 NT columns (NT tiles of 16, NT in
+// {1, 2, 4}) and C keys of one (b, hk); grid (S, Hkv NB, B), NB = ceil(R / (16 NT)). The key loop is the
+// one-token kernel's (wave w takes subtiles w, w + 4, ..., two per step, all loads first, K to registers,
+// V through the wave-private LDS tile, no workgroup barrier), but every K fragment pair and every transposed
+// V fragment is fetched once per subtile and serves all NT tiles, each with its own Q^T registers, mask,
+// (m, l) and accumulators. The buffer resources cover n_blk rows, the limit of the block's last valid
+// column, so rows behind the appended run (stale, NaN included) read as zero and a block of early tokens
+// does not walk keys that only later tokens see. Rows between a column's own limit and n_blk are the finite
+// rows just appended: their scores are computed and masked, p = 0 exactly, and the steps a column sees
+// nothing of leave its state as it is (alpha = 2^0). A column's arithmetic is therefore the one-token
+// kernel's, expression for expression, and with the same (S, C) its output has the same bits.
+// The four waves are merged tile after tile through the one mo / mm / ml buffer. Partials: o_part
+// [B, Tn, H, S, 64], ml_part [B, Tn, H, S, 2], merged by pdt_attn_decode_combine over B Tn rows of heads.
+//
+// The kernel is compiled without the packed fp32 instructions (v_pk_mul_f32 and its kin: a per-function target
+// feature), so that its fp32 arithmetic is one scalar IEEE operation per source operation. A function with a
+// feature set of its own inlines only what is always_inline, which the HIP header's __shfl_xor and
+// __syncthreads are not: xor_lanes and block_barrier are their bodies.
+namespace {
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PDT_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define PDT_NO_PACKED_F32
+#endif
+
+__device__ __forceinline__ float xor_lanes(float x, int mask, int lane) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((lane ^ mask) << 2, __builtin_bit_cast(int, x)));
+}
+
+__device__ __forceinline__ void block_barrier() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+template <int NT>
+PDT_NO_PACKED_F32 __global__ __launch_bounds__(256) void attn_extend_kernel(
+    const uint16_t* __restrict__ qkv, int64_t q_sb, int64_t q_st, const uint16_t* __restrict__ kc,
+    const uint16_t* __restrict__ vc, const int* __restrict__ lens, float* __restrict__ o_part,
+    float* __restrict__ ml_part, uint16_t* __restrict__ out, float* __restrict__ lse, int Tn, int H, int Hkv, int NB,
+    int cap, int C, float sl2) {
+  __shared__ __attribute__((aligned(16))) char vs[4][U * SUB_BYTES];
+  __shared__ __attribute__((aligned(16))) float mo[4][16][D];
+  __shared__ float mm[4][16], ml[4][16];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int S = gridDim.x, sp = blockIdx.x, b = blockIdx.z;
+  const int hk = blockIdx.y / NB, q0 = (blockIdx.y - hk * NB) * (16 * NT);
+  const int G = H / Hkv, R = G * Tn;
+  const int64_t len = lens[b];
+  const int c0 = sp * C;
+  // the block's last valid column bounds the rows that are read at all
+  const int n_blk = (int)min(max(len + (min(q0 + 16 * NT, R) - 1) / G + 1, (int64_t)0), (int64_t)cap);
+  const int cend_blk = min(c0 + C, n_blk);
+  const int nit = cend_blk > c0 ? (cend_blk - c0 + 63) >> 6 : 0;
+  const int64_t slice = ((int64_t)b * Hkv + hk) * cap * D;
+  const __amdgpu_buffer_rsrc_t krs =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(kc + slice), (short)0, n_blk * ROW_BYTES, 0x00020000);
+  const __amdgpu_buffer_rsrc_t vrs =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(vc + slice), (short)0, n_blk * ROW_BYTES, 0x00020000);
+  char* vw = vs[w];
+
+  // Q^T as the B operand, per tile: lane (c, g) holds column q0 + 16 j + c, elements 32 s + 8 g .. + 8, and
+  // that column's key limit within the chunk (0 for a column past R: everything masked, nothing stored)
+  bf16x8 bq[NT][2];
+  int cend[NT];
+  f4 oacc[NT][4];
+  float m[NT], l[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    const int q = q0 + 16 * j + c;
+    const int t = q / G, hq = q - t * G;
+    cend[j] = q < R ? min(c0 + C, (int)min(max(len + t + 1, (int64_t)0), (int64_t)cap)) : 0;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      if (q < R) {
+        bq[j][s] = *reinterpret_cast<const bf16x8*>(qkv + (int64_t)b * q_sb + (int64_t)t * q_st +
+                                                    (int64_t)(hk * G + hq) * D + 32 * s + 8 * g);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) bq[j][s][e] = (__bf16)0.f;
+      }
+    }
+#pragma unroll
+    for (int nn = 0; nn < 4; ++nn) oacc[j][nn] = f4{0.f, 0.f, 0.f, 0.f};
+    m[j] = -INFINITY;
+    l[j] = 0.f;
+  }
+
+  for (int it = 0; it < nit; it += U) {
+    // ---- all loads of the step first: K fragments, then V rows for the LDS tile
+    bf16x8 ka[U][2], vr[U][2];
+    int key0[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      key0[u] = c0 + 64 * (it + u) + 16 * w;  // >= cend_blk when it + u >= nit: masked in every column
+      const uint32_t base = it + u < nit ? (uint32_t)key0[u] * ROW_BYTES : OOB;
+#pragma unroll
+      for (int s = 0; s < 2; ++s) ka[u][s] = load8(krs, base + (uint32_t)(c * ROW_BYTES + (32 * s + 8 * g) * 2));
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t base = it + u < nit ? (uint32_t)key0[u] * ROW_BYTES : OOB;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int id = lane + 64 * i;
+        vr[u][i] = load8(vrs, base + (uint32_t)((id >> 3) * ROW_BYTES + (id & 7) * 16));
+      }
+    }
+    wave_lds_order();  // the tile is wave-private: see attn_decode_kernel
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int id = lane + 64 * i;
+        *reinterpret_cast<bf16x8*>(vw + u * SUB_BYTES + swz(id >> 3, id & 7)) = vr[u][i];
+      }
+    wave_lds_order();
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      s4 va[4];  // V^T of the subtile, once for all NT tiles
+#pragma unroll
+      for (int nn = 0; nn < 4; ++nn) va[nn] = lds_tr4(vw + u * SUB_BYTES, 4 * g, 16 * nn, lane);
+#pragma unroll
+      for (int j = 0; j < NT; ++j) {
+        f4 st = {0.f, 0.f, 0.f, 0.f};
+        st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka[u][0], bq[j][0], st, 0, 0, 0);
+        st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka[u][1], bq[j][1], st, 0, 0, 0);
+        float mt = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          if (key0[u] + 4 * g + r >= cend[j]) st[r] = -INFINITY;
+          mt = fmaxf(mt, st[r]);
+        }
+        mt = fmaxf(mt, xor_lanes(mt, 16, lane));
+        mt = fmaxf(mt, xor_lanes(mt, 32, lane));
+        const float mn = fmaxf(m[j], mt * sl2);
+        const float alpha = (mn == -INFINITY) ? 1.f : fast_exp2(m[j] - mn);
+        const float msub = (mn == -INFINITY) ? 0.f : mn;
+        float ls = 0.f;
+        s4 pb;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float p = fast_exp2(fmaf(st[r], sl2, -msub));
+          ls += p;
+          pb[r] = __builtin_bit_cast(short, (__bf16)p);
+        }
+        l[j] = l[j] * alpha + ls;
+        m[j] = mn;
+#pragma unroll
+        for (int nn = 0; nn < 4; ++nn) {
+          oacc[j][nn] *= alpha;
+          oacc[j][nn] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(va[nn], pb, oacc[j][nn], 0, 0, 0);
+        }
+      }
+    }
+  }
+  // ---- merge the four waves in wave order, one tile at a time through the one buffer
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    float lj = l[j];
+    lj += xor_lanes(lj, 16, lane);
+    lj += xor_lanes(lj, 32, lane);
+    if (g == 0) {
+      mm[w][c] = m[j];
+      ml[w][c] = lj;
+    }
+#pragma unroll
+    for (int nn = 0; nn < 4; ++nn) *reinterpret_cast<f4*>(&mo[w][c][16 * nn + 4 * g]) = oacc[j][nn];
+    block_barrier();
+    {
+      const int qh = tid >> 4, d4 = (tid & 15) * 4;
+      float M = -INFINITY;
+#pragma unroll
+      for (int ww = 0; ww < 4; ++ww) M = fmaxf(M, mm[ww][qh]);
+      float L = 0.f;
+      f4 o = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ww = 0; ww < 4; ++ww) {
+        const float wt = merge_weight(mm[ww][qh], M);
+        L += ml[ww][qh] * wt;
+        o += *reinterpret_cast<const f4*>(&mo[ww][qh][d4]) * wt;
+      }
+      const int q = q0 + 16 * j + qh;
+      if (q < R) {
+        const int t = q / G, hq = q - t * G;
+        const int64_t row = ((int64_t)b * Tn + t) * H + hk * G + hq;
+        if (S == 1) {
+          const float inv = L > 0.f ? 1.f / L : 0.f;
+          const float v4[4] = {o[0] * inv, o[1] * inv, o[2] * inv, o[3] * inv};
+          Vec4<uint16_t>::st(out, row * D + d4, v4);
+          if (lse && d4 == 0) lse[row] = (M + log2f(L)) * LN2;
+        } else {
+          *reinterpret_cast<f4*>(o_part + (row * S + sp) * D + d4) = o;
+          if (d4 == 0) {
+            ml_part[(row * S + sp) * 2] = M;
+            ml_part[(row * S + sp) * 2 + 1] = L;
+          }
+        }
+      }
+    }
+    if (j + 1 < NT) block_barrier();  // mo / mm / ml are rewritten by the next tile
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+// (S, C, NB, NT) into geo4 for Tn new tokens per sequence on a cache of `capacity` positions: R = G Tn query
+// columns per K/V head in NB blocks of NT 16-column tiles, NT the smallest of 1, 2, 4 with 16 NT >= min(R, 64).
+// (S, C) is pdt_attn_decode_geo's rule with the column blocks counted as batch (the workgroup target) and the
+// block's column count as the group (the merge-traffic cap); an override gives the one-token kernel's (S, C).
+// A function of shapes, never of lens. -2: B NB or the grid's y dimension past its limit.
+int pdt_attn_extend_geo(int B, int Hkv, int capacity, int Tn, int G, int splits_override, int* geo4) {
+  if (B <= 0 || Hkv <= 0 || capacity <= 0 || Tn <= 0 || G <= 0 || splits_override < 0) return -1;
+  const int64_t R = (int64_t)G * Tn;
+  const int cols = (int)(R < 64 ? R : 64);
+  const int NT = cols <= 16 ? 1 : (cols <= 32 ? 2 : 4);
+  const int64_t NB = (R + 16 * NT - 1) / (16 * NT);
+  if ((int64_t)B * NB > 0x7fffffffLL || (int64_t)Hkv * NB > 65535) return -2;
+  const int rc = pdt_attn_decode_geo((int)(B * NB), Hkv, capacity, splits_override, cols, geo4);
+  if (rc != 0) return rc;
+  geo4[2] = (int)NB;
+  geo4[3] = NT;
+  return 0;
+}
+
+// qkv [B, Tn, (H + 2 Hkv) 64] with Q rotated (batch stride q_sb, row stride q_st, in elements), caches
+// [B, Hkv, capacity, 64] already holding the Tn tokens at lens[b] + t, lens int32 [B], the count before the
+// append. S > 1: writes o_part [B, Tn, H, S, 64] and ml_part [B, Tn, H, S, 2] for pdt_attn_decode_combine
+// (B Tn rows of heads); S == 1: writes out [B, Tn, H 64] (and lse [B, Tn, H] unless null). (S, C, NB, NT)
+// must be what pdt_attn_extend_geo returns for these shapes.
+int pdt_attn_extend(const uint16_t* qkv, int64_t q_sb, int64_t q_st, const uint16_t* k_cache, const uint16_t* v_cache,
+                    const int* lens, float* o_part, float* ml_part, uint16_t* out, float* lse, int B, int Tn, int H,
+                    int Hkv, int capacity, int S, int C, int NB, int NT, float scale, hipStream_t s) {
+  if (B <= 0 || Tn < 1 || H <= 0 || Hkv <= 0 || H % Hkv != 0 || capacity <= 0) return -1;
+  if (S <= 0 || C <= 0 || C % 64 != 0 || (int64_t)S * C < capacity || (int64_t)(S - 1) * C >= capacity) return -2;
+  const int64_t R = (int64_t)(H / Hkv) * Tn;
+  if ((NT != 1 && NT != 2 && NT != 4) || NB != (R + 16 * NT - 1) / (16 * NT)) return -2;
+  if ((int64_t)capacity * ROW_BYTES > 0x7fffffffLL || (int64_t)Hkv * NB > 65535 || B > 65535 || R > 0x7fffffffLL)
+    return -3;
+  if (S > 1 && (!o_part || !ml_part)) return -4;
+  const dim3 grid(S, Hkv * NB, B);
+  const float sl2 = scale * LOG2E;
+#define PDT_EXTEND(N)                                                                                              \
+  hipLaunchKernelGGL(attn_extend_kernel<N>, grid, dim3(256), 0, s, qkv, q_sb, q_st, k_cache, v_cache, lens, o_part, \
+                     ml_part, out, lse, Tn, H, Hkv, NB, capacity, C, sl2)
+  if (NT == 1) PDT_EXTEND(1);
+  else if (NT == 2) PDT_EXTEND(2);
+  else PDT_EXTEND(4);
+#undef PDT_EXTEND
+  return 0;
+}
+
+}  // extern "C"

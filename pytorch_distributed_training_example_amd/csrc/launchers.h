@@ -58,6 +58,11 @@ int pdt_attn_decode(const uint16_t* qkv, int64_t q_sb, const uint16_t* k_cache, 
                     int capacity, int S, int C, float scale, hipStream_t s);
 int pdt_attn_decode_combine(const float* o_part, const float* ml_part, uint16_t* out, float* lse, int B, int H, int S,
                             hipStream_t s);
+// Tn new tokens per sequence, already appended at lens[b] + t; geo4 = (S, C, NB, NT)
+int pdt_attn_extend_geo(int B, int Hkv, int capacity, int Tn, int G, int splits_override, int* geo4);
+int pdt_attn_extend(const uint16_t* qkv, int64_t q_sb, int64_t q_st, const uint16_t* k_cache, const uint16_t* v_cache,
+                    const int* lens, float* o_part, float* ml_part, uint16_t* out, float* lse, int B, int Tn, int H,
+                    int Hkv, int capacity, int S, int C, int NB, int NT, float scale, hipStream_t s);
 
 // kernels/batchnorm.hip
 int64_t pdt_bn_workspace_floats(int64_t M, int C);

@@ -31,7 +31,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..config import SW
-from ..ops.attention import attention_decode, attention_qkv
+from ..ops.attention import attention_decode, attention_extend, attention_qkv
 from ..ops.cross_entropy import cross_entropy
 from ..ops.fp8 import Fp8Act, add_rms_norm_fp8, fp8_input_slot, fp8_linear, fp8_ok, fp8_swiglu_mlp, rms_fp8_ok
 from ..ops.kv_cache import KVCache
@@ -97,16 +97,21 @@ class LlamaAttention(nn.Module):
     def _forward_cached(self, x, rope, cache: KVCache, layer: int):
         """Inference on a KV cache: the Tn new rows are rotated at positions lens[b] + t and appended (one
         kernel); a prefill (Tn > 1, empty cache) then runs the causal flash forward on them, a decode step
-        (Tn == 1) the split-KV kernel on the cache. ``cache.lens`` is advanced by the caller after the last layer."""
+        (Tn == 1) the split-KV kernel on the cache, and ``Llama.extend`` (which sets ``cache.extending`` around
+        its forward) with Tn > 1 the multi-token append kernel, whatever the cache holds. ``cache.lens`` is
+        advanced by the caller after the last layer."""
         Tn = x.shape[1]
-        if Tn > 1 and cache.bound > 0:
+        if Tn > 1 and cache.bound > 0 and not cache.extending:
             raise ValueError(f"{Tn} new tokens onto a cache that may hold {cache.bound} positions: chunked prefill "
-                             "is not supported (prefill an empty cache, then decode one token at a time)")
+                             "is not what prefill does (prefill an empty cache, then extend() or decode_step())")
         cache.require(Tn, rope.cos.shape[0])
         qkv = _linear(x, self.c_attn)
         qkv = rope_append_(qkv, rope.cos, rope.sin, self.heads, self.kv_heads, cache.k[layer], cache.v[layer],
                            cache.lens)
-        if Tn > 1:
+        if Tn > 1 and cache.extending:
+            y = attention_extend(qkv, cache.k[layer], cache.v[layer], cache.lens, self.heads, self.kv_heads,
+                                 cache=cache)
+        elif Tn > 1:
             y = attention_qkv(qkv, self.heads, causal=True, kv_heads=self.kv_heads)
         else:
             y = attention_decode(qkv, cache.k[layer], cache.v[layer], cache.lens, self.heads, self.kv_heads,
@@ -249,16 +254,70 @@ class Llama(nn.Module):
         cache.advance(1)
         return linear(x[:, 0], self.lm_head.weight)
 
+    def extend(self, idx: torch.Tensor, cache: KVCache, new_lens=None, last_only: bool = False) -> torch.Tensor:
+        """Append ``idx`` [B, Tn] at positions ``cache.lens[b] + t`` of a cache that may already hold a
+        conversation (a later turn's prompt, a slice of a chunked prefill, drafted tokens to verify: the
+        caller rolls back with ``cache.set_lens``). Returns the logits [B, Tn, V]; with ``last_only`` [B, V]
+        of every sequence's last valid new row (the LM head runs on those B rows only). ``cache.lens``
+        advances by Tn, or, for right-padded ragged input, by ``new_lens[b]`` in [0, Tn] (a sequence, a CPU
+        tensor, or a device tensor, which is clamped rather than read); the next append overwrites the
+        padding rows. Tn == 1 runs the split-KV decode kernel, Tn > 1 the multi-token append kernel, on an
+        empty cache too. With ``new_lens`` None or on the device nothing here reads the device, so the call
+        can be captured like ``decode_step``."""
+        B, Tn = idx.shape
+        self._check_cache(cache, B)
+        if Tn < 1:
+            raise ValueError("extend: at least one new token per sequence")
+        if new_lens is not None:
+            new_lens = _lens_arg(new_lens, B, 0, Tn, idx.device, "new_lens")
+        x = F.embedding(idx, self.transformer.wte.weight)
+        cache.extending = True
+        try:
+            x = run_llama_blocks(self.transformer.h, x, self.transformer.ln_f, self.rope, cache)
+        finally:
+            cache.extending = False
+        if new_lens is None:
+            cache.advance(Tn)
+        else:
+            cache.set_lens(cache.lens + new_lens, bound=cache.bound + Tn)
+        if last_only:
+            if new_lens is None:
+                x = x[:, -1]
+            else:  # a sequence that got nothing returns its row 0: the caller keeps what it had
+                x = x.gather(1, (new_lens.long() - 1).clamp(min=0)[:, None, None].expand(B, 1, x.shape[-1]))[:, 0]
+        return linear(x, self.lm_head.weight)
+
+    def _prefill_chunked(self, idx: torch.Tensor, cache: KVCache, prompt_lens, chunk: int) -> torch.Tensor:
+        """``prefill`` in slices of ``chunk`` positions: the first through ``prefill``, the rest through
+        ``extend(..., last_only=True)``; a sequence whose prompt ended in an earlier slice keeps its logits."""
+        B, T0 = idx.shape
+        if chunk < 1:
+            raise ValueError(f"prefill_chunk must be positive, got {chunk}")
+        if prompt_lens is not None:
+            prompt_lens = _lens_arg(prompt_lens, B, 1, T0, idx.device, "prompt_lens")
+        first = min(chunk, T0)
+        logits = self.prefill(idx[:, :first], cache, None if prompt_lens is None else prompt_lens.clamp(max=first))
+        for s in range(first, T0, chunk):
+            part = idx[:, s:s + chunk]
+            if prompt_lens is None:
+                logits = self.extend(part, cache, last_only=True)
+            else:
+                n = (prompt_lens - s).clamp(0, part.shape[1])
+                logits = torch.where((n > 0)[:, None], self.extend(part, cache, new_lens=n, last_only=True), logits)
+        return logits
+
     @torch.no_grad()
     def generate(self, idx: torch.Tensor, max_new_tokens: int, temperature: float = 0.0, top_k: int | None = None,
                  eos_token: int | None = None, generator: torch.Generator | None = None, prompt_lens=None,
-                 return_logits: bool = False):
+                 return_logits: bool = False, prefill_chunk: int | None = None):
         """Sample ``max_new_tokens`` tokens after the prompts ``idx`` [B, T0] (right-padded when
         ``prompt_lens`` is given); returns them as [B, max_new_tokens] on the device, with ``return_logits``
         also the logits [B, max_new_tokens, V] each was drawn from. Greedy at ``temperature`` 0, otherwise
         ``torch.multinomial`` of softmax(logits / temperature) (restricted to the ``top_k`` largest) on
         ``generator``. With ``eos_token`` everything after a sequence's first EOS is EOS (a device-side mask:
-        no step reads a token on the host). Runs in ``eval()`` and restores the mode."""
+        no step reads a token on the host). With ``prefill_chunk`` the prompt runs in slices of that many
+        positions (``prefill`` of the first, ``extend`` of the rest), which bounds the activation memory of a
+        long prompt by the slice. Runs in ``eval()`` and restores the mode."""
         B, T0 = idx.shape
         if max_new_tokens < 1:
             raise ValueError(f"max_new_tokens must be positive, got {max_new_tokens}")
@@ -269,7 +328,10 @@ class Llama(nn.Module):
         self.eval()
         try:
             cache = self.new_cache(B, T0 + max_new_tokens)
-            logits = self.prefill(idx, cache, prompt_lens)
+            if prefill_chunk is None:
+                logits = self.prefill(idx, cache, prompt_lens)
+            else:
+                logits = self._prefill_chunked(idx, cache, prompt_lens, prefill_chunk)
             toks, all_logits = [], []
             done = torch.zeros(B, dtype=torch.bool, device=idx.device)
             for i in range(max_new_tokens):
@@ -286,6 +348,18 @@ class Llama(nn.Module):
             self.train(was_training)
         out = torch.stack(toks, 1)
         return (out, torch.stack(all_logits, 1)) if return_logits else out
+
+
+def _lens_arg(lens, batch: int, lo: int, hi: int, device, name: str) -> torch.Tensor:
+    """``lens`` as int32 [batch] on ``device``: a sequence or a CPU tensor is checked against [lo, hi], a
+    device tensor is clamped to it rather than read."""
+    if not isinstance(lens, torch.Tensor):
+        lens = torch.as_tensor(lens, dtype=torch.int32)
+    if lens.device.type == "cpu":
+        if lens.shape != (batch,) or int(lens.min()) < lo or int(lens.max()) > hi:
+            raise ValueError(f"{name} must be {batch} lengths in [{lo}, {hi}], got {lens.tolist()}")
+        return lens.to(device=device, dtype=torch.int32)
+    return lens.clamp(lo, hi).to(torch.int32)
 
 
 def _sample(logits: torch.Tensor, temperature: float, top_k: int | None, generator) -> torch.Tensor:

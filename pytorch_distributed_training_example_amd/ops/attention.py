@@ -263,6 +263,78 @@ def attention_decode(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
     return (out, lse) if return_lse else out
 
 
+EXTEND_STATS = {"native_calls": 0, "geo": None}  # launches of the append kernel and its last (S, C, NB, NT)
+
+
+def attention_extend_geo(batch: int, kv_heads: int, capacity: int, tokens: int, splits: int | None = None,
+                         group: int = 1):
+    """(S, C, NB, NT) of the multi-token append kernel: the ``group * tokens`` query columns of a K/V head in
+    NB blocks of NT 16-column tiles, S splits of C keys. A function of the shapes, never of ``lens``."""
+    return tuple(int(x) for x in native().attn_extend_geo(batch, kv_heads, capacity, tokens, group, int(splits or 0)))
+
+
+def _extend_reference(qkv, k_cache, v_cache, lens, heads, kv_heads, scale):
+    """``_decode_reference`` with the key limit of every token: query (b, t) sees keys 0 .. lens[b] + t."""
+    B, Tn, _ = qkv.shape
+    cap, dh = k_cache.shape[2], k_cache.shape[3]
+    G = heads // kv_heads
+    q = qkv[:, :, :heads * dh].reshape(B, Tn, heads, dh).float()
+    pos = lens[:, None] + torch.arange(Tn, device=qkv.device)[None, :]  # [B, Tn]
+    valid = torch.arange(cap, device=qkv.device)[None, None, :] <= pos[:, :, None]  # [B, Tn, cap]
+    seen = valid.any(1)  # [B, cap]: rows past the last token's limit may hold anything and are taken out
+    k = torch.where(seen[:, None, :, None], k_cache.float(), torch.zeros((), device=qkv.device))
+    v = torch.where(seen[:, None, :, None], v_cache.float(), torch.zeros((), device=qkv.device))
+    s = torch.einsum("bthd,bhkd->bthk", q, k.repeat_interleave(G, dim=1)) * scale
+    s = s.masked_fill(~valid[:, :, None, :], float("-inf"))
+    lse = torch.logsumexp(s, -1)
+    p = torch.exp(s - lse[..., None])
+    o = torch.einsum("bthk,bhkd->bthd", p, v.repeat_interleave(G, dim=1))
+    return o.to(qkv.dtype).reshape(B, Tn, heads * dh), lse
+
+
+def attention_extend(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, lens: torch.Tensor,
+                     heads: int, kv_heads: int | None = None, scale: float | None = None,
+                     splits: int | None = None, cache=None, return_lse: bool = False):
+    """Attention of Tn new tokens per sequence on a KV cache (a later turn's prompt, a slice of a chunked
+    prefill, drafted tokens to verify): ``qkv`` [B, Tn, (H + 2·Hkv)·64] with Q rotated, ``rope_append_``
+    having written the tokens' K and V at positions ``lens[b] + t``; ``lens`` int32 [B] is the count before
+    the append and is read on the device. Query (b, t) sees keys 0 .. lens[b] + t. Returns [B, Tn, H·64] (and
+    the LSE [B, Tn, H] with ``return_lse``). Inference only.
+
+    bf16 GPU tensors run the append kernel (csrc/kernels/attn_decode.hip, attn_extend); ``splits`` and
+    ``cache`` as in ``attention_decode``. CPU, fp32 and ``PDT_DISABLE_NATIVE=1`` take the PyTorch reference."""
+    kv_heads = heads if kv_heads is None else kv_heads
+    if kv_heads <= 0 or heads % kv_heads != 0:
+        raise ValueError(f"attention_extend: heads = {heads} is not a positive multiple of kv_heads = {kv_heads}")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (qkv, k_cache, v_cache)):
+        raise RuntimeError("attention_extend: inference only (run it under torch.no_grad())")
+    if qkv.dim() != 3 or qkv.shape[1] < 1 or qkv.shape[2] % (heads + 2 * kv_heads) != 0:
+        raise ValueError(f"attention_extend: qkv {tuple(qkv.shape)} is not [B, Tn >= 1, (heads + 2·kv_heads)·Dh]")
+    dh = qkv.shape[2] // (heads + 2 * kv_heads)
+    scale = scale if scale is not None else 1.0 / math.sqrt(dh)
+    if use_native(qkv) and qkv.dtype == torch.bfloat16:  # head dim 64 and the layouts: the binding's checks
+        B, Tn = qkv.shape[0], qkv.shape[1]
+        cap = k_cache.shape[2] if k_cache.dim() == 4 else 0
+        out = torch.empty(B, Tn, heads * dh, device=qkv.device, dtype=qkv.dtype)
+        lse = torch.empty(B, Tn, heads, device=qkv.device, dtype=torch.float32) if return_lse else None
+        o_part = ml_part = None
+        if cap > 0 and dh == 64:
+            S = attention_extend_geo(B, kv_heads, cap, Tn, splits, heads // kv_heads)[0]
+            if S > 1:
+                if cache is not None:
+                    o_part, ml_part = cache.scratch(heads, S, Tn)
+                else:
+                    o_part = torch.empty(B, Tn, heads, S, 64, device=qkv.device, dtype=torch.float32)
+                    ml_part = torch.empty(B, Tn, heads, S, 2, device=qkv.device, dtype=torch.float32)
+        geo = native().attn_extend(qkv, k_cache, v_cache, lens, heads, kv_heads, scale, int(splits or 0), out,
+                                   o_part, ml_part, lse)
+        EXTEND_STATS["native_calls"] += 1
+        EXTEND_STATS["geo"] = tuple(int(x) for x in geo)
+        return (out, lse) if return_lse else out
+    out, lse = _extend_reference(qkv, k_cache, v_cache, lens, heads, kv_heads, scale)
+    return (out, lse) if return_lse else out
+
+
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False,
               dropout_p: float = 0.0, scale: float | None = None) -> torch.Tensor:
     """Unpacked [B, H, T, Dh] interface (SDPA-compatible)."""

@@ -11,8 +11,8 @@ What the host does know is an upper bound of ``lens``, kept by the three mutator
 refuses ``bound + n > capacity`` and ``bound + n > table_len`` before any launch. (The kernels clamp
 positions to the cache as well: a wrong ``lens`` costs a wrong answer, never an out-of-bounds store.)
 
-The fp32 scratch of the split-KV partials belongs to the cache too: ``scratch(heads, S)`` allocates once
-per (heads, S) and hands the same tensors back on every later step. The batch is fixed for the life of
+The fp32 scratch of the split-KV partials belongs to the cache too: ``scratch(heads, S, tokens)`` allocates once
+per (heads, S, tokens) and hands the same tensors back on every later step. The batch is fixed for the life of
 a cache.
 """
 from __future__ import annotations
@@ -35,6 +35,7 @@ class KVCache:
         self.lens = torch.zeros(batch, device=self.device, dtype=torch.int32)
         self._bound = 0  # host-side upper bound of lens
         self._scratch: dict = {}
+        self.extending = False  # set by Llama.extend around its forward: Tn > 1 then runs the append kernel
 
     @property
     def bound(self) -> int:
@@ -79,11 +80,13 @@ class KVCache:
             raise ValueError(f"KVCache: {n} more positions on top of up to {self._bound} exceed the rotary "
                              f"table's {table_len} positions")
 
-    def scratch(self, heads: int, S: int):
-        """(o_part [B, heads, S, 64], ml_part [B, heads, S, 2]) fp32: allocated on the first request."""
-        key = (heads, S)
+    def scratch(self, heads: int, S: int, tokens: int = 1):
+        """(o_part [B, heads, S, 64], ml_part [B, heads, S, 2]) fp32: allocated on the first request. With
+        ``tokens`` > 1 (a multi-token append) the shapes are [B, tokens, heads, S, 64] and [B, tokens, heads, S, 2]."""
+        key = (heads, S) if tokens == 1 else (heads, S, tokens)
         if key not in self._scratch:
+            lead = (self.batch,) if tokens == 1 else (self.batch, tokens)
             self._scratch[key] = (
-                torch.empty(self.batch, heads, S, HEAD_DIM, device=self.device, dtype=torch.float32),
-                torch.empty(self.batch, heads, S, 2, device=self.device, dtype=torch.float32))
+                torch.empty(*lead, heads, S, HEAD_DIM, device=self.device, dtype=torch.float32),
+                torch.empty(*lead, heads, S, 2, device=self.device, dtype=torch.float32))
         return self._scratch[key]

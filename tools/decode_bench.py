@@ -28,7 +28,15 @@ greedy, in one process on the same weights:
   full      128 times model(idx) on the growing sequence, argmax of the last position
 and the per-token time of the decode steps alone, eager and replayed.
 
-    python tools/decode_bench.py [--rounds 7] [--iters 50] [--gen-rounds 3] [--no-generate] [--out FILE]
+--extend: the multi-token append kernel instead. The same shape, Tn in {4, 8, 64} new tokens per sequence at
+lens in {128, 1023 - Tn} (the count before the append; lens + Tn keys are read). Candidates, each captured
+once and replayed, taking turns within every round, over rotating caches, device events, median of the rounds:
+  extend    one attention_extend call (default geometry)
+  decodes   Tn successive attention_decode calls at lens + t on the same cache (all the parent commit can do)
+  sdpa      F.scaled_dot_product_attention with an explicit [Tn, lens + Tn] mask on K/V materialised at 16
+            heads and cut to lens + Tn keys (the expansion and the cut are not timed)
+
+    python tools/decode_bench.py [--rounds 7] [--iters 50] [--gen-rounds 3] [--no-generate] [--extend] [--out FILE]
 """
 from __future__ import annotations
 
@@ -144,6 +152,66 @@ def bench_kernel(rounds, iters, emit):
         del cache, ke, ve
 
 
+def bench_extend(rounds, iters, emit):
+    from pytorch_distributed_training_example_amd.ops.attention import (attention_decode, attention_extend,
+                                                                       attention_extend_geo)
+    from pytorch_distributed_training_example_amd.ops.kv_cache import KVCache
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    scale = 1.0 / math.sqrt(DH)
+    for hkv in KV_HEADS:
+        cache_bytes = 2 * B * hkv * CAP * DH * 2
+        ncopy = max(1, min(64, ROTATE_BYTES // cache_bytes))
+        cache = KVCache(ncopy, B, hkv, CAP, dev)
+        for l in range(ncopy):
+            cache.k[l].copy_(torch.randn(B, hkv, CAP, DH, device=dev, generator=g))
+            cache.v[l].copy_(torch.randn(B, hkv, CAP, DH, device=dev, generator=g))
+        emit(f"## Hkv = {hkv} (G = {H // hkv}): one cache {cache_bytes / 2**20:.0f} MiB, rotating over {ncopy} "
+             f"({ncopy * cache_bytes / 2**20:.0f} MiB)")
+        for tn in (4, 8, 64):
+            qkv = torch.randn(B, tn, (H + 2 * hkv) * DH, device=dev, generator=g).bfloat16()
+            rows = [qkv[:, t:t + 1].contiguous() for t in range(tn)]
+            geo = attention_extend_geo(B, hkv, CAP, tn, None, H // hkv)
+            for lens in (128, CAP - 1 - tn):
+                n = lens + tn
+                cache.set_lens([lens] * B)
+                lens_t = [cache.lens + t for t in range(tn)]
+                must = 2 * B * hkv * n * DH * 2 + 2 * B * tn * H * DH * 2
+                q4 = qkv[:, :, :H * DH].reshape(B, tn, H, DH).transpose(1, 2)
+                ke = [cache.k[l][:, :, :n].repeat_interleave(H // hkv, dim=1).contiguous() for l in range(ncopy)]
+                ve = [cache.v[l][:, :, :n].repeat_interleave(H // hkv, dim=1).contiguous() for l in range(ncopy)]
+                mask = torch.arange(n, device=dev)[None, :] <= lens + torch.arange(tn, device=dev)[:, None]
+
+                def extend(i):
+                    return attention_extend(qkv, cache.k[i % ncopy], cache.v[i % ncopy], cache.lens, H, hkv, scale,
+                                            cache=cache)
+
+                def decodes(i):
+                    return [attention_decode(rows[t], cache.k[i % ncopy], cache.v[i % ncopy], lens_t[t], H, hkv, scale,
+                                             cache=cache) for t in range(tn)]
+
+                def sdpa(i):
+                    return F.scaled_dot_product_attention(q4, ke[i % ncopy], ve[i % ncopy], attn_mask=mask, scale=scale)
+
+                a = extend(0)
+                same = torch.equal(a, torch.cat(decodes(0), 1))  # equal bits when both ran the same (S, C)
+                err = (a.float() - sdpa(0).transpose(1, 2).reshape(B, tn, H * DH).float()).abs().max().item()
+                cands = {"extend": extend, "decodes": decodes, "sdpa": sdpa}
+                graphs = {k: _graphed(fn, iters) for k, fn in cands.items()}
+                t = {k: [] for k in cands}
+                for _ in range(rounds):
+                    for k in cands:
+                        t[k].append(_time_ms(lambda i, gr=graphs[k]: gr.replay(), 1) / iters)
+                med = {k: statistics.median(v) for k, v in t.items()}
+                for k in cands:
+                    emit(f"Tn {tn:3d} lens {lens:5d}  {k:<8} {med[k] * 1e3:7.1f} us ({min(t[k]) * 1e3:.1f}-{max(t[k]) * 1e3:.1f})  "
+                         f"{med[k] / med['extend']:5.2f}x extend  must move {must / 1e6:6.2f} MB  {must / med[k] / 1e9:5.2f} TB/s")
+                emit(f"Tn {tn:3d} lens {lens:5d}  geo (S, C, NB, NT) = {geo}; bits equal to the decodes: {same}; "
+                     f"max |extend - sdpa| = {err:.3g}")
+                del graphs, ke, ve
+        del cache
+
+
 def bench_generate(rounds, emit, prompt=128, new=128):
     from pytorch_distributed_training_example_amd.models import get_model
     from pytorch_distributed_training_example_amd.models.precision import to_bf16_mixed
@@ -257,6 +325,7 @@ def main(argv=None):
     ap.add_argument("--gen-rounds", type=int, default=3)
     ap.add_argument("--no-generate", action="store_true", help="kernel only")
     ap.add_argument("--no-kernel", action="store_true", help="generation only")
+    ap.add_argument("--extend", action="store_true", help="the multi-token append kernel instead")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -269,9 +338,11 @@ def main(argv=None):
 
     emit(f"# {torch.cuda.get_device_name(0)}; B={B} H={H} Dh={DH} capacity={CAP} bf16; median of {a.rounds} alternating "
          f"rounds (min-max), {a.iters} calls per window, device events")
-    if not a.no_kernel:
+    if a.extend:
+        bench_extend(a.rounds, a.iters, emit)
+    elif not a.no_kernel:
         bench_kernel(a.rounds, a.iters, emit)
-    if not a.no_generate:
+    if not a.no_generate and not a.extend:
         bench_generate(a.gen_rounds, emit)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
