@@ -385,8 +385,11 @@ int pdt_attn_decode_combine(const float* o_part, const float* ml_part, uint16_t*
 // column, so rows behind the appended run (stale, NaN included) read as zero and a block of early tokens
 // does not walk keys that only later tokens see. Rows between a column's own limit and n_blk are the finite
 // rows just appended: their scores are computed and masked, p = 0 exactly, and the steps a column sees
-// nothing of leave its state as it is (alpha = 2^0). A column's arithmetic is therefore the one-token
-// kernel's, expression for expression, and with the same (S, C) its output has the same bits.
+// nothing of leave its state as it is (alpha = 2^0). A column's source is therefore the one-token kernel's,
+// expression for expression, but not its instructions: the one-token kernel is compiled with the packed fp32
+// operations, and the two round the row sum l differently. With the same (S, C), m and every bit of O
+// measured equal; l, and with it the LSE, differs by one fp32 ulp in one or two rows of 17 launches in 360
+// (profiles/r20/decode_vs_extend_bits.txt).
 // The four waves are merged tile after tile through the one mo / mm / ml buffer. Partials: o_part
 // [B, Tn, H, S, 64], ml_part [B, Tn, H, S, 2], merged by pdt_attn_decode_combine over B Tn rows of heads.
 //

@@ -78,6 +78,18 @@ def test_envelope_at_every_seam(H, Hkv, Tn, splits, amplitude):
     print(f"{name}: worst O ratio {worst:.3f} of {oe.ATTN_C}")
 
 
+def test_one_token_geometry_is_the_append_rule_at_one_token():
+    """Up to 64 heads per group (one column block) the two rules give one (S, C): what lets a cache's scratch
+    and a captured grid serve either kernel."""
+    from pytorch_distributed_training_example_amd.ops.attention import attention_decode_geo, attention_extend_geo
+    for Hkv in (1, 8):
+        for G in (1, 4, 16, 17, 32, 64):
+            for cap in (40, 320, 1024, 4096):
+                for s in (None, 1, 5):
+                    one, ext = attention_decode_geo(B, Hkv, cap, s, G), attention_extend_geo(B, Hkv, cap, 1, s, G)
+                    assert one == ext[:2] and ext[2] == 1, f"Hkv {Hkv} G {G} capacity {cap} splits {s}: {one}, {ext}"
+
+
 @pytest.mark.parametrize("splits", [1, 2, 5])
 @pytest.mark.parametrize("H,Hkv,Tn", [(6, 2, 17), (32, 1, 5)])
 def test_bits_of_the_one_token_kernel_at_every_token(H, Hkv, Tn, splits):
