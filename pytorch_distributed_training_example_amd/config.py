@@ -102,6 +102,10 @@ PDT_FP8_SWIGLU              1            fp8 Llama MLPs: SwiGLU (and its backwar
                                          (fp8.hip fp8_swiglu_cast_kernel): no bf16 activation, no cast pass. With
                                          this and PDT_FP8_LN off, the per-Linear fp8 path (bf16 RMSNorm / SwiGLU
                                          plus a cast pass): the unfused reference of the tests
+PDT_DECODE_GEMM             0            Llama inference on at most 64 rows (decode_step, a short extend, the LM
+                                         head of a prefill): the Linears run on the weight-streaming skinny GEMM
+                                         (gemm_skinny.hip, ops/linear.py linear_skinny), c_fc with SwiGLU in its
+                                         epilogue. 0: the library GEMM + the SwiGLU kernel, bit for bit as before
 PDT_WGRAD_STREAM_M          0            conv weight gradients with <= this many output pixels run on a side
                                          stream, concurrent with their data gradient (0 = in-stream)
 PDT_DROPOUT_FUSED           1            GPT-2 / ViT dropout from counter-generated masks inside our kernels
@@ -120,7 +124,7 @@ class _Switches:
                  "subsample_native", "linear_splitk", "fused_addln", "embedding_native", "linear_epilogue",
                  "bwd_fused", "bwd_fused_shapes", "bwd_alg", "alg_glo", "bwd_alg_min_m", "z3_virtual", "bwd_alg_first", "ds_alg", "bn2_defer", "bn_apply_gemm_k", "strided_bstats", "gap_native", "sub_out",
                  "fp8_fused_gelu", "fp8_weight_multi", "fp8_cast_colsum", "fp8_ln", "fp8_swiglu", "wgrad_stream_m",
-                 "dropout_fused")
+                 "dropout_fused", "decode_gemm")
 
     def __init__(self):
         self.reload()
@@ -192,6 +196,7 @@ class _Switches:
         # with their data gradient (0 = off): small-batch grids leave CUs idle (ops/conv.py _WgradFork)
         self.wgrad_stream_m = int(e("PDT_WGRAD_STREAM_M", "0"))
         self.dropout_fused = on("PDT_DROPOUT_FUSED")
+        self.decode_gemm = e("PDT_DECODE_GEMM", "0") == "1"
         return self
 
 

@@ -2025,6 +2025,47 @@ Tensor swiglu_bwd(Tensor dy, Tensor gu, c10::optional<Tensor> dgu_out) {
   return dgu;
 }
 
+// ----------------------------------------------------------------------------- skinny GEMM (gemm_skinny.hip)
+// (S, FT, NT) of gemm_skinny for x [M, K], w [N, K]: S grid splits of K, FT feature tiles per workgroup, NT
+// column tiles. mode 0 plain, 1 SwiGLU; splits 0: the default rule. Refuses shapes outside the contract.
+std::vector<int64_t> gemm_skinny_geo(int64_t M, int64_t N, int64_t K, int64_t mode, int64_t splits) {
+  TORCH_CHECK(M >= 1 && M <= 64, "gemm_skinny: 1 <= M <= 64 rows, got ", M);
+  TORCH_CHECK(N >= 16 && N % 16 == 0 && N <= 0x7fffffffLL, "gemm_skinny: N % 16 == 0, got ", N);
+  TORCH_CHECK(K >= 64 && K % 64 == 0 && K <= 0x7fffffffLL, "gemm_skinny: K % 64 == 0, got ", K);
+  TORCH_CHECK(mode == 0 || mode == 1, "gemm_skinny: mode 0 (plain) or 1 (SwiGLU), got ", mode);
+  TORCH_CHECK(mode == 0 || N % 32 == 0, "gemm_skinny: SwiGLU needs w = [gate; up] with F = N / 2 a multiple of 16, got N = ", N);
+  TORCH_CHECK(splits >= 0 && splits <= 65535, "gemm_skinny: splits in [0, 65535], got ", splits);
+  TORCH_CHECK(N * K * 2 < 0x80000000LL, "gemm_skinny: w of ", N, " x ", K, " is past 2^31 bytes");
+  int g[3];
+  const int rc = pdt_gemm_skinny_geo((int)M, (int)N, (int)K, (int)mode, (int)splits, g);
+  TORCH_CHECK(rc == 0, "pdt_gemm_skinny_geo failed: ", rc);
+  return {g[0], g[1], g[2]};
+}
+
+// y [M, N] = x [M, K] w [N, K]^T (mode 0) or y [M, N / 2] = swiglu of it (mode 1) for M <= 64, bf16.
+// y_out: write into this tensor instead of a new one.
+Tensor gemm_skinny(Tensor x, Tensor w, int64_t mode, int64_t splits, c10::optional<Tensor> y_out) {
+  const Op op("gemm_skinny", x);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16, "gemm_skinny: x and w must be bf16");
+  TORCH_CHECK(w.device() == op.dev, "gemm_skinny: w must be on ", op.dev);
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1), "gemm_skinny: x [M, K] and w [N, K]");
+  TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && aligned16(x) && aligned16(w),
+              "gemm_skinny: x and w must be contiguous and 16-byte aligned");
+  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+  const std::vector<int64_t> geo = gemm_skinny_geo(M, N, K, mode, splits);
+  const int64_t S = geo[0];
+  auto y = out_or_new(op, "y_out", y_out, {M, mode == 1 ? N / 2 : N}, x.options());
+  Tensor ws;
+  if (S > 1) ws = at::empty({S * M * N}, x.options().dtype(at::kFloat));
+  const int rc = pdt_gemm_skinny(bf16_ptr(x), bf16_ptr(w), bf16_out(y), ptr_or_null<float>(ws), (int)M, (int)N, (int)K,
+                                 (int)mode, (int)S, (int)geo[1], (int)geo[2], stream());
+  TORCH_CHECK(rc == 0, "pdt_gemm_skinny failed: ", rc);
+  return y;
+}
+
+// A/B only: non-temporal W loads on (1, the default) / off (0); returns the previous setting.
+int64_t gemm_skinny_tune(int64_t w_nontemporal) { return pdt_gemm_skinny_tune((int)w_nontemporal); }
+
 // ----------------------------------------------------------------------------- dropout (philox.h)
 const int64_t* ticket_ptr(const Tensor& ticket, const Tensor& like) {
   TORCH_CHECK(ticket.is_cuda() && ticket.scalar_type() == at::kLong && ticket.numel() == 2 && ticket.is_contiguous() &&
@@ -2925,6 +2966,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("heads"), py::arg("kv_heads"), py::arg("scale"), py::arg("splits"), py::arg("out"),
         py::arg("o_part") = py::none(), py::arg("ml_part") = py::none(), py::arg("lse") = py::none());
   m.def("swiglu_fwd", &swiglu_fwd, py::arg("gu"), py::arg("y_out") = py::none());
+  m.def("gemm_skinny_geo", &gemm_skinny_geo, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("mode") = 0,
+        py::arg("splits") = 0);
+  m.def("gemm_skinny", &gemm_skinny, py::arg("x"), py::arg("w"), py::arg("mode") = 0, py::arg("splits") = 0,
+        py::arg("y_out") = py::none());
+  m.def("gemm_skinny_tune", &gemm_skinny_tune, py::arg("w_nontemporal"));
   m.def("swiglu_bwd", &swiglu_bwd, py::arg("dy"), py::arg("gu"), py::arg("dgu_out") = py::none());
   py::class_<P2PComm>(m, "P2PComm")
       .def(py::init<int, int, int64_t, int, int>(), py::arg("rank"), py::arg("world"), py::arg("capacity_bytes"),

@@ -275,6 +275,12 @@ int pdt_gemm_nt_fp8(const uint8_t* A, const uint8_t* B, uint16_t* C, const float
                     const void* bias, int bias_f32, int epi, int M, int N, int K, float* ws, int ksplit,
                     hipStream_t s);
 
+// kernels/gemm_skinny.hip: Y[M, N] = X[M, K] W[N, K]^T for M <= 64; mode 0 plain, 1 SwiGLU on packed [gate; up] rows
+int pdt_gemm_skinny_tune(int w_nontemporal);
+int pdt_gemm_skinny_geo(int M, int N, int K, int mode, int splits, int* geo3);
+int pdt_gemm_skinny(const uint16_t* x, const uint16_t* w, uint16_t* y, float* ws, int M, int N, int K, int mode, int S,
+                    int FT, int NT, hipStream_t s);
+
 // kernels/layernorm.hip
 int64_t pdt_ln_workspace_floats(int64_t N, int D);
 int pdt_ln_fwd(const void* x, const void* res, int dtype, const float* w, const float* b, void* y, void* sum_out,

@@ -35,7 +35,7 @@ from ..ops.attention import attention_decode, attention_extend, attention_qkv
 from ..ops.cross_entropy import cross_entropy
 from ..ops.fp8 import Fp8Act, add_rms_norm_fp8, fp8_input_slot, fp8_linear, fp8_ok, fp8_swiglu_mlp, rms_fp8_ok
 from ..ops.kv_cache import KVCache
-from ..ops.linear import linear
+from ..ops.linear import SKINNY_MAX_ROWS, linear, linear_skinny
 from ..ops.rmsnorm import RMSNorm, add_rms_norm
 from ..ops.rope import RotaryTable, rope_append_, rope_qkv_
 from ..ops.swiglu import swiglu
@@ -66,12 +66,22 @@ def _fp8_tag(mod: nn.Linear):
     return getattr(mod, "_fp8", None) if mod.training else None
 
 
+def _skinny(x, training: bool) -> bool:
+    """Decode-time rows: ``PDT_DECODE_GEMM=1``, ``eval()``, no autograd and at most 64 rows of ``x``. Then the
+    Linears go through ``linear_skinny`` (the weight-streaming kernel where its contract holds)."""
+    return (SW.decode_gemm and not training and not torch.is_grad_enabled() and isinstance(x, torch.Tensor)
+            and 0 < x.numel() // x.shape[-1] <= SKINNY_MAX_ROWS)
+
+
 def _linear(x, mod: nn.Linear) -> torch.Tensor:
     """``mod``'s bias-free GEMM: fp8 when ``enable_fp8`` tagged it and the shape is served (ops/fp8.py; ``x``
-    may then be an ``Fp8Act``, already e4m3 from ``add_rms_norm_fp8``), else bf16 (ops/linear.py)."""
+    may then be an ``Fp8Act``, already e4m3 from ``add_rms_norm_fp8``), else bf16 (ops/linear.py); decode-time
+    rows under ``PDT_DECODE_GEMM=1`` on the skinny GEMM."""
     t = _fp8_tag(mod)
     if t is not None and (isinstance(x, Fp8Act) or fp8_ok(x, mod.weight)):
         return fp8_linear(x, mod.weight, None, t[0], t[1])
+    if _skinny(x, mod.training):
+        return linear_skinny(x, mod.weight)
     return linear(x, mod.weight)
 
 
@@ -130,6 +140,8 @@ class LlamaMLP(nn.Module):
             y = fp8_swiglu_mlp(x, self.c_fc, self.c_proj)  # SwiGLU emits e4m3 for c_proj (PDT_FP8_SWIGLU)
             if y is not None:
                 return y
+        if _skinny(x, self.c_fc.training):  # c_fc with SwiGLU in the GEMM's epilogue: no [rows, 2F] round trip
+            return _linear(linear_skinny(x, self.c_fc.weight, swiglu=True), self.c_proj)
         return _linear(swiglu(_linear(x, self.c_fc)), self.c_proj)
 
 
@@ -192,6 +204,12 @@ class Llama(nn.Module):
         self.rope = RotaryTable(cfg.block_size, cfg.rope_base, HEAD_DIM)  # non-persistent fp32 buffers
         init_weights(self, n_layer=cfg.n_layer)
 
+    def _head(self, x: torch.Tensor) -> torch.Tensor:
+        """The LM head on the cached path's rows (always bf16; decode-time rows as in ``_linear``)."""
+        if _skinny(x, self.training):
+            return linear_skinny(x, self.lm_head.weight)
+        return linear(x, self.lm_head.weight)
+
     def forward(self, idx: torch.Tensor, targets: torch.Tensor | None = None):
         if idx.shape[1] > self.cfg.block_size:
             raise ValueError(f"sequence length {idx.shape[1]} exceeds block_size {self.cfg.block_size} "
@@ -242,7 +260,7 @@ class Llama(nn.Module):
                 prompt_lens = prompt_lens.clamp(1, T0)
             cache.set_lens(prompt_lens.to(torch.int32), bound=T0)
             last = x.gather(1, (prompt_lens.long() - 1)[:, None, None].expand(B, 1, x.shape[-1]))[:, 0]
-        return linear(last, self.lm_head.weight)
+        return self._head(last)
 
     def decode_step(self, tok: torch.Tensor, cache: KVCache) -> torch.Tensor:
         """One token per sequence: ``tok`` [B] sits at position ``cache.lens[b]``; returns the logits [B, V]
@@ -252,7 +270,7 @@ class Llama(nn.Module):
         x = F.embedding(tok[:, None], self.transformer.wte.weight)
         x = run_llama_blocks(self.transformer.h, x, self.transformer.ln_f, self.rope, cache)
         cache.advance(1)
-        return linear(x[:, 0], self.lm_head.weight)
+        return self._head(x[:, 0])
 
     def extend(self, idx: torch.Tensor, cache: KVCache, new_lens=None, last_only: bool = False) -> torch.Tensor:
         """Append ``idx`` [B, Tn] at positions ``cache.lens[b] + t`` of a cache that may already hold a
@@ -285,7 +303,7 @@ class Llama(nn.Module):
                 x = x[:, -1]
             else:  # a sequence that got nothing returns its row 0: the caller keeps what it had
                 x = x.gather(1, (new_lens.long() - 1).clamp(min=0)[:, None, None].expand(B, 1, x.shape[-1]))[:, 0]
-        return linear(x, self.lm_head.weight)
+        return self._head(x)
 
     def _prefill_chunked(self, idx: torch.Tensor, cache: KVCache, prompt_lens, chunk: int) -> torch.Tensor:
         """``prefill`` in slices of ``chunk`` positions: the first through ``prefill``, the rest through

@@ -14,6 +14,11 @@ mispredict the step (GPT-2-medium lost 3 % on them), hence not the default. Our 
 some shapes only (vit_qkv 1.08x, vit_fc2 1.03x, gpt2_proj + bias 1.05x; 0.61-0.94x on the others:
 profiles/r5/gemm_bn128.txt, profiles/r3/gemm_vs_hipblaslt.md), so all-or-nothing would lose. ``=1``: ours
 on every shape it serves, ``=0``: never. ``PDT_LINEAR_DUMP=path`` writes the decisions at exit.
+
+Inference on at most 64 rows (a decode step, a short extend) has a kernel of its own, ``linear_skinny``
+(csrc/kernels/gemm_skinny.hip): the weights stream once from memory to the matrix cores' registers, optionally
+with SwiGLU applied to ``c_fc``'s packed gate/up output in the same launch. The Llama decoder uses it under
+``PDT_DECODE_GEMM=1`` (default 0).
 """
 from __future__ import annotations
 
@@ -223,3 +228,42 @@ def linear_gelu(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
             or not _ours(x, weight, "gelu", bias, approximate == "tanh"):
         return None
     return _LinearGeluFn.apply(x, weight, bias, approximate == "tanh")
+
+
+# ---------------------------------------------------------------------------- decode-time Linears (M <= 64)
+SKINNY_STATS = {"native_calls": 0, "geo": None}  # launches of the skinny GEMM and the last (S, FT, NT) it ran with
+SKINNY_MAX_ROWS = 64
+
+
+def skinny_ok(x: torch.Tensor, w: torch.Tensor, swiglu: bool = False) -> bool:
+    """Inside gemm_skinny.hip's contract: GPU bf16, 1..64 rows, out features % 16 (% 32 with ``swiglu``: F % 16),
+    in features % 64, a contiguous 16-byte aligned weight below 2^31 bytes."""
+    if not (x.is_cuda and w.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and w.dim() == 2
+            and x.dim() >= 1 and x.shape[-1] == w.shape[1]):
+        return False
+    N, K = w.shape
+    rows = x.numel() // K if K else 0
+    return (1 <= rows <= SKINNY_MAX_ROWS and N % (32 if swiglu else 16) == 0 and N > 0 and K % 64 == 0 and K > 0
+            and w.is_contiguous() and w.data_ptr() % 16 == 0 and N * K * 2 < 2 ** 31)
+
+
+def linear_skinny(x: torch.Tensor, w: torch.Tensor, swiglu: bool = False, splits: Optional[int] = None) -> torch.Tensor:
+    """``x @ w.T`` (``swiglu``: SwiGLU of it, ``w`` the packed [gate; up] rows) for inference on at most 64 rows, on
+    the weight-streaming kernel. GPU bf16 inside the contract with no gradient to record; anything else (CPU,
+    fp32, ``PDT_DISABLE_NATIVE=1``, a shape outside the contract, autograd) is ``F.linear`` (then
+    ``ops.swiglu.swiglu``). ``splits``: grid split-K override (None: the kernel's rule)."""
+    needs_grad = torch.is_grad_enabled() and (x.requires_grad or w.requires_grad)
+    if use_native(x) and not needs_grad and skinny_ok(x, w, swiglu):
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        if x2.data_ptr() % 16 == 0:
+            mode, sp = (1 if swiglu else 0), int(splits or 0)
+            y = native().gemm_skinny(x2, w, mode, sp)
+            SKINNY_STATS["native_calls"] += 1
+            SKINNY_STATS["geo"] = tuple(int(v) for v in native().gemm_skinny_geo(x2.shape[0], w.shape[0], w.shape[1],
+                                                                                 mode, sp))
+            return y.view(*x.shape[:-1], y.shape[-1])
+    y = F.linear(x, w)
+    if swiglu:
+        from .swiglu import swiglu as _swiglu
+        y = _swiglu(y)
+    return y

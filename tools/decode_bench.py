@@ -318,6 +318,132 @@ def bench_generate(rounds, emit, prompt=128, new=128):
         del model, state
 
 
+GEMM_SHAPES = (("c_attn", 3072, 1024, False), ("attn c_proj", 1024, 1024, False), ("c_fc", 5632, 1024, False),
+               ("c_fc + SwiGLU", 5632, 1024, True), ("mlp c_proj", 1024, 2816, False), ("lm_head", 32000, 1024, False))
+GEMM_ROWS = (1, 8, 16, 32, 64)
+
+
+def bench_gemm(rounds, iters, emit):
+    """llama_medium's decode-time Linears: the skinny GEMM against F.linear (+ the SwiGLU kernel), each captured
+    and replayed, alternating, the weights rotating through >= 512 MiB of distinct copies (a window has at least
+    as many calls as there are copies, so no replay finds its weights in the Infinity Cache)."""
+    from pytorch_distributed_training_example_amd.ops._native import native
+    from pytorch_distributed_training_example_amd.ops.swiglu import swiglu
+    C, dev = native(), "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    for name, N, K, fused in GEMM_SHAPES:
+        ncopy = -(-ROTATE_BYTES // (N * K * 2))
+        calls = max(iters, ncopy)
+        w = (torch.randn(ncopy, N, K, device=dev, generator=g) / math.sqrt(K)).bfloat16()
+        emit(f"## {name}: N = {N}, K = {K}, {N * K * 2 / 2**20:.1f} MiB of weights x {ncopy} copies, {calls} calls per window")
+        for M in GEMM_ROWS:
+            x = torch.randn(M, K, device=dev, generator=g).bfloat16()
+            mode = 1 if fused else 0
+            geo = tuple(C.gemm_skinny_geo(M, N, K, mode, 0))
+            must = N * K * 2 + M * K * 2 + M * (N // 2 if fused else N) * 2
+
+            def ours(i):
+                return C.gemm_skinny(x, w[i % ncopy], mode, 0)
+
+            def lib(i):
+                y = F.linear(x, w[i % ncopy])
+                return swiglu(y) if fused else y
+
+            cands = {"skinny": ours, "library": lib}
+            if M == 8:  # the W loads without the non-temporal bit, same kernel otherwise
+                def plain(i):
+                    C.gemm_skinny_tune(0)
+                    y = C.gemm_skinny(x, w[i % ncopy], mode, 0)
+                    C.gemm_skinny_tune(1)
+                    return y
+                cands["skinny, plain W loads"] = plain
+            err = (ours(0).float() - lib(0).float()).abs().max().item()
+            t = _alternate(cands, rounds, calls)
+            med = {k: statistics.median(v[1]) for k, v in t.items()}
+            for k, (_, tg) in t.items():
+                emit(f"M {M:2d}  {k:<22} (S, FT, NT) = {geo}  replayed {med[k] * 1e3:6.1f} us ({min(tg) * 1e3:.1f}-"
+                     f"{max(tg) * 1e3:.1f})  {must / med[k] / 1e9:5.2f} TB/s  {med['library'] / med[k]:5.2f}x library")
+            emit(f"M {M:2d}  max |skinny - library| = {err:.3g}")
+        del w
+
+
+def bench_gemm_generate(rounds, emit, prompt=128, new=128):
+    """The captured llama_medium decode step and the 128-after-128-token generation on it, PDT_DECODE_GEMM 0
+    against 1 (and 1 with plain instead of non-temporal weight loads) in one process, alternating."""
+    from pytorch_distributed_training_example_amd.config import SW
+    from pytorch_distributed_training_example_amd.models import get_model
+    from pytorch_distributed_training_example_amd.models.precision import to_bf16_mixed
+    from pytorch_distributed_training_example_amd.ops._native import native
+    torch.manual_seed(0)
+    model = to_bf16_mixed(get_model("llama_medium").cuda()).eval()
+    idx = torch.randint(0, model.cfg.vocab_size, (B, prompt), generator=torch.Generator().manual_seed(1)).cuda()
+    configs = {"0": (False, 1), "1": (True, 1), "1, plain W loads": (True, 0)}  # name: (switch, gemm_skinny_tune)
+    states = {}
+
+    def select(name):
+        SW.decode_gemm = configs[name][0]
+        native().gemm_skinny_tune(configs[name][1])
+
+    with torch.no_grad():
+        for name in configs:
+            select(name)
+            cache = model.new_cache(B, prompt + new)
+            model.prefill(idx, cache)
+            tok = torch.zeros(B, dtype=torch.long, device="cuda")
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                model.decode_step(tok, cache)
+            torch.cuda.current_stream().wait_stream(side)
+            cache.reset()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                logits = model.decode_step(tok, cache)
+            states[name] = (cache, tok, graph, logits)
+
+        def gen(name):
+            select(name)
+            cache, tok, graph, logits = states[name]
+            cache.reset()
+            toks = [model.prefill(idx, cache).argmax(-1)]
+            cache.set_lens(cache.lens, bound=prompt + new)
+            for _ in range(new - 1):
+                tok.copy_(toks[-1])
+                graph.replay()
+                toks.append(logits.argmax(-1))
+            return torch.stack(toks, 1)
+
+        toks = {name: gen(name) for name in configs}
+        torch.cuda.synchronize()
+        ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
+        t_gen, t_step = {n: [] for n in configs}, {n: [] for n in configs}
+        for _ in range(rounds):
+            for name in configs:
+                s, e = ev(), ev()
+                s.record()
+                gen(name)
+                e.record()
+                torch.cuda.synchronize()
+                t_gen[name].append(s.elapsed_time(e))
+                states[name][0].set_lens([prompt] * B)
+                s, e = ev(), ev()
+                s.record()
+                for _ in range(32):
+                    states[name][2].replay()
+                e.record()
+                torch.cuda.synchronize()
+                t_step[name].append(s.elapsed_time(e) / 32)
+    SW.reload()
+    native().gemm_skinny_tune(1)
+    for name in configs:
+        mg, ms = statistics.median(t_gen[name]), statistics.median(t_step[name])
+        emit(f"llama_medium PDT_DECODE_GEMM={name}: {prompt}+{new} tokens x {B} on the captured step {mg:8.1f} ms "
+             f"({min(t_gen[name]):.1f}-{max(t_gen[name]):.1f}), {B * new / mg * 1e3:7.0f} new tok/s; replayed step at "
+             f"position {prompt}..{prompt + 31}: {ms:.3f} ms ({min(t_step[name]):.3f}-{max(t_step[name]):.3f})")
+    emit(f"llama_medium: tokens with the switch on == off: {float((toks['1'] == toks['0']).float().mean()):.3f} of "
+         "positions (the two paths round differently; after a near-tie the rest differs)")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--rounds", type=int, default=7)
@@ -326,6 +452,8 @@ def main(argv=None):
     ap.add_argument("--no-generate", action="store_true", help="kernel only")
     ap.add_argument("--no-kernel", action="store_true", help="generation only")
     ap.add_argument("--extend", action="store_true", help="the multi-token append kernel instead")
+    ap.add_argument("--gemm", action="store_true", help="the decode-time Linears: skinny GEMM against the library, "
+                    "then the generation with PDT_DECODE_GEMM 0 and 1")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -338,11 +466,16 @@ def main(argv=None):
 
     emit(f"# {torch.cuda.get_device_name(0)}; B={B} H={H} Dh={DH} capacity={CAP} bf16; median of {a.rounds} alternating "
          f"rounds (min-max), {a.iters} calls per window, device events")
-    if a.extend:
+    if a.gemm:
+        if not a.no_kernel:
+            bench_gemm(a.rounds, a.iters, emit)
+        if not a.no_generate:
+            bench_gemm_generate(a.gen_rounds, emit)
+    elif a.extend:
         bench_extend(a.rounds, a.iters, emit)
     elif not a.no_kernel:
         bench_kernel(a.rounds, a.iters, emit)
-    if not a.no_generate and not a.extend:
+    if not a.no_generate and not a.extend and not a.gemm:
         bench_generate(a.gen_rounds, emit)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
