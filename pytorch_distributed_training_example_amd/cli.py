@@ -92,6 +92,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--sample-tokens", type=int, default=0, metavar="N",
                    help="llama_* only: after the last epoch rank 0 generates N tokens on the KV cache and prints "
                         "'Sample: [ids]' (with --resume and a finished checkpoint: sample it without training)")
+    p.add_argument("--sample-weights", choices=["bf16", "fp8"], default="bf16",
+                   help="llama_* only, with --sample-tokens: fp8 quantises the Linear weights row-wise to e4m3 before "
+                        "sampling (Llama.quantize_decode_weights: decode steps then stream one byte per weight)")
     p.add_argument("--sample-prompt", default="1", metavar="IDS", help="comma-separated prompt token ids (default: 1)")
     p.add_argument("--sample-temperature", type=float, default=0.0, metavar="T",
                    help="0 (default): greedy; otherwise sample from softmax(logits / T), seeded from --seed")
@@ -135,6 +138,10 @@ def kv_heads_ok(model_name: str, n: int) -> bool:
 
 def sample_args_error(args) -> Optional[str]:
     """Why the --sample-* flags cannot be served, or None: checked before any process is spawned."""
+    fp8_weights = getattr(args, "sample_weights", "bf16") != "bf16"
+    if fp8_weights and _llama_heads(args.model) is None:
+        return (f"--sample-weights {args.sample_weights}: the quantised decode weights belong to the llama_* models' "
+                f"generation (model {args.model} has none); drop the flag or choose one of them")
     if args.sample_tokens == 0:
         return None
     if _llama_heads(args.model) is None:
@@ -358,6 +365,8 @@ def run(rank: int, world: int, args) -> dict:
     if getattr(args, "sample_tokens", 0) and rank == 0:
         gen = torch.Generator(device=device).manual_seed(args.seed)
         prompt = torch.tensor([parse_prompt(args.sample_prompt)], device=device)
+        if getattr(args, "sample_weights", "bf16") == "fp8":
+            model.quantize_decode_weights()
         toks = model.generate(prompt, args.sample_tokens, temperature=args.sample_temperature,
                               top_k=args.sample_top_k, generator=gen)
         result["sample"] = toks[0].tolist()

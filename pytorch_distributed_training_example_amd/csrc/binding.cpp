@@ -2066,6 +2066,61 @@ Tensor gemm_skinny(Tensor x, Tensor w, int64_t mode, int64_t splits, c10::option
 // A/B only: non-temporal W loads on (1, the default) / off (0); returns the previous setting.
 int64_t gemm_skinny_tune(int64_t w_nontemporal) { return pdt_gemm_skinny_tune((int)w_nontemporal); }
 
+// ----------------------------------------------------------------------------- W8A16 skinny GEMM (gemm_skinny_w8.hip)
+// w [N, K] bf16 -> (wq [N, K] e4m3fn, scale [N] fp32): one scale per row, amax / 448 (1 for a zero row).
+std::vector<Tensor> quantize_rows_e4m3(Tensor w) {
+  const Op op("quantize_rows_e4m3", w);
+  TORCH_CHECK(w.scalar_type() == at::kBFloat16 && w.dim() == 2 && w.is_contiguous() && aligned16(w),
+              "quantize_rows_e4m3: w must be a contiguous 16-byte aligned bf16 [N, K]");
+  const int64_t N = w.size(0), K = w.size(1);
+  TORCH_CHECK(N >= 1 && K >= 8 && K % 8 == 0 && N <= 0x7fffffffLL && K <= 0x7fffffffLL,
+              "quantize_rows_e4m3: N >= 1 and K % 8 == 0, got ", N, " x ", K);
+  auto wq = at::empty({N, K}, w.options().dtype(at::kFloat8_e4m3fn));
+  auto scale = at::empty({N}, w.options().dtype(at::kFloat));
+  const int rc = pdt_quant_rows_e4m3(bf16_ptr(w), byte_ptr(wq), scale.data_ptr<float>(), (int)N, (int)K, stream());
+  TORCH_CHECK(rc == 0, "pdt_quant_rows_e4m3 failed: ", rc);
+  return {wq, scale};
+}
+
+// (S, FT, NT) of gemm_skinny_w8 for x [M, K], wq [N, K]; as gemm_skinny_geo. Refuses shapes outside the contract.
+std::vector<int64_t> gemm_skinny_w8_geo(int64_t M, int64_t N, int64_t K, int64_t mode, int64_t splits) {
+  TORCH_CHECK(M >= 1 && M <= 64, "gemm_skinny_w8: 1 <= M <= 64 rows, got ", M);
+  TORCH_CHECK(N >= 16 && N % 16 == 0 && N <= 0x7fffffffLL, "gemm_skinny_w8: N % 16 == 0, got ", N);
+  TORCH_CHECK(K >= 128 && K % 128 == 0 && K < (1 << 24), "gemm_skinny_w8: K % 128 == 0 and K < 2^24, got ", K);
+  TORCH_CHECK(mode == 0 || mode == 1, "gemm_skinny_w8: mode 0 (plain) or 1 (SwiGLU), got ", mode);
+  TORCH_CHECK(mode == 0 || N % 32 == 0, "gemm_skinny_w8: SwiGLU needs wq = [gate; up] with F = N / 2 a multiple of 16, got N = ", N);
+  TORCH_CHECK(splits >= 0 && splits <= 65535, "gemm_skinny_w8: splits in [0, 65535], got ", splits);
+  TORCH_CHECK(N * K < 0x80000000LL, "gemm_skinny_w8: wq of ", N, " x ", K, " is past 2^31 bytes");
+  int g[3];
+  const int rc = pdt_gemm_skinny_w8_geo((int)M, (int)N, (int)K, (int)mode, (int)splits, g);
+  TORCH_CHECK(rc == 0, "gemm_skinny_w8: pdt_gemm_skinny_w8_geo failed: ", rc);
+  return {g[0], g[1], g[2]};
+}
+
+// y [M, N] = bf16(scale[n] * x [M, K] float(wq [N, K])^T) (mode 0) or y [M, N / 2] = swiglu of it (mode 1) for
+// M <= 64: x bf16, wq e4m3fn, scale fp32 [N]. y_out: write into this tensor instead of a new one.
+Tensor gemm_skinny_w8(Tensor x, Tensor wq, Tensor scale, int64_t mode, int64_t splits, c10::optional<Tensor> y_out) {
+  const Op op("gemm_skinny_w8", x);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && wq.scalar_type() == at::kFloat8_e4m3fn,
+              "gemm_skinny_w8: x must be bf16 and wq float8_e4m3fn");
+  TORCH_CHECK(wq.device() == op.dev, "gemm_skinny_w8: wq must be on ", op.dev);
+  TORCH_CHECK(x.dim() == 2 && wq.dim() == 2 && x.size(1) == wq.size(1), "gemm_skinny_w8: x [M, K] and wq [N, K]");
+  TORCH_CHECK(x.is_contiguous() && wq.is_contiguous() && aligned16(x) && aligned16(wq),
+              "gemm_skinny_w8: x and wq must be contiguous and 16-byte aligned");
+  const int64_t M = x.size(0), K = x.size(1), N = wq.size(0);
+  TORCH_CHECK(scale.dim() == 1 && aligned16(scale), "gemm_skinny_w8: scale must be a 16-byte aligned fp32 [N]");
+  const float* sc = f32_ptr(op, "scale", scale, N);
+  const std::vector<int64_t> geo = gemm_skinny_w8_geo(M, N, K, mode, splits);
+  const int64_t S = geo[0];
+  auto y = out_or_new(op, "y_out", y_out, {M, mode == 1 ? N / 2 : N}, x.options());
+  Tensor ws;
+  if (S > 1) ws = at::empty({S * M * N}, x.options().dtype(at::kFloat));
+  const int rc = pdt_gemm_skinny_w8(bf16_ptr(x), byte_ptr(wq), sc, bf16_out(y), ptr_or_null<float>(ws), (int)M, (int)N,
+                                    (int)K, (int)mode, (int)S, (int)geo[1], (int)geo[2], stream());
+  TORCH_CHECK(rc == 0, "gemm_skinny_w8: pdt_gemm_skinny_w8 failed: ", rc);
+  return y;
+}
+
 // ----------------------------------------------------------------------------- dropout (philox.h)
 const int64_t* ticket_ptr(const Tensor& ticket, const Tensor& like) {
   TORCH_CHECK(ticket.is_cuda() && ticket.scalar_type() == at::kLong && ticket.numel() == 2 && ticket.is_contiguous() &&
@@ -2971,6 +3026,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_skinny", &gemm_skinny, py::arg("x"), py::arg("w"), py::arg("mode") = 0, py::arg("splits") = 0,
         py::arg("y_out") = py::none());
   m.def("gemm_skinny_tune", &gemm_skinny_tune, py::arg("w_nontemporal"));
+  m.def("quantize_rows_e4m3", &quantize_rows_e4m3, py::arg("w"));
+  m.def("gemm_skinny_w8_geo", &gemm_skinny_w8_geo, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("mode") = 0,
+        py::arg("splits") = 0);
+  m.def("gemm_skinny_w8", &gemm_skinny_w8, py::arg("x"), py::arg("wq"), py::arg("scale"), py::arg("mode") = 0,
+        py::arg("splits") = 0, py::arg("y_out") = py::none());
   m.def("swiglu_bwd", &swiglu_bwd, py::arg("dy"), py::arg("gu"), py::arg("dgu_out") = py::none());
   py::class_<P2PComm>(m, "P2PComm")
       .def(py::init<int, int, int64_t, int, int>(), py::arg("rank"), py::arg("world"), py::arg("capacity_bytes"),

@@ -20,6 +20,11 @@ Parameter names follow the nanoGPT-style layout of models/gpt2.py: ``transformer
 ``transformer.h.{i}.ln_1``, ``.attn.c_attn`` (packed q, k, v rows: ``(n_head + 2·n_kv_head)·64`` of them),
 ``.attn.c_proj``, ``.ln_2``, ``.mlp.c_fc`` (packed [gate; up] rows), ``.mlp.c_proj``, ``transformer.ln_f``,
 ``lm_head``; ``from_hf_state_dict`` maps a Hugging Face Llama state dict onto it.
+
+Weight-only 8-bit decoding: ``Llama.quantize_decode_weights()`` quantises every block Linear and the LM head
+row-wise to e4m3 (ops/linear.py ``quantize_rows_e4m3``); calls on at most 64 rows in ``eval()`` under
+``no_grad`` then run the W8A16 skinny GEMM (``linear_skinny_w8``), whatever ``PDT_DECODE_GEMM`` says. More rows
+(a long prefill) and training keep the bf16 weights, which stay in place; ``drop_decode_weights()`` undoes it.
 """
 from __future__ import annotations
 
@@ -35,7 +40,7 @@ from ..ops.attention import attention_decode, attention_extend, attention_qkv
 from ..ops.cross_entropy import cross_entropy
 from ..ops.fp8 import Fp8Act, add_rms_norm_fp8, fp8_input_slot, fp8_linear, fp8_ok, fp8_swiglu_mlp, rms_fp8_ok
 from ..ops.kv_cache import KVCache
-from ..ops.linear import SKINNY_MAX_ROWS, linear, linear_skinny
+from ..ops.linear import SKINNY_MAX_ROWS, linear, linear_skinny, linear_skinny_w8, quantize_rows_e4m3
 from ..ops.rmsnorm import RMSNorm, add_rms_norm
 from ..ops.rope import RotaryTable, rope_append_, rope_qkv_
 from ..ops.swiglu import swiglu
@@ -73,13 +78,30 @@ def _skinny(x, training: bool) -> bool:
             and 0 < x.numel() // x.shape[-1] <= SKINNY_MAX_ROWS)
 
 
+def _w8(x, mod: nn.Linear):
+    """``mod``'s (wq, scale) when ``quantize_decode_weights`` left them there and this call is decode-time
+    (``eval()``, no autograd, at most 64 rows); else None. Weights updated in place since then are refused."""
+    q = getattr(mod, "_w8", None)
+    if (q is None or mod.training or torch.is_grad_enabled() or not isinstance(x, torch.Tensor)
+            or not 0 < x.numel() // x.shape[-1] <= SKINNY_MAX_ROWS):
+        return None
+    if q[2] != mod.weight._version:
+        raise RuntimeError("a Linear's weight changed in place after quantize_decode_weights(): its e4m3 copy is "
+                           "stale; call quantize_decode_weights() again (or drop_decode_weights())")
+    return q[0], q[1]
+
+
 def _linear(x, mod: nn.Linear) -> torch.Tensor:
     """``mod``'s bias-free GEMM: fp8 when ``enable_fp8`` tagged it and the shape is served (ops/fp8.py; ``x``
     may then be an ``Fp8Act``, already e4m3 from ``add_rms_norm_fp8``), else bf16 (ops/linear.py); decode-time
-    rows under ``PDT_DECODE_GEMM=1`` on the skinny GEMM."""
+    rows on the W8A16 skinny GEMM after ``quantize_decode_weights()``, else under ``PDT_DECODE_GEMM=1`` on the
+    bf16 skinny GEMM."""
     t = _fp8_tag(mod)
     if t is not None and (isinstance(x, Fp8Act) or fp8_ok(x, mod.weight)):
         return fp8_linear(x, mod.weight, None, t[0], t[1])
+    q = _w8(x, mod)
+    if q is not None:
+        return linear_skinny_w8(x, q[0], q[1])
     if _skinny(x, mod.training):
         return linear_skinny(x, mod.weight)
     return linear(x, mod.weight)
@@ -140,6 +162,9 @@ class LlamaMLP(nn.Module):
             y = fp8_swiglu_mlp(x, self.c_fc, self.c_proj)  # SwiGLU emits e4m3 for c_proj (PDT_FP8_SWIGLU)
             if y is not None:
                 return y
+        q = _w8(x, self.c_fc)
+        if q is not None:  # as below, on the e4m3 weights
+            return _linear(linear_skinny_w8(x, q[0], q[1], swiglu=True), self.c_proj)
         if _skinny(x, self.c_fc.training):  # c_fc with SwiGLU in the GEMM's epilogue: no [rows, 2F] round trip
             return _linear(linear_skinny(x, self.c_fc.weight, swiglu=True), self.c_proj)
         return _linear(swiglu(_linear(x, self.c_fc)), self.c_proj)
@@ -205,7 +230,11 @@ class Llama(nn.Module):
         init_weights(self, n_layer=cfg.n_layer)
 
     def _head(self, x: torch.Tensor) -> torch.Tensor:
-        """The LM head on the cached path's rows (always bf16; decode-time rows as in ``_linear``)."""
+        """The LM head on the cached path's rows (never the training fp8 path; decode-time rows as in
+        ``_linear``)."""
+        q = _w8(x, self.lm_head)
+        if q is not None:
+            return linear_skinny_w8(x, q[0], q[1])
         if _skinny(x, self.training):
             return linear_skinny(x, self.lm_head.weight)
         return linear(x, self.lm_head.weight)
@@ -220,6 +249,29 @@ class Llama(nn.Module):
         if targets is None:
             return logits
         return cross_entropy(logits.reshape(-1, logits.shape[-1]), targets.reshape(-1))
+
+    # ------------------------------------------------------------------ weight-only 8-bit decoding
+    def _decode_linears(self):
+        for blk in self.transformer.h:
+            yield from (blk.attn.c_attn, blk.attn.c_proj, blk.mlp.c_fc, blk.mlp.c_proj)
+        yield self.lm_head
+
+    @torch.no_grad()
+    def quantize_decode_weights(self) -> "Llama":
+        """Quantise every block Linear and the LM head row-wise to e4m3 for decode-time calls (at most 64 rows,
+        ``eval()``, no autograd): each module gets ``_w8 = (wq, scale, weight._version)`` as a plain attribute,
+        not a parameter or buffer, so ``state_dict()`` is unchanged and the bf16 weights stay for everything
+        else. Call it again after the weights change."""
+        for mod in self._decode_linears():
+            wq, scale = quantize_rows_e4m3(mod.weight.detach().to(torch.bfloat16))
+            mod._w8 = (wq, scale, mod.weight._version)
+        return self
+
+    def drop_decode_weights(self) -> "Llama":
+        for mod in self._decode_linears():
+            if hasattr(mod, "_w8"):
+                del mod._w8
+        return self
 
     # ------------------------------------------------------------------ generation on a KV cache
     def new_cache(self, batch: int, capacity: int | None = None) -> KVCache:

@@ -18,7 +18,9 @@ on every shape it serves, ``=0``: never. ``PDT_LINEAR_DUMP=path`` writes the dec
 Inference on at most 64 rows (a decode step, a short extend) has a kernel of its own, ``linear_skinny``
 (csrc/kernels/gemm_skinny.hip): the weights stream once from memory to the matrix cores' registers, optionally
 with SwiGLU applied to ``c_fc``'s packed gate/up output in the same launch. The Llama decoder uses it under
-``PDT_DECODE_GEMM=1`` (default 0).
+``PDT_DECODE_GEMM=1`` (default 0). ``quantize_rows_e4m3`` + ``linear_skinny_w8`` are the same Linears on weights
+stored as e4m3 bytes with one fp32 scale per output feature (csrc/kernels/gemm_skinny_w8.hip): half the bytes to
+stream; ``Llama.quantize_decode_weights()`` opts a model in.
 """
 from __future__ import annotations
 
@@ -231,7 +233,8 @@ def linear_gelu(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
 
 
 # ---------------------------------------------------------------------------- decode-time Linears (M <= 64)
-SKINNY_STATS = {"native_calls": 0, "geo": None}  # launches of the skinny GEMM and the last (S, FT, NT) it ran with
+# launches of the bf16 skinny GEMM, the last (S, FT, NT) either kernel ran with, launches of the e4m3-weight one
+SKINNY_STATS = {"native_calls": 0, "geo": None, "w8_calls": 0}
 SKINNY_MAX_ROWS = 64
 
 
@@ -263,6 +266,72 @@ def linear_skinny(x: torch.Tensor, w: torch.Tensor, swiglu: bool = False, splits
                                                                                  mode, sp))
             return y.view(*x.shape[:-1], y.shape[-1])
     y = F.linear(x, w)
+    if swiglu:
+        from .swiglu import swiglu as _swiglu
+        y = _swiglu(y)
+    return y
+
+
+# ---------------------------------------------------------------------------- the same on e4m3 weights (W8A16)
+E4M3_MAX = 448.0
+
+
+def quantize_rows_e4m3(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``w`` [N, K] bf16 -> (``wq`` [N, K] float8_e4m3fn, ``scale`` [N] fp32), one scale per output feature, in
+    fp32: amax = max_k |w|, scale = amax * (1 / 448) (1 for a zero row), wq = e4m3(clamp(w * (448 / amax), +-448)),
+    round to nearest even. The kernel on the GPU, the same formula in torch elsewhere (CPU,
+    ``PDT_DISABLE_NATIVE=1``, K % 8 != 0): equal bytes and scales. A NaN or Inf in ``w`` is refused."""
+    if w.dim() != 2 or w.dtype != torch.bfloat16:
+        raise ValueError(f"quantize_rows_e4m3: a bf16 [N, K] weight, got {w.dtype} {tuple(w.shape)}")
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("quantize_rows_e4m3: the weight holds NaN or Inf")
+    if use_native(w) and w.shape[1] % 8 == 0 and w.numel() > 0:
+        wc = w.contiguous()
+        if wc.data_ptr() % 16 == 0:
+            wq, scale = native().quantize_rows_e4m3(wc)
+            return wq, scale
+    wf = w.float()
+    amax = wf.abs().amax(1)
+    zero = amax == 0
+    scale = torch.where(zero, torch.ones_like(amax), amax * torch.tensor(1.0 / E4M3_MAX, dtype=torch.float32))
+    # (a division of tensors: ``448 / amax`` would be ``amax.reciprocal() * 448``, two roundings and other bytes)
+    inv = torch.where(zero, torch.zeros_like(amax), torch.full_like(amax, E4M3_MAX) / amax)
+    return (wf * inv[:, None]).clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn), scale
+
+
+def skinny_w8_ok(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor, swiglu: bool = False) -> bool:
+    """Inside gemm_skinny_w8.hip's contract: GPU, bf16 rows (1..64), e4m3 weights with an fp32 scale per output
+    feature, out features % 16 (% 32 with ``swiglu``), in features % 128 and below 2^24, contiguous 16-byte
+    aligned weights and scales, the weight below 2^31 bytes."""
+    if not (x.is_cuda and wq.is_cuda and scale.is_cuda and x.dtype == torch.bfloat16
+            and wq.dtype == torch.float8_e4m3fn and scale.dtype == torch.float32 and wq.dim() == 2 and x.dim() >= 1
+            and x.shape[-1] == wq.shape[1] and scale.shape == (wq.shape[0],)):
+        return False
+    N, K = wq.shape
+    rows = x.numel() // K if K else 0
+    return (1 <= rows <= SKINNY_MAX_ROWS and N % (32 if swiglu else 16) == 0 and N > 0 and K % 128 == 0
+            and 0 < K < 2 ** 24 and wq.is_contiguous() and wq.data_ptr() % 16 == 0 and scale.is_contiguous()
+            and scale.data_ptr() % 16 == 0 and N * K < 2 ** 31)
+
+
+def linear_skinny_w8(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor, swiglu: bool = False,
+                     splits: Optional[int] = None) -> torch.Tensor:
+    """``x @ (wq.float() * scale[:, None]).T`` (``swiglu``: SwiGLU of it, ``wq`` the packed [gate; up] rows) for
+    inference on at most 64 rows, on the W8A16 weight-streaming kernel: the scale multiplies the fp32 sum once.
+    GPU bf16 rows inside the contract with no gradient to record; anything else (CPU, fp32,
+    ``PDT_DISABLE_NATIVE=1``, a shape outside the contract, autograd on ``x``) is ``F.linear`` on the dequantised
+    weight (then ``ops.swiglu.swiglu``). ``splits``: grid split-K override (None: the kernel's rule)."""
+    needs_grad = torch.is_grad_enabled() and x.requires_grad
+    if use_native(x) and not needs_grad and skinny_w8_ok(x, wq, scale, swiglu):
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        if x2.data_ptr() % 16 == 0:
+            mode, sp = (1 if swiglu else 0), int(splits or 0)
+            y = native().gemm_skinny_w8(x2, wq, scale, mode, sp)
+            SKINNY_STATS["w8_calls"] += 1
+            SKINNY_STATS["geo"] = tuple(int(v) for v in native().gemm_skinny_w8_geo(x2.shape[0], wq.shape[0],
+                                                                                    wq.shape[1], mode, sp))
+            return y.view(*x.shape[:-1], y.shape[-1])
+    y = F.linear(x, (wq.float() * scale[:, None]).to(x.dtype))
     if swiglu:
         from .swiglu import swiglu as _swiglu
         y = _swiglu(y)

@@ -36,6 +36,12 @@ once and replayed, taking turns within every round, over rotating caches, device
   sdpa      F.scaled_dot_product_attention with an explicit [Tn, lens + Tn] mask on K/V materialised at 16
             heads and cut to lens + Tn keys (the expansion and the cut are not timed)
 
+--gemm-w8: the decode-time Linears on e4m3 weights. llama_medium's five Linears (and c_fc + SwiGLU) at M in
+{1, 8, 16, 32, 64}: the W8A16 skinny GEMM, the bf16 skinny GEMM and F.linear, the --gemm recipe (captured and
+replayed, weights rotating through 512 MiB of distinct copies, alternating, device events, median of the rounds);
+each line's rate is over the bytes that candidate must move. Then the generation A/B under PDT_DECODE_GEMM=1:
+the captured step and 128 tokens after a 128-token prompt, bf16 weights against quantize_decode_weights().
+
     python tools/decode_bench.py [--rounds 7] [--iters 50] [--gen-rounds 3] [--no-generate] [--extend] [--out FILE]
 """
 from __future__ import annotations
@@ -444,6 +450,132 @@ def bench_gemm_generate(rounds, emit, prompt=128, new=128):
          "positions (the two paths round differently; after a near-tie the rest differs)")
 
 
+def bench_gemm_w8(rounds, iters, emit):
+    """As bench_gemm, with the e4m3-weight kernel as a third candidate; every candidate rotates through its own
+    >= 512 MiB of distinct weight copies."""
+    from pytorch_distributed_training_example_amd.ops._native import native
+    from pytorch_distributed_training_example_amd.ops.swiglu import swiglu
+    C, dev = native(), "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    for name, N, K, fused in GEMM_SHAPES:
+        ncopy, ncopy8 = -(-ROTATE_BYTES // (N * K * 2)), -(-ROTATE_BYTES // (N * K))
+        calls = max(iters, ncopy8)
+        w = (torch.randn(ncopy, N, K, device=dev, generator=g) / math.sqrt(K)).bfloat16()
+        q = [C.quantize_rows_e4m3(w[i % ncopy]) for i in range(ncopy8)]
+        wq, sc = torch.stack([a for a, _ in q]), torch.stack([b for _, b in q])
+        del q
+        emit(f"## {name}: N = {N}, K = {K}: {N * K / 2**20:.1f} MiB e4m3 x {ncopy8} copies, {N * K * 2 / 2**20:.1f} MiB bf16 "
+             f"x {ncopy} copies, {calls} calls per window")
+        for M in GEMM_ROWS:
+            x = torch.randn(M, K, device=dev, generator=g).bfloat16()
+            mode = 1 if fused else 0
+            geo8, geo = tuple(C.gemm_skinny_w8_geo(M, N, K, mode, 0)), tuple(C.gemm_skinny_geo(M, N, K, mode, 0))
+            io = M * K * 2 + M * (N // 2 if fused else N) * 2
+            must = {"w8": N * K + N * 4 + io, "skinny": N * K * 2 + io, "library": N * K * 2 + io}
+
+            def w8(i):
+                return C.gemm_skinny_w8(x, wq[i % ncopy8], sc[i % ncopy8], mode, 0)
+
+            def ours(i):
+                return C.gemm_skinny(x, w[i % ncopy], mode, 0)
+
+            def lib(i):
+                y = F.linear(x, w[i % ncopy])
+                return swiglu(y) if fused else y
+
+            cands = {"w8": w8, "skinny": ours, "library": lib}
+            err = (w8(0).float() - ours(0).float()).abs().max().item()
+            t = _alternate(cands, rounds, calls)
+            med = {k: statistics.median(v[1]) for k, v in t.items()}
+            for k, (_, tg) in t.items():
+                emit(f"M {M:2d}  {k:<8} (S, FT, NT) = {geo8 if k == 'w8' else geo}  replayed {med[k] * 1e3:6.1f} us "
+                     f"({min(tg) * 1e3:.1f}-{max(tg) * 1e3:.1f})  {must[k] / med[k] / 1e9:5.2f} TB/s  "
+                     f"{med['skinny'] / med[k]:5.2f}x skinny")
+            emit(f"M {M:2d}  max |w8 - skinny| = {err:.3g} (the quantisation)")
+        del w, wq, sc
+
+
+def bench_gemm_w8_generate(rounds, emit, prompt=128, new=128):
+    """The captured llama_medium decode step and the 128-after-128-token generation on it under PDT_DECODE_GEMM=1:
+    bf16 weights against quantize_decode_weights(), one process, alternating."""
+    from pytorch_distributed_training_example_amd.config import SW
+    from pytorch_distributed_training_example_amd.models import get_model
+    from pytorch_distributed_training_example_amd.models.precision import to_bf16_mixed
+    torch.manual_seed(0)
+    model = to_bf16_mixed(get_model("llama_medium").cuda()).eval()
+    idx = torch.randint(0, model.cfg.vocab_size, (B, prompt), generator=torch.Generator().manual_seed(1)).cuda()
+    SW.decode_gemm = True
+    quantised = model.quantize_decode_weights()._decode_linears
+    saved = [m._w8 for m in quantised()]
+    model.drop_decode_weights()
+    states = {}
+
+    def select(name):
+        for m, q in zip(quantised(), saved):
+            if name == "e4m3":
+                m._w8 = q
+            elif hasattr(m, "_w8"):
+                del m._w8
+
+    with torch.no_grad():
+        for name in ("bf16", "e4m3"):
+            select(name)
+            cache = model.new_cache(B, prompt + new)
+            model.prefill(idx, cache)
+            tok = torch.zeros(B, dtype=torch.long, device="cuda")
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                model.decode_step(tok, cache)
+            torch.cuda.current_stream().wait_stream(side)
+            cache.reset()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                logits = model.decode_step(tok, cache)
+            states[name] = (cache, tok, graph, logits)
+
+        def gen(name):
+            select(name)
+            cache, tok, graph, logits = states[name]
+            cache.reset()
+            toks = [model.prefill(idx, cache).argmax(-1)]
+            cache.set_lens(cache.lens, bound=prompt + new)
+            for _ in range(new - 1):
+                tok.copy_(toks[-1])
+                graph.replay()
+                toks.append(logits.argmax(-1))
+            return torch.stack(toks, 1)
+
+        toks = {name: gen(name) for name in states}
+        torch.cuda.synchronize()
+        ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
+        t_gen, t_step = {n: [] for n in states}, {n: [] for n in states}
+        for _ in range(rounds):
+            for name in states:
+                s, e = ev(), ev()
+                s.record()
+                gen(name)
+                e.record()
+                torch.cuda.synchronize()
+                t_gen[name].append(s.elapsed_time(e))
+                states[name][0].set_lens([prompt] * B)
+                s, e = ev(), ev()
+                s.record()
+                for _ in range(32):
+                    states[name][2].replay()
+                e.record()
+                torch.cuda.synchronize()
+                t_step[name].append(s.elapsed_time(e) / 32)
+    SW.reload()
+    for name in states:
+        mg, ms = statistics.median(t_gen[name]), statistics.median(t_step[name])
+        emit(f"llama_medium PDT_DECODE_GEMM=1, {name} weights: {prompt}+{new} tokens x {B} on the captured step {mg:8.1f} ms "
+             f"({min(t_gen[name]):.1f}-{max(t_gen[name]):.1f}), {B * new / mg * 1e3:7.0f} new tok/s; replayed step at "
+             f"position {prompt}..{prompt + 31}: {ms:.3f} ms ({min(t_step[name]):.3f}-{max(t_step[name]):.3f})")
+    emit(f"llama_medium: tokens with e4m3 weights == bf16 weights: {float((toks['e4m3'] == toks['bf16']).float().mean()):.3f} "
+         "of positions (a random-weight model: the quantisation moves near-ties, after which the rest differs)")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--rounds", type=int, default=7)
@@ -454,6 +586,9 @@ def main(argv=None):
     ap.add_argument("--extend", action="store_true", help="the multi-token append kernel instead")
     ap.add_argument("--gemm", action="store_true", help="the decode-time Linears: skinny GEMM against the library, "
                     "then the generation with PDT_DECODE_GEMM 0 and 1")
+    ap.add_argument("--gemm-w8", action="store_true", help="the decode-time Linears on e4m3 weights: the W8A16 skinny "
+                    "GEMM against the bf16 one and the library, then the generation with and without "
+                    "quantize_decode_weights() under PDT_DECODE_GEMM=1")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -466,7 +601,12 @@ def main(argv=None):
 
     emit(f"# {torch.cuda.get_device_name(0)}; B={B} H={H} Dh={DH} capacity={CAP} bf16; median of {a.rounds} alternating "
          f"rounds (min-max), {a.iters} calls per window, device events")
-    if a.gemm:
+    if a.gemm_w8:
+        if not a.no_kernel:
+            bench_gemm_w8(a.rounds, a.iters, emit)
+        if not a.no_generate:
+            bench_gemm_w8_generate(a.gen_rounds, emit)
+    elif a.gemm:
         if not a.no_kernel:
             bench_gemm(a.rounds, a.iters, emit)
         if not a.no_generate:
@@ -475,7 +615,7 @@ def main(argv=None):
         bench_extend(a.rounds, a.iters, emit)
     elif not a.no_kernel:
         bench_kernel(a.rounds, a.iters, emit)
-    if not a.no_generate and not a.extend and not a.gemm:
+    if not a.no_generate and not a.extend and not a.gemm and not a.gemm_w8:
         bench_generate(a.gen_rounds, emit)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
