@@ -95,6 +95,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--sample-weights", choices=["bf16", "fp8"], default="bf16",
                    help="llama_* only, with --sample-tokens: fp8 quantises the Linear weights row-wise to e4m3 before "
                         "sampling (Llama.quantize_decode_weights: decode steps then stream one byte per weight)")
+    p.add_argument("--sample-cache", choices=["contiguous", "paged"], default="contiguous",
+                   help="llama_* only, with --sample-tokens: paged generates on a PagedKVCache (pages of 64 positions "
+                        "found through a block table) instead of one contiguous slab per sequence")
     p.add_argument("--sample-prompt", default="1", metavar="IDS", help="comma-separated prompt token ids (default: 1)")
     p.add_argument("--sample-temperature", type=float, default=0.0, metavar="T",
                    help="0 (default): greedy; otherwise sample from softmax(logits / T), seeded from --seed")
@@ -368,7 +371,8 @@ def run(rank: int, world: int, args) -> dict:
         if getattr(args, "sample_weights", "bf16") == "fp8":
             model.quantize_decode_weights()
         toks = model.generate(prompt, args.sample_tokens, temperature=args.sample_temperature,
-                              top_k=args.sample_top_k, generator=gen)
+                              top_k=args.sample_top_k, generator=gen,
+                              paged=getattr(args, "sample_cache", "contiguous") == "paged")
         result["sample"] = toks[0].tolist()
         print(f"Sample: {result['sample']}", flush=True)
     metrics.close()

@@ -1992,6 +1992,100 @@ std::vector<int64_t> attn_extend(Tensor qkv, Tensor k_cache, Tensor v_cache, Ten
   return geo;
 }
 
+// ----------------------------------------------------------------------------- paged KV cache (attn_paged.hip)
+// The checks the paged append and the paged decode attention share: qkv [B, Tn, (heads + 2 kv_heads) * 64] bf16,
+// pools [n_pages, kv_heads, 64, 64] bf16 contiguous, block_table int32 [B, max_pages] and lens int32 [B]
+// contiguous, all on the op's device.
+struct PagedDims {
+  int B, Tn, H, Hkv, n_pages, max_pages;
+};
+PagedDims paged_dims(const Op& op, const Tensor& qkv, const Tensor& k_pool, const Tensor& v_pool,
+                     const Tensor& block_table, const Tensor& lens, int64_t heads, int64_t kv_heads) {
+  TORCH_CHECK(qkv.scalar_type() == at::kBFloat16, op.name, ": qkv must be bf16, got ", qkv.scalar_type());
+  TORCH_CHECK(qkv.dim() == 3 && qkv.is_contiguous() && aligned16(qkv), op.name,
+              ": qkv must be a contiguous, 16-byte aligned [B, Tn, (heads + 2 * kv_heads) * 64] tensor");
+  TORCH_CHECK(heads > 0 && kv_heads > 0 && heads % kv_heads == 0, op.name, ": heads = ", heads,
+              " is not a positive multiple of kv_heads = ", kv_heads);
+  TORCH_CHECK(qkv.size(2) == (heads + 2 * kv_heads) * 64, op.name, ": head dim must be 64: last dim ", qkv.size(2),
+              " is not (heads + 2 * kv_heads) * 64 with heads = ", heads, ", kv_heads = ", kv_heads);
+  for (const Tensor* c : {&k_pool, &v_pool}) {
+    TORCH_CHECK(c->defined() && c->device() == op.dev && c->scalar_type() == at::kBFloat16, op.name,
+                ": the pools must be bf16 tensors on ", op.dev);
+    TORCH_CHECK(c->dim() == 4 && c->size(0) > 0 && c->size(1) == kv_heads && c->size(2) == 64 && c->size(3) == 64,
+                op.name, ": the pools must be [n_pages, kv_heads, 64, 64] (pages of 64 keys, head dim 64) with kv_heads = ",
+                kv_heads, ", got ", c->sizes());
+    TORCH_CHECK(c->is_contiguous() && aligned16(*c), op.name, ": the pools must be contiguous and 16-byte aligned");
+  }
+  TORCH_CHECK(k_pool.sizes() == v_pool.sizes(), op.name, ": k_pool and v_pool must have equal sizes");
+  TORCH_CHECK(k_pool.size(0) <= 0x7fffffffLL, op.name, ": too many pages");
+  TORCH_CHECK(block_table.defined() && block_table.device() == op.dev && block_table.scalar_type() == at::kInt &&
+                  block_table.is_contiguous() && block_table.dim() == 2 && block_table.size(0) == qkv.size(0) &&
+                  block_table.size(1) > 0 && block_table.size(1) <= (1 << 23),
+              op.name, ": block_table must be a contiguous int32 [B, max_pages] tensor on ", op.dev);
+  TORCH_CHECK(lens.defined() && lens.device() == op.dev && lens.scalar_type() == at::kInt && lens.is_contiguous() &&
+                  lens.dim() == 1 && lens.size(0) == qkv.size(0),
+              op.name, ": lens must be a contiguous int32 [B] tensor on ", op.dev);
+  return {(int)qkv.size(0), (int)qkv.size(1), (int)heads, (int)kv_heads, (int)k_pool.size(0), (int)block_table.size(1)};
+}
+
+// rope_kv_append on a paged cache: row (b, t) goes to page block_table[b, p >> 6], row p & 63, p = lens[b] + t
+// (a position outside the table or a page id outside the pool writes nothing to the pools).
+void rope_kv_append_paged(Tensor qkv, Tensor cos, Tensor sin, int64_t heads, int64_t kv_heads, Tensor k_pool,
+                          Tensor v_pool, Tensor block_table, Tensor lens) {
+  const Op op("rope_kv_append_paged", qkv);
+  const PagedDims d = paged_dims(op, qkv, k_pool, v_pool, block_table, lens, heads, kv_heads);
+  TORCH_CHECK(cos.dim() == 2 && cos.size(1) == 32 && sin.sizes() == cos.sizes(),
+              "rope_kv_append_paged: cos and sin must be [T_max, 32] tables");
+  const int64_t Tmax = cos.size(0);
+  const float* cp = f32_ptr(op, "cos", cos, Tmax * 32);
+  const float* sp = f32_ptr(op, "sin", sin, Tmax * 32);
+  TORCH_CHECK(Tmax > 0 && Tmax <= 0x7fffffffLL && aligned16(cos) && aligned16(sin),
+              "rope_kv_append_paged: cos / sin must be 16-byte aligned");
+  int rc = pdt_rope_kv_append_paged(bf16_out(qkv), cp, sp, bf16_out(k_pool), bf16_out(v_pool),
+                                    block_table.data_ptr<int>(), lens.data_ptr<int>(), d.B, d.Tn, d.H, d.Hkv,
+                                    d.n_pages, d.max_pages, (int)Tmax, stream());
+  TORCH_CHECK(rc == 0, "pdt_rope_kv_append_paged failed: ", rc);
+}
+
+// attn_decode on a paged cache; the arguments of attn_decode with the pools and the table for the caches.
+// Returns (S, C) = attn_decode_geo(B, kv_heads, 64 * max_pages, splits, heads / kv_heads), the geometry that ran.
+std::vector<int64_t> attn_decode_paged(Tensor qkv, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor lens,
+                                       int64_t heads, int64_t kv_heads, double scale, int64_t splits, Tensor out,
+                                       c10::optional<Tensor> o_part, c10::optional<Tensor> ml_part,
+                                       c10::optional<Tensor> lse) {
+  const Op op("attn_decode_paged", qkv);
+  const PagedDims d = paged_dims(op, qkv, k_pool, v_pool, block_table, lens, heads, kv_heads);
+  TORCH_CHECK(d.Tn == 1, "attn_decode_paged: one new token per sequence, got Tn = ", d.Tn);
+  TORCH_CHECK(scale > 0 && splits >= 0, "attn_decode_paged: scale must be positive and splits >= 0");
+  TORCH_CHECK(out.defined() && out.device() == op.dev && out.scalar_type() == at::kBFloat16 && out.is_contiguous() &&
+                  out.numel() == (int64_t)d.B * d.H * 64 && aligned16(out),
+              "attn_decode_paged: out must be a contiguous bf16 [B, 1, heads * 64] tensor on ", op.dev);
+  const std::vector<int64_t> geo = attn_decode_geo(d.B, d.Hkv, (int64_t)d.max_pages * 64, splits, d.H / d.Hkv);
+  const int64_t S = geo[0], rows = (int64_t)d.B * d.H;
+  float* lp = opt_f32_ptr(op, "lse", lse, rows);
+  float *op_ptr = nullptr, *ml_ptr = nullptr;
+  if (S > 1) {
+    TORCH_CHECK(has(o_part) && has(ml_part), "attn_decode_paged: S = ", S, " splits need the o_part / ml_part scratch");
+    for (const Tensor* t : {&*o_part, &*ml_part})
+      TORCH_CHECK(t->device() == op.dev && t->scalar_type() == at::kFloat && t->is_contiguous() && aligned16(*t),
+                  "attn_decode_paged: the scratch must be contiguous, 16-byte aligned fp32 on ", op.dev);
+    TORCH_CHECK(o_part->numel() >= rows * S * 64 && ml_part->numel() >= rows * S * 2,
+                "attn_decode_paged: scratch too small for S = ", S, ": o_part ", o_part->numel(), " < ", rows * S * 64,
+                " or ml_part ", ml_part->numel(), " < ", rows * S * 2);
+    op_ptr = o_part->data_ptr<float>();
+    ml_ptr = ml_part->data_ptr<float>();
+  }
+  int rc = pdt_attn_decode_paged(bf16_ptr(qkv), qkv.stride(0), bf16_ptr(k_pool), bf16_ptr(v_pool),
+                                 block_table.data_ptr<int>(), lens.data_ptr<int>(), op_ptr, ml_ptr, bf16_out(out), lp,
+                                 d.B, d.H, d.Hkv, d.n_pages, d.max_pages, (int)S, (int)geo[1], (float)scale, stream());
+  TORCH_CHECK(rc == 0, "pdt_attn_decode_paged failed: ", rc);
+  if (S > 1) {
+    rc = pdt_attn_decode_combine(op_ptr, ml_ptr, bf16_out(out), lp, d.B, d.H, (int)S, stream());
+    TORCH_CHECK(rc == 0, "pdt_attn_decode_combine failed: ", rc);
+  }
+  return geo;
+}
+
 // y = silu(gu[:, :F]) * gu[:, F:] for gu [..., 2F] (swiglu.hip)
 Tensor swiglu_fwd(Tensor gu, c10::optional<Tensor> y_out) {
   const Op op("swiglu_fwd", gu);
@@ -3020,6 +3114,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_extend", &attn_extend, py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"),
         py::arg("heads"), py::arg("kv_heads"), py::arg("scale"), py::arg("splits"), py::arg("out"),
         py::arg("o_part") = py::none(), py::arg("ml_part") = py::none(), py::arg("lse") = py::none());
+  m.def("rope_kv_append_paged", &rope_kv_append_paged, py::arg("qkv"), py::arg("cos"), py::arg("sin"),
+        py::arg("heads"), py::arg("kv_heads"), py::arg("k_pool"), py::arg("v_pool"), py::arg("block_table"),
+        py::arg("lens"));
+  m.def("attn_decode_paged", &attn_decode_paged, py::arg("qkv"), py::arg("k_pool"), py::arg("v_pool"),
+        py::arg("block_table"), py::arg("lens"), py::arg("heads"), py::arg("kv_heads"), py::arg("scale"),
+        py::arg("splits"), py::arg("out"), py::arg("o_part") = py::none(), py::arg("ml_part") = py::none(),
+        py::arg("lse") = py::none());
   m.def("swiglu_fwd", &swiglu_fwd, py::arg("gu"), py::arg("y_out") = py::none());
   m.def("gemm_skinny_geo", &gemm_skinny_geo, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("mode") = 0,
         py::arg("splits") = 0);

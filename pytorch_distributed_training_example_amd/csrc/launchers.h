@@ -64,6 +64,17 @@ int pdt_attn_extend(const uint16_t* qkv, int64_t q_sb, int64_t q_st, const uint1
                     const int* lens, float* o_part, float* ml_part, uint16_t* out, float* lse, int B, int Tn, int H,
                     int Hkv, int capacity, int S, int C, int NB, int NT, float scale, hipStream_t s);
 
+// kernels/attn_paged.hip: the same on a paged cache. k_pool, v_pool [n_pages, Hkv, 64, 64] bf16 (pages of 64
+// keys); block_table int32 [B, max_pages] (page of positions [64 j, 64 j + 64) of slot b, or -1) and lens on
+// the device. (S, C) is pdt_attn_decode_geo's for a capacity of 64 max_pages; pdt_attn_decode_combine merges.
+int pdt_rope_kv_append_paged(uint16_t* qkv, const float* cos, const float* sin, uint16_t* k_pool, uint16_t* v_pool,
+                             const int* block_table, const int* lens, int B, int Tn, int H, int Hkv, int n_pages,
+                             int max_pages, int Tmax, hipStream_t s);
+int pdt_attn_decode_paged(const uint16_t* qkv, int64_t q_sb, const uint16_t* k_pool, const uint16_t* v_pool,
+                          const int* block_table, const int* lens, float* o_part, float* ml_part, uint16_t* out,
+                          float* lse, int B, int H, int Hkv, int n_pages, int max_pages, int S, int C, float scale,
+                          hipStream_t s);
+
 // kernels/batchnorm.hip
 int64_t pdt_bn_workspace_floats(int64_t M, int C);
 void pdt_bn_tiles_fused(int on);

@@ -36,13 +36,13 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..config import SW
-from ..ops.attention import attention_decode, attention_extend, attention_qkv
+from ..ops.attention import attention_decode, attention_decode_paged, attention_extend, attention_qkv
 from ..ops.cross_entropy import cross_entropy
 from ..ops.fp8 import Fp8Act, add_rms_norm_fp8, fp8_input_slot, fp8_linear, fp8_ok, fp8_swiglu_mlp, rms_fp8_ok
-from ..ops.kv_cache import KVCache
+from ..ops.kv_cache import PAGE, KVCache, PagedKVCache
 from ..ops.linear import SKINNY_MAX_ROWS, linear, linear_skinny, linear_skinny_w8, quantize_rows_e4m3
 from ..ops.rmsnorm import RMSNorm, add_rms_norm
-from ..ops.rope import RotaryTable, rope_append_, rope_qkv_
+from ..ops.rope import RotaryTable, rope_append_, rope_append_paged_, rope_qkv_
 from ..ops.swiglu import swiglu
 from .transformer import init_weights
 
@@ -132,6 +132,8 @@ class LlamaAttention(nn.Module):
         (Tn == 1) the split-KV kernel on the cache, and ``Llama.extend`` (which sets ``cache.extending`` around
         its forward) with Tn > 1 the multi-token append kernel, whatever the cache holds. ``cache.lens`` is
         advanced by the caller after the last layer."""
+        if isinstance(cache, PagedKVCache):
+            return self._forward_paged(x, rope, cache, layer)
         Tn = x.shape[1]
         if Tn > 1 and cache.bound > 0 and not cache.extending:
             raise ValueError(f"{Tn} new tokens onto a cache that may hold {cache.bound} positions: chunked prefill "
@@ -148,6 +150,28 @@ class LlamaAttention(nn.Module):
         else:
             y = attention_decode(qkv, cache.k[layer], cache.v[layer], cache.lens, self.heads, self.kv_heads,
                                  cache=cache)
+        return _linear(y, self.c_proj)
+
+    def _forward_paged(self, x, rope, cache: PagedKVCache, layer: int):
+        """``_forward_cached`` on a paged cache: the paged append, then the causal flash forward on the new rows
+        (Tn > 1: a prefill of empty slots, the ones ``cache.select`` named) or the paged split-KV kernel
+        (Tn == 1, every slot). Tn > 1 onto a slot that holds something is the multi-token append, which has no
+        paged kernel yet."""
+        Tn = x.shape[1]
+        table, lens, slots = cache.view()
+        if Tn > 1 and any(cache.bounds[s] > 0 for s in (range(cache.slots) if slots is None else slots)):
+            raise NotImplementedError(f"{Tn} new tokens onto paged slots that may hold something: the multi-token "
+                                      "append (extend) has no paged kernel yet; a paged cache takes a prefill of "
+                                      "empty slots and one-token decode steps")
+        cache.require(Tn, rope.cos.shape[0], slots)
+        qkv = _linear(x, self.c_attn)
+        qkv = rope_append_paged_(qkv, rope.cos, rope.sin, self.heads, self.kv_heads, cache.k[layer], cache.v[layer],
+                                 table, lens)
+        if Tn > 1:
+            y = attention_qkv(qkv, self.heads, causal=True, kv_heads=self.kv_heads)
+        else:
+            y = attention_decode_paged(qkv, cache.k[layer], cache.v[layer], table, lens, self.heads, self.kv_heads,
+                                       cache=cache)
         return _linear(y, self.c_proj)
 
 
@@ -280,6 +304,46 @@ class Llama(nn.Module):
         w = self.lm_head.weight
         return KVCache(self.cfg.n_layer, batch, self.cfg.kv_heads, capacity or self.cfg.block_size, w.device, w.dtype)
 
+    def new_paged_cache(self, slots: int, n_pages: int, max_pages_per_seq: int | None = None) -> PagedKVCache:
+        """A paged KV cache of ``slots`` sequence slots on a pool of ``n_pages`` pages of 64 positions per layer;
+        a slot may hold up to ``max_pages_per_seq`` pages (default: what ``block_size`` positions need)."""
+        w = self.lm_head.weight
+        cache = PagedKVCache(self.cfg.n_layer, slots, self.cfg.kv_heads, n_pages,
+                             max_pages_per_seq or -(-self.cfg.block_size // PAGE), w.device, w.dtype)
+        cache.table_len = self.cfg.block_size
+        return cache
+
+    def _prefill_paged(self, idx: torch.Tensor, cache: PagedKVCache, prompt_lens, slots) -> torch.Tensor:
+        """``prefill`` of the admitted, empty slots ``slots`` (default: all of them) of a paged cache, whose pages
+        ``cache.reserve(T0, slots)`` has handed out; the other slots are not touched."""
+        b, T0 = idx.shape
+        if slots is None:  # every slot runs: refuse before the forward, not after it has written the others' pages
+            idle = [s for s in range(cache.slots) if not cache.is_active(s)]
+            if idle:
+                raise ValueError(f"prefill: slots {idle} of the paged cache are not admitted; admit() every slot, or "
+                                 "name the ones to prefill with slots=")
+        slots = list(range(cache.slots)) if slots is None else [int(s) for s in slots]
+        if (cache.n_layer, cache.kv_heads) != (self.cfg.n_layer, self.cfg.kv_heads) or len(slots) != b:
+            raise ValueError(f"paged cache for {cache.n_layer} layers x {cache.kv_heads} K/V heads does not fit this "
+                             f"model ({self.cfg.n_layer} x {self.cfg.kv_heads}), or {len(slots)} slots for {b} prompts")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise RuntimeError("the KV-cache path is inference only: call it under torch.no_grad()")
+        if prompt_lens is not None:
+            prompt_lens = _lens_arg(prompt_lens, b, 1, T0, idx.device, "prompt_lens")
+        cache.select(slots)  # refuses slots that are not distinct and admitted
+        try:
+            x = F.embedding(idx, self.transformer.wte.weight)
+            x = run_llama_blocks(self.transformer.h, x, self.transformer.ln_f, self.rope, cache)
+        finally:
+            cache.select(None)
+        if prompt_lens is None:
+            cache.set_lens(torch.full((b,), T0, dtype=torch.int32), slots=slots)
+            last = x[:, -1]
+        else:
+            cache.set_lens(prompt_lens, bound=T0, slots=slots)
+            last = x.gather(1, (prompt_lens.long() - 1)[:, None, None].expand(b, 1, x.shape[-1]))[:, 0]
+        return self._head(last)
+
     def _check_cache(self, cache: KVCache, batch: int) -> None:
         if (cache.n_layer, cache.kv_heads) != (self.cfg.n_layer, self.cfg.kv_heads) or cache.batch != batch:
             raise ValueError(f"cache for {cache.n_layer} layers x {cache.kv_heads} K/V heads x batch {cache.batch} "
@@ -287,13 +351,20 @@ class Llama(nn.Module):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise RuntimeError("the KV-cache path is inference only: call it under torch.no_grad()")
 
-    def prefill(self, idx: torch.Tensor, cache: KVCache, prompt_lens=None) -> torch.Tensor:
+    def prefill(self, idx: torch.Tensor, cache: KVCache, prompt_lens=None, slots=None) -> torch.Tensor:
         """Run the prompts ``idx`` [B, T0] into an empty ``cache``; returns the logits [B, V] of every
         sequence's last prompt position (the LM head runs on those B rows only). Ragged prompts are
         right-padded and ``prompt_lens`` (B lengths in [1, T0]: a sequence, a CPU tensor, or a device tensor,
         which is clamped to that range rather than read) gives their lengths: all T0 rows are appended,
         then ``cache.lens = prompt_lens``; causality keeps the padding out of the real positions and the next
-        append overwrites it."""
+        append overwrites it.
+
+        With a ``PagedKVCache`` and ``slots`` (B distinct admitted, empty slots, their pages reserved) only
+        those sequences run and the other slots are not touched: this is how a sequence joins a running batch."""
+        if isinstance(cache, PagedKVCache):
+            return self._prefill_paged(idx, cache, prompt_lens, slots)
+        if slots is not None:
+            raise ValueError("prefill: slots names slots of a PagedKVCache; a KVCache's batch is fixed")
         B, T0 = idx.shape
         self._check_cache(cache, B)
         x = F.embedding(idx, self.transformer.wte.weight)
@@ -317,7 +388,9 @@ class Llama(nn.Module):
     def decode_step(self, tok: torch.Tensor, cache: KVCache) -> torch.Tensor:
         """One token per sequence: ``tok`` [B] sits at position ``cache.lens[b]``; returns the logits [B, V]
         of the next one and advances ``cache.lens`` on the device after the last layer. Nothing here reads
-        the device, so the step can be captured with ``torch.cuda.graph`` and replayed."""
+        the device, so the step can be captured with ``torch.cuda.graph`` and replayed. On a ``PagedKVCache``
+        ``tok`` is [slots] and every slot runs, so the shape is fixed: an inactive slot's row is computed and
+        ignored (finite logits, its ``lens`` does not move); ``cache.reserve(1)`` comes before the step."""
         self._check_cache(cache, tok.shape[0])
         x = F.embedding(tok[:, None], self.transformer.wte.weight)
         x = run_llama_blocks(self.transformer.h, x, self.transformer.ln_f, self.rope, cache)
@@ -379,7 +452,7 @@ class Llama(nn.Module):
     @torch.no_grad()
     def generate(self, idx: torch.Tensor, max_new_tokens: int, temperature: float = 0.0, top_k: int | None = None,
                  eos_token: int | None = None, generator: torch.Generator | None = None, prompt_lens=None,
-                 return_logits: bool = False, prefill_chunk: int | None = None):
+                 return_logits: bool = False, prefill_chunk: int | None = None, paged: bool = False):
         """Sample ``max_new_tokens`` tokens after the prompts ``idx`` [B, T0] (right-padded when
         ``prompt_lens`` is given); returns them as [B, max_new_tokens] on the device, with ``return_logits``
         also the logits [B, max_new_tokens, V] each was drawn from. Greedy at ``temperature`` 0, otherwise
@@ -387,17 +460,29 @@ class Llama(nn.Module):
         ``generator``. With ``eos_token`` everything after a sequence's first EOS is EOS (a device-side mask:
         no step reads a token on the host). With ``prefill_chunk`` the prompt runs in slices of that many
         positions (``prefill`` of the first, ``extend`` of the rest), which bounds the activation memory of a
-        long prompt by the slice. Runs in ``eval()`` and restores the mode."""
+        long prompt by the slice. With ``paged`` the same loop runs on a ``PagedKVCache`` sized for the batch,
+        which reserves pages before the prefill and before every step (no ``prefill_chunk`` there: a paged
+        cache has no multi-token append yet). Runs in ``eval()`` and restores the mode."""
         B, T0 = idx.shape
         if max_new_tokens < 1:
             raise ValueError(f"max_new_tokens must be positive, got {max_new_tokens}")
+        if paged and prefill_chunk is not None:
+            raise NotImplementedError("generate: prefill_chunk needs the multi-token append, which has no paged "
+                                      "kernel yet")
         if T0 + max_new_tokens > self.cfg.block_size:
             raise ValueError(f"prompt of {T0} + {max_new_tokens} new tokens exceeds block_size {self.cfg.block_size} "
                              "(the RoPE table)")
         was_training = self.training
         self.eval()
         try:
-            cache = self.new_cache(B, T0 + max_new_tokens)
+            if paged:
+                per_seq = -(-(T0 + max_new_tokens) // PAGE)
+                cache = self.new_paged_cache(B, B * per_seq, per_seq)
+                for s in range(B):
+                    cache.admit(s)
+                cache.reserve(T0)
+            else:
+                cache = self.new_cache(B, T0 + max_new_tokens)
             if prefill_chunk is None:
                 logits = self.prefill(idx, cache, prompt_lens)
             else:
@@ -413,6 +498,8 @@ class Llama(nn.Module):
                 if return_logits:
                     all_logits.append(logits)
                 if i + 1 < max_new_tokens:
+                    if paged:
+                        cache.reserve(1)
                     logits = self.decode_step(tok, cache)
         finally:
             self.train(was_training)

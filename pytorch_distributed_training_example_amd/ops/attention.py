@@ -25,6 +25,7 @@ import torch
 import torch.nn.functional as F
 
 from ._native import native, use_native
+from .kv_cache import PAGE
 
 KERNEL_HEAD_DIMS = (64,)
 
@@ -260,6 +261,58 @@ def attention_decode(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
         DECODE_STATS["geo"] = (int(geo[0]), int(geo[1]))
         return (out, lse) if return_lse else out
     out, lse = _decode_reference(qkv, k_cache, v_cache, lens, heads, kv_heads, scale)
+    return (out, lse) if return_lse else out
+
+
+PAGED_STATS = {"native_calls": 0, "geo": None}  # launches of the paged decode kernel and the last (S, C) it ran with
+
+
+def attention_decode_paged(qkv: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor,
+                           lens: torch.Tensor, heads: int, kv_heads: int | None = None, scale: float | None = None,
+                           splits: int | None = None, cache=None, return_lse: bool = False):
+    """``attention_decode`` on a paged cache: ``k_pool`` / ``v_pool`` [n_pages, Hkv, 64, 64] hold pages of 64
+    positions, ``block_table`` (int32 [B, max_pages] on qkv's device) names the page of positions
+    [64 j, 64 j + 64) of slot b or -1, ``lens`` int32 [B] is read on the device: slot b attends to its keys
+    0 .. lens[b] (``rope_append_paged_`` has written the new token at ``lens[b]``), whatever else its pages or
+    the pool hold. Returns [B, 1, H·64] (and the LSE [B, H] with ``return_lse``). Inference only.
+
+    bf16 GPU tensors run the paged split-KV kernel (csrc/kernels/attn_paged.hip) with the (S, C) of
+    ``attention_decode_geo`` for a capacity of 64·max_pages; ``splits`` and ``cache`` (a ``PagedKVCache``) as in
+    ``attention_decode``. CPU, fp32 and ``PDT_DISABLE_NATIVE=1`` gather every slot's pages into a contiguous
+    cache and take the PyTorch reference."""
+    kv_heads = heads if kv_heads is None else kv_heads
+    if kv_heads <= 0 or heads % kv_heads != 0:
+        raise ValueError(f"attention_decode_paged: heads = {heads} is not a positive multiple of kv_heads = {kv_heads}")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (qkv, k_pool, v_pool)):
+        raise RuntimeError("attention_decode_paged: inference only (run it under torch.no_grad())")
+    if qkv.dim() != 3 or qkv.shape[1] != 1 or qkv.shape[2] % (heads + 2 * kv_heads) != 0:
+        raise ValueError(f"attention_decode_paged: qkv {tuple(qkv.shape)} is not [B, 1, (heads + 2·kv_heads)·Dh]")
+    dh = qkv.shape[2] // (heads + 2 * kv_heads)
+    scale = scale if scale is not None else 1.0 / math.sqrt(dh)
+    if use_native(qkv) and qkv.dtype == torch.bfloat16:  # head dim 64 and the layouts: the binding's checks
+        B = qkv.shape[0]
+        out = torch.empty(B, 1, heads * dh, device=qkv.device, dtype=qkv.dtype)
+        lse = torch.empty(B, heads, device=qkv.device, dtype=torch.float32) if return_lse else None
+        o_part = ml_part = None
+        if block_table.dim() == 2 and block_table.shape[1] > 0 and dh == 64:
+            S, _ = attention_decode_geo(B, kv_heads, PAGE * block_table.shape[1], splits, heads // kv_heads)
+            if S > 1:
+                if cache is not None:
+                    o_part, ml_part = cache.scratch(heads, S)
+                else:
+                    o_part = torch.empty(B, heads, S, 64, device=qkv.device, dtype=torch.float32)
+                    ml_part = torch.empty(B, heads, S, 2, device=qkv.device, dtype=torch.float32)
+        geo = native().attn_decode_paged(qkv, k_pool, v_pool, block_table, lens, heads, kv_heads, scale,
+                                         int(splits or 0), out, o_part, ml_part, lse)
+        PAGED_STATS["native_calls"] += 1
+        PAGED_STATS["geo"] = (int(geo[0]), int(geo[1]))
+        return (out, lse) if return_lse else out
+    from .rope import gather_pages
+    if k_pool.dim() != 4 or k_pool.shape != v_pool.shape or block_table.dim() != 2 or block_table.shape[0] != qkv.shape[0]:
+        raise ValueError(f"attention_decode_paged: pools {tuple(k_pool.shape)}, {tuple(v_pool.shape)} are not "
+                         f"[n_pages, kv_heads, 64, Dh] or the table {tuple(block_table.shape)} is not [B, max_pages]")
+    out, lse = _decode_reference(qkv, gather_pages(k_pool, block_table), gather_pages(v_pool, block_table),
+                                 lens, heads, kv_heads, scale)
     return (out, lse) if return_lse else out
 
 

@@ -90,3 +90,211 @@ class KVCache:
                 torch.empty(*lead, heads, S, HEAD_DIM, device=self.device, dtype=torch.float32),
                 torch.empty(*lead, heads, S, 2, device=self.device, dtype=torch.float32))
         return self._scratch[key]
+
+
+PAGE = 64
+
+
+class PagedKVCache:
+    """A KV cache in pages of 64 positions (csrc/kernels/attn_paged.hip reads and writes it).
+
+    Per layer ``k[l]`` and ``v[l]`` are pools [n_pages, Hkv, 64, 64] shared by ``slots`` sequence slots;
+    ``block_table`` (int32 [slots, max_pages_per_seq], on the device, one for all layers) names the page of
+    positions [64 j, 64 j + 64) of a slot, or -1. ``lens`` and ``active`` are int32 [slots] on the device. A slot
+    holds only the pages its sequence has reached, a finished sequence gives them back (``free``) and a new one
+    joins (``admit``, then ``Llama.prefill(..., slots=[s])``) while the others decode.
+
+    The allocator lives on the host: a mirror of the table, a free list and, per slot, an upper bound of
+    ``lens`` kept without a device read, as ``KVCache.bound`` is. ``reserve(n)`` gives every active slot the
+    pages ``bound + n`` positions need, before the step that writes them, and uploads the table only when an
+    entry changed (in steady decoding once per 64 steps and slot); it raises before it changes or launches
+    anything when the pool, ``max_pages_per_seq`` or the rotary table (``table_len``) cannot cover the step.
+    Nothing on the step path reads the device, so a captured decode step replays with ``reserve`` called
+    between the replays. Freed pages are not cleared: the kernels never read a row at or past ``lens``."""
+
+    def __init__(self, n_layer: int, slots: int, kv_heads: int, n_pages: int, max_pages_per_seq: int, device,
+                 dtype=torch.bfloat16):
+        if min(n_layer, slots, kv_heads, n_pages, max_pages_per_seq) <= 0:
+            raise ValueError("PagedKVCache: n_layer, slots, kv_heads, n_pages and max_pages_per_seq must be positive, "
+                             f"got {(n_layer, slots, kv_heads, n_pages, max_pages_per_seq)}")
+        self.n_layer, self.slots, self.kv_heads = n_layer, slots, kv_heads
+        self.n_pages, self.max_pages = n_pages, max_pages_per_seq
+        self.device, self.dtype = torch.device(device), dtype
+        shape = (n_pages, kv_heads, PAGE, HEAD_DIM)
+        self.k = [torch.zeros(shape, device=self.device, dtype=dtype) for _ in range(n_layer)]
+        self.v = [torch.zeros(shape, device=self.device, dtype=dtype) for _ in range(n_layer)]
+        self.block_table = torch.full((slots, max_pages_per_seq), -1, device=self.device, dtype=torch.int32)
+        self.lens = torch.zeros(slots, device=self.device, dtype=torch.int32)
+        self.active = torch.zeros(slots, device=self.device, dtype=torch.int32)
+        self.table_len: int | None = None  # positions of the rotary table, when the owner has one
+        self._table = torch.full((slots, max_pages_per_seq), -1, dtype=torch.int32)  # host mirror
+        self._free = list(range(n_pages - 1, -1, -1))  # popped from the end: page 0 first
+        self._held = [0] * slots  # pages a slot holds: the first _held[s] entries of its table row
+        self._bound = [0] * slots
+        self._active = [False] * slots
+        self._scratch: dict = {}
+        self._view = None  # (block_table rows, lens) of the slots a prefill runs on
+
+    # ------------------------------------------------------------------ what the contiguous cache also answers
+    @property
+    def batch(self) -> int:
+        return self.slots
+
+    @property
+    def capacity(self) -> int:
+        return self.max_pages * PAGE
+
+    @property
+    def bound(self) -> int:
+        """An upper bound of every entry of ``lens``, known without reading the device."""
+        return max(self._bound)
+
+    @property
+    def bounds(self) -> list:
+        return list(self._bound)
+
+    @property
+    def free_pages(self) -> int:
+        return len(self._free)
+
+    def pages_of(self, slot: int) -> list:
+        return self._table[slot, :self._held[slot]].tolist()
+
+    def is_active(self, slot: int) -> bool:
+        return self._active[slot]
+
+    # ------------------------------------------------------------------ slots
+    def _slot(self, slot: int) -> int:
+        if not 0 <= int(slot) < self.slots:
+            raise ValueError(f"PagedKVCache: slot {slot} outside [0, {self.slots})")
+        return int(slot)
+
+    def admit(self, slot: int) -> None:
+        """Open ``slot`` for a new sequence: active, empty, no pages yet (``reserve`` hands them out)."""
+        slot = self._slot(slot)
+        if self._active[slot]:
+            raise ValueError(f"PagedKVCache.admit: slot {slot} is in use (free it first)")
+        self._active[slot] = True
+        self._bound[slot] = 0
+        self.active[slot] = 1
+        self.lens[slot] = 0
+
+    def free(self, slot: int) -> None:
+        """Return the slot's pages to the free list (uncleared), its table row to -1, its lens and active to 0."""
+        slot = self._slot(slot)
+        held = self._held[slot]
+        self._free.extend(reversed(self._table[slot, :held].tolist()))
+        self._table[slot] = -1
+        self._held[slot], self._bound[slot], self._active[slot] = 0, 0, False
+        self.active[slot] = 0
+        self.lens[slot] = 0
+        if held:
+            self.block_table.copy_(self._table)
+
+    def _named(self, slots) -> list:
+        if slots is None:
+            return [s for s in range(self.slots) if self._active[s]]
+        named = [self._slot(s) for s in slots]
+        if len(set(named)) != len(named) or not all(self._active[s] for s in named):
+            raise ValueError(f"PagedKVCache: slots {list(slots)} must be distinct admitted slots")
+        return named
+
+    def reserve(self, n: int = 1, slots=None) -> None:
+        """Before a step of ``n`` tokens: every named slot (default: every active one) gets the pages that
+        ``ceil((bound + n) / 64)`` needs. Raises, with nothing changed, when the free list, ``max_pages_per_seq``
+        or the rotary table cannot cover it."""
+        named = self._named(slots)
+        need = {}
+        for s in named:
+            end = self._bound[s] + n
+            if self.table_len is not None and end > self.table_len:
+                raise ValueError(f"PagedKVCache: {n} more positions on top of up to {self._bound[s]} in slot {s} exceed "
+                                 f"the rotary table's {self.table_len} positions")
+            pages = -(-end // PAGE)
+            if pages > self.max_pages:
+                raise ValueError(f"PagedKVCache: {n} more positions on top of up to {self._bound[s]} in slot {s} need "
+                                 f"{pages} pages, more than max_pages_per_seq = {self.max_pages}")
+            need[s] = max(pages - self._held[s], 0)
+        total = sum(need.values())
+        if total > len(self._free):
+            raise ValueError(f"PagedKVCache: the step needs {total} more pages and the pool has {len(self._free)} free "
+                             f"of {self.n_pages}")
+        if total == 0:
+            return
+        for s, k in need.items():
+            for _ in range(k):
+                self._table[s, self._held[s]] = self._free.pop()
+                self._held[s] += 1
+        self.block_table.copy_(self._table)
+
+    def require(self, n: int, table_len: int | None = None, slots=None) -> None:
+        """Refuse ``n`` more positions that the named slots' pages (``reserve`` was not called) or the rotary
+        table might not hold."""
+        for s in self._named(slots):
+            end = self._bound[s] + n
+            if end > self._held[s] * PAGE:
+                raise ValueError(f"PagedKVCache: {n} more positions on top of up to {self._bound[s]} in slot {s} exceed "
+                                 f"its {self._held[s]} pages: call reserve({n}) before the step")
+            if table_len is not None and end > table_len:
+                raise ValueError(f"PagedKVCache: {n} more positions on top of up to {self._bound[s]} in slot {s} exceed "
+                                 f"the rotary table's {table_len} positions")
+
+    # ------------------------------------------------------------------ lens
+    def advance(self, n: int = 1) -> None:
+        """``lens += n * active`` on the device; the bounds of the active slots follow."""
+        self.lens.add_(self.active, alpha=n)
+        for s in range(self.slots):
+            if self._active[s]:
+                self._bound[s] += n
+
+    def set_lens(self, lens, bound=None, slots=None) -> None:
+        """``lens[slots] = lens`` (default: all slots). ``KVCache.set_lens``'s contract per slot: a sequence or a
+        CPU tensor gives the bounds itself; a device tensor is not read: pass ``bound`` (an int for every named
+        slot, or one per slot, which the caller vouches for), or the present bounds are kept, which the new
+        values must not exceed."""
+        named = list(range(self.slots)) if slots is None else [self._slot(s) for s in slots]
+        if not isinstance(lens, torch.Tensor):
+            lens = torch.as_tensor(lens, dtype=torch.int32)
+        if lens.shape != (len(named),):
+            raise ValueError(f"PagedKVCache.set_lens: expected {len(named)} lengths, got shape {tuple(lens.shape)}")
+        if bound is not None and not isinstance(bound, (list, tuple)):
+            bound = [int(bound)] * len(named)
+        if lens.device.type == "cpu":
+            vals = [int(x) for x in lens.tolist()]
+            if bound is None:
+                bound = vals
+            if min(vals) < 0 or any(v > b for v, b in zip(vals, bound)):
+                raise ValueError(f"PagedKVCache.set_lens: lengths {vals} are negative or exceed the stated bounds {bound}")
+        if bound is not None:
+            if len(bound) != len(named) or any(not 0 <= b <= self._held[s] * PAGE for s, b in zip(named, bound)):
+                raise ValueError(f"PagedKVCache.set_lens: bounds {list(bound)} do not fit the pages the slots hold "
+                                 f"({[self._held[s] for s in named]})")
+            for s, b in zip(named, bound):
+                self._bound[s] = int(b)
+        lens = lens.to(device=self.device, dtype=torch.int32)
+        if slots is None:
+            self.lens.copy_(lens)
+        else:
+            self.lens.index_copy_(0, torch.as_tensor(named, device=self.device), lens)
+
+    # ------------------------------------------------------------------ what a forward runs on
+    def select(self, slots) -> None:
+        """The slots the next forward's rows are (a prefill of newly admitted slots), or None for all of them."""
+        if slots is None:
+            self._view = None
+        else:
+            idx = torch.as_tensor(self._named(slots), device=self.device)
+            self._view = (self.block_table.index_select(0, idx).contiguous(), self.lens.index_select(0, idx), list(slots))
+
+    def view(self):
+        """(block_table rows, lens, slots or None) of the slots the forward runs on."""
+        return self._view if self._view is not None else (self.block_table, self.lens, None)
+
+    def scratch(self, heads: int, S: int):
+        """(o_part [slots, heads, S, 64], ml_part [slots, heads, S, 2]) fp32: allocated on the first request."""
+        key = (heads, S)
+        if key not in self._scratch:
+            self._scratch[key] = (
+                torch.empty(self.slots, heads, S, HEAD_DIM, device=self.device, dtype=torch.float32),
+                torch.empty(self.slots, heads, S, 2, device=self.device, dtype=torch.float32))
+        return self._scratch[key]

@@ -20,6 +20,7 @@ import torch
 from torch import nn
 
 from ._native import native, use_native
+from .kv_cache import PAGE
 
 KERNEL_HEAD_DIM = 64
 
@@ -172,3 +173,57 @@ def rope_append_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, heads:
         raise ValueError(f"rope_append_: caches {tuple(k_cache.shape)}, {tuple(v_cache.shape)} are not "
                          f"[{qkv.shape[0]}, {kv_heads}, capacity, {dh}]")
     return _append_reference_(qkv, cos, sin, heads, kv_heads, k_cache, v_cache, lens)
+
+
+# ----------------------------------------------------------------------------- the same on a paged cache
+APPEND_PAGED_STATS = {"native_calls": 0}  # launches of the paged append kernel
+
+
+def gather_pages(pool: torch.Tensor, block_table: torch.Tensor) -> torch.Tensor:
+    """A slot's pages as a contiguous cache [B, Hkv, 64·max_pages, Dh], for the reference paths: ``pool``
+    [n_pages, Hkv, 64, Dh] read through ``block_table`` [B, max_pages]; an entry outside the pool gives zero
+    rows, as the kernel's resource of zero records does."""
+    B, mp = block_table.shape
+    tbl = block_table.long()
+    ok = (tbl >= 0) & (tbl < pool.shape[0])
+    pages = torch.where(ok[:, :, None, None, None], pool[torch.where(ok, tbl, torch.zeros_like(tbl))],
+                        torch.zeros((), dtype=pool.dtype, device=pool.device))
+    return pages.permute(0, 2, 1, 3, 4).reshape(B, pool.shape[1], mp * PAGE, pool.shape[3])
+
+
+def rope_append_paged_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, heads: int, kv_heads: int | None,
+                       k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor,
+                       lens: torch.Tensor) -> torch.Tensor:
+    """``rope_append_`` on a paged cache: ``k_pool`` / ``v_pool`` [n_pages, kv_heads, 64, Dh] hold pages of 64
+    positions and ``block_table`` (int32 [B, max_pages], on qkv's device) names the page of positions
+    [64 j, 64 j + 64) of slot b, or -1. Row (b, t) at p = lens[b] + t is rotated in place as ``rope_append_``
+    rotates it and stored at row p & 63 of page ``block_table[b, p >> 6]``; a row whose p is outside the table or
+    the rotary table does nothing, one whose page id is outside the pool is rotated and not stored. Returns
+    ``qkv``; ``lens`` is not advanced. Inference only."""
+    kv_heads = heads if kv_heads is None else kv_heads
+    if kv_heads <= 0 or heads % kv_heads != 0:
+        raise ValueError(f"rope_append_paged_: heads = {heads} is not a positive multiple of kv_heads = {kv_heads}")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (qkv, k_pool, v_pool)):
+        raise RuntimeError("rope_append_paged_: inference only (run it under torch.no_grad())")
+    if qkv.dim() != 3 or qkv.shape[-1] % (heads + 2 * kv_heads) != 0 or not qkv.is_contiguous():
+        raise ValueError(f"rope_append_paged_: qkv {tuple(qkv.shape)} is not a contiguous [B, Tn, (heads + "
+                         f"2·kv_heads)·Dh] with heads = {heads}, kv_heads = {kv_heads}")
+    if use_native(qkv) and qkv.dtype == torch.bfloat16:  # head dim 64, layouts, table, lens: the binding's checks
+        native().rope_kv_append_paged(qkv, cos, sin, heads, kv_heads, k_pool, v_pool, block_table, lens)
+        APPEND_PAGED_STATS["native_calls"] += 1
+        return qkv
+    dh = qkv.shape[-1] // (heads + 2 * kv_heads)
+    if k_pool.shape != v_pool.shape or k_pool.dim() != 4 or tuple(k_pool.shape[1:]) != (kv_heads, PAGE, dh) \
+            or block_table.dim() != 2 or block_table.shape[0] != qkv.shape[0]:
+        raise ValueError(f"rope_append_paged_: pools {tuple(k_pool.shape)}, {tuple(v_pool.shape)} are not [n_pages, "
+                         f"{kv_heads}, {PAGE}, {dh}] or the table {tuple(block_table.shape)} is not [{qkv.shape[0]}, "
+                         "max_pages]")
+    # the contiguous reference on the gathered pages, then the named pages written back
+    B, mp = block_table.shape
+    kc, vc = gather_pages(k_pool, block_table), gather_pages(v_pool, block_table)
+    _append_reference_(qkv, cos, sin, heads, kv_heads, kc, vc, lens)
+    tbl = block_table.long()
+    ok = (tbl >= 0) & (tbl < k_pool.shape[0])
+    for pool, c in ((k_pool, kc), (v_pool, vc)):
+        pool[tbl[ok]] = c.view(B, kv_heads, mp, PAGE, dh).permute(0, 2, 1, 3, 4)[ok]
+    return qkv

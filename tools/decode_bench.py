@@ -42,7 +42,12 @@ replayed, weights rotating through 512 MiB of distinct copies, alternating, devi
 each line's rate is over the bytes that candidate must move. Then the generation A/B under PDT_DECODE_GEMM=1:
 the captured step and 128 tokens after a 128-token prompt, bf16 weights against quantize_decode_weights().
 
-    python tools/decode_bench.py [--rounds 7] [--iters 50] [--gen-rounds 3] [--no-generate] [--extend] [--out FILE]
+--paged: the paged decode kernel. The kernel table's shapes and recipe (captured and replayed, rotating caches,
+alternating, device events, median of the rounds): attention_decode_paged with a sequential block table and
+with a seeded shuffled one against attention_decode on the same keys, and whether the three give the same
+bits; then llama_medium's captured decode step on a KVCache and on a PagedKVCache.
+
+    python tools/decode_bench.py [--rounds 7] [--iters 50] [--gen-rounds 3] [--no-generate] [--extend] [--paged] [--out FILE]
 """
 from __future__ import annotations
 
@@ -156,6 +161,110 @@ def bench_kernel(rounds, iters, emit):
                      f"({min(tg) * 1e3:.1f}-{max(tg) * 1e3:.1f})  must move {must / 1e6:6.2f} MB  {must / m / 1e9:6.2f} TB/s")
             emit(f"lens {lens:5d}  max |ours - sdpa| = {err:.3g}")
         del cache, ke, ve
+
+
+def bench_paged(rounds, iters, emit):
+    """--paged: attention_decode_paged under a sequential and a seeded shuffled block table against
+    attention_decode (the contiguous kernel, unchanged) on the shapes of bench_kernel, the same keys in all
+    three, every candidate captured and replayed over rotating caches, and whether the bits agree."""
+    from pytorch_distributed_training_example_amd.ops.attention import (attention_decode, attention_decode_geo,
+                                                                         attention_decode_paged)
+    from pytorch_distributed_training_example_amd.ops.kv_cache import KVCache
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    scale = 1.0 / math.sqrt(DH)
+    MP = CAP // 64
+    perm = torch.randperm(B * MP, generator=torch.Generator().manual_seed(0)).to(dev)
+    tables = {"paged seq ": torch.arange(B * MP, device=dev, dtype=torch.int32).view(B, MP),
+              "paged shuf": perm.to(torch.int32).view(B, MP).contiguous()}
+    for hkv in KV_HEADS:
+        cache_bytes = 2 * B * hkv * CAP * DH * 2
+        ncopy = max(1, min(64, ROTATE_BYTES // cache_bytes))
+        cache = KVCache(ncopy, B, hkv, CAP, dev)
+        pools = {k: ([], []) for k in tables}
+        for l in range(ncopy):
+            for c, which in ((cache.k[l], 0), (cache.v[l], 1)):
+                c.copy_(torch.randn(B, hkv, CAP, DH, device=dev, generator=g))
+                seq = c.view(B, hkv, MP, 64, DH).permute(0, 2, 1, 3, 4).reshape(B * MP, hkv, 64, DH).contiguous()
+                shuf = torch.empty_like(seq)
+                shuf[perm] = seq  # logical page i lives in pool page perm[i]
+                pools["paged seq "][which].append(seq)
+                pools["paged shuf"][which].append(shuf)
+        qkv = torch.randn(B, 1, (H + 2 * hkv) * DH, device=dev, generator=g).bfloat16()
+        S, C = attention_decode_geo(B, hkv, CAP, None, H // hkv)
+        emit(f"## Hkv = {hkv} (G = {H // hkv}): (S, C) = ({S}, {C}) for all three, {S * hkv * B} workgroups; one cache "
+             f"{cache_bytes / 2**20:.0f} MiB, rotating over {ncopy} ({ncopy * cache_bytes / 2**20:.0f} MiB)")
+        for lens in LENS:
+            cache.set_lens([lens] * B)
+            must = 2 * B * hkv * (lens + 1) * DH * 2 + 2 * B * H * DH * 2
+            cands = {"contiguous": lambda i: attention_decode(qkv, cache.k[i % ncopy], cache.v[i % ncopy], cache.lens, H, hkv,
+                                                              scale, cache=cache)}
+            for name, table in tables.items():
+                cands[name] = lambda i, kp=pools[name][0], vp=pools[name][1], t=table: attention_decode_paged(
+                    qkv, kp[i % ncopy], vp[i % ncopy], t, cache.lens, H, hkv, scale, cache=cache)
+            ref = attention_decode(qkv, cache.k[0], cache.v[0], cache.lens, H, hkv, scale, cache=cache, return_lse=True)
+            same = []
+            for name, table in tables.items():
+                o, lse = attention_decode_paged(qkv, pools[name][0][0], pools[name][1][0], table, cache.lens, H, hkv, scale,
+                                                cache=cache, return_lse=True)
+                same.append(f"{name.strip()}: O {bool(torch.equal(o, ref[0]))}, LSE {bool(torch.equal(lse, ref[1]))}")
+            t = _alternate(cands, rounds, iters)
+            base = statistics.median(t["contiguous"][1])
+            for name, (te, tg) in t.items():
+                m = statistics.median(tg)
+                emit(f"lens {lens:5d}  {name:<10} replayed {m * 1e3:6.1f} us ({min(tg) * 1e3:.1f}-{max(tg) * 1e3:.1f})  "
+                     f"{m / base:5.2f}x contiguous  must move {must / 1e6:6.2f} MB  {must / m / 1e9:6.2f} TB/s")
+            emit(f"lens {lens:5d}  bits equal to the contiguous kernel's: " + "; ".join(same))
+        del cache, pools
+
+
+def bench_paged_step(rounds, emit, prompt=128, steps=32):
+    """--paged: llama_medium's captured decode step at positions prompt .. prompt + steps - 1 on a KVCache and on
+    a PagedKVCache (pages reserved up front), the two graphs taking turns."""
+    from pytorch_distributed_training_example_amd.models import get_model
+    from pytorch_distributed_training_example_amd.models.precision import to_bf16_mixed
+    torch.manual_seed(0)
+    model = to_bf16_mixed(get_model("llama_medium").cuda()).eval()
+    idx = torch.randint(0, model.cfg.vocab_size, (B, prompt), generator=torch.Generator().manual_seed(1)).cuda()
+    tok = torch.zeros(B, dtype=torch.long, device="cuda")
+    runs = {}
+    with torch.no_grad():
+        for name in ("contiguous", "paged"):
+            if name == "paged":
+                cache = model.new_paged_cache(B, B * 4, 4)
+                for s in range(B):
+                    cache.admit(s)
+                cache.reserve(prompt + steps + 4)
+            else:
+                cache = model.new_cache(B, prompt + steps + 4)
+            model.prefill(idx, cache)
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                model.decode_step(tok, cache)
+            torch.cuda.current_stream().wait_stream(side)
+            cache.set_lens([prompt] * B)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                logits = model.decode_step(tok, cache)
+            runs[name] = (cache, graph, logits)
+    out = {k: [] for k in runs}
+    for _ in range(rounds + 1):  # the first round warms up
+        for k, (cache, graph, _) in runs.items():
+            cache.set_lens([prompt] * B)
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(steps):
+                graph.replay()
+            e.record()
+            torch.cuda.synchronize()
+            out[k].append(s.elapsed_time(e) / steps)
+    for k, v in out.items():
+        v = v[1:]
+        emit(f"llama_medium kv_heads=16: captured decode step at position {prompt}..{prompt + steps - 1}, {k:<10} cache: "
+             f"{statistics.median(v):.3f} ms ({min(v):.3f}-{max(v):.3f})")
+    emit("llama_medium: last replayed logits equal on the two caches: "
+         f"{bool(torch.equal(runs['contiguous'][2], runs['paged'][2]))}")
 
 
 def bench_extend(rounds, iters, emit):
@@ -589,6 +698,8 @@ def main(argv=None):
     ap.add_argument("--gemm-w8", action="store_true", help="the decode-time Linears on e4m3 weights: the W8A16 skinny "
                     "GEMM against the bf16 one and the library, then the generation with and without "
                     "quantize_decode_weights() under PDT_DECODE_GEMM=1")
+    ap.add_argument("--paged", action="store_true", help="the paged decode kernel under a sequential and a shuffled "
+                    "block table against the contiguous kernel, then llama_medium's captured step on both caches")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -601,7 +712,12 @@ def main(argv=None):
 
     emit(f"# {torch.cuda.get_device_name(0)}; B={B} H={H} Dh={DH} capacity={CAP} bf16; median of {a.rounds} alternating "
          f"rounds (min-max), {a.iters} calls per window, device events")
-    if a.gemm_w8:
+    if a.paged:
+        if not a.no_kernel:
+            bench_paged(a.rounds, a.iters, emit)
+        if not a.no_generate:
+            bench_paged_step(a.gen_rounds, emit)
+    elif a.gemm_w8:
         if not a.no_kernel:
             bench_gemm_w8(a.rounds, a.iters, emit)
         if not a.no_generate:
@@ -615,7 +731,7 @@ def main(argv=None):
         bench_extend(a.rounds, a.iters, emit)
     elif not a.no_kernel:
         bench_kernel(a.rounds, a.iters, emit)
-    if not a.no_generate and not a.extend and not a.gemm and not a.gemm_w8:
+    if not a.no_generate and not a.extend and not a.gemm and not a.gemm_w8 and not a.paged:
         bench_generate(a.gen_rounds, emit)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
