@@ -2086,6 +2086,49 @@ std::vector<int64_t> attn_decode_paged(Tensor qkv, Tensor k_pool, Tensor v_pool,
   return geo;
 }
 
+// attn_extend on a paged cache (attn_paged_extend.hip); the arguments of attn_extend with the pools and the table
+// for the caches. Returns (S, C, NB, NT) = attn_extend_geo(B, kv_heads, 64 * max_pages, Tn, heads / kv_heads, splits).
+std::vector<int64_t> attn_extend_paged(Tensor qkv, Tensor k_pool, Tensor v_pool, Tensor block_table, Tensor lens,
+                                       int64_t heads, int64_t kv_heads, double scale, int64_t splits, Tensor out,
+                                       c10::optional<Tensor> o_part, c10::optional<Tensor> ml_part,
+                                       c10::optional<Tensor> lse) {
+  const Op op("attn_extend_paged", qkv);
+  const PagedDims d = paged_dims(op, qkv, k_pool, v_pool, block_table, lens, heads, kv_heads);
+  TORCH_CHECK(d.Tn >= 1, "attn_extend_paged: at least one new token per sequence, got Tn = ", d.Tn);
+  TORCH_CHECK(scale > 0 && splits >= 0, "attn_extend_paged: scale must be positive and splits >= 0");
+  const int64_t rows = (int64_t)d.B * d.Tn * d.H;
+  TORCH_CHECK((int64_t)d.B * d.Tn <= 0x7fffffffLL, "attn_extend_paged: B * Tn = ", (int64_t)d.B * d.Tn, " is too large");
+  TORCH_CHECK(out.defined() && out.device() == op.dev && out.scalar_type() == at::kBFloat16 && out.is_contiguous() &&
+                  out.numel() == rows * 64 && aligned16(out),
+              "attn_extend_paged: out must be a contiguous bf16 [B, Tn, heads * 64] tensor on ", op.dev);
+  const std::vector<int64_t> geo =
+      attn_extend_geo(d.B, d.Hkv, (int64_t)d.max_pages * 64, d.Tn, d.H / d.Hkv, splits);
+  const int64_t S = geo[0];
+  float* lp = opt_f32_ptr(op, "lse", lse, rows);
+  float *op_ptr = nullptr, *ml_ptr = nullptr;
+  if (S > 1) {
+    TORCH_CHECK(has(o_part) && has(ml_part), "attn_extend_paged: S = ", S, " splits need the o_part / ml_part scratch");
+    for (const Tensor* t : {&*o_part, &*ml_part})
+      TORCH_CHECK(t->device() == op.dev && t->scalar_type() == at::kFloat && t->is_contiguous() && aligned16(*t),
+                  "attn_extend_paged: the scratch must be contiguous, 16-byte aligned fp32 on ", op.dev);
+    TORCH_CHECK(o_part->numel() >= rows * S * 64 && ml_part->numel() >= rows * S * 2,
+                "attn_extend_paged: scratch too small for S = ", S, ", Tn = ", d.Tn, ": o_part ", o_part->numel(), " < ",
+                rows * S * 64, " or ml_part ", ml_part->numel(), " < ", rows * S * 2);
+    op_ptr = o_part->data_ptr<float>();
+    ml_ptr = ml_part->data_ptr<float>();
+  }
+  int rc = pdt_attn_extend_paged(bf16_ptr(qkv), qkv.stride(0), qkv.stride(1), bf16_ptr(k_pool), bf16_ptr(v_pool),
+                                 block_table.data_ptr<int>(), lens.data_ptr<int>(), op_ptr, ml_ptr, bf16_out(out), lp,
+                                 d.B, d.Tn, d.H, d.Hkv, d.n_pages, d.max_pages, (int)S, (int)geo[1], (int)geo[2],
+                                 (int)geo[3], (float)scale, stream());
+  TORCH_CHECK(rc == 0, "pdt_attn_extend_paged failed: ", rc);
+  if (S > 1) {
+    rc = pdt_attn_decode_combine(op_ptr, ml_ptr, bf16_out(out), lp, d.B * d.Tn, d.H, (int)S, stream());
+    TORCH_CHECK(rc == 0, "pdt_attn_decode_combine failed: ", rc);
+  }
+  return geo;
+}
+
 // y = silu(gu[:, :F]) * gu[:, F:] for gu [..., 2F] (swiglu.hip)
 Tensor swiglu_fwd(Tensor gu, c10::optional<Tensor> y_out) {
   const Op op("swiglu_fwd", gu);
@@ -3118,6 +3161,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("heads"), py::arg("kv_heads"), py::arg("k_pool"), py::arg("v_pool"), py::arg("block_table"),
         py::arg("lens"));
   m.def("attn_decode_paged", &attn_decode_paged, py::arg("qkv"), py::arg("k_pool"), py::arg("v_pool"),
+        py::arg("block_table"), py::arg("lens"), py::arg("heads"), py::arg("kv_heads"), py::arg("scale"),
+        py::arg("splits"), py::arg("out"), py::arg("o_part") = py::none(), py::arg("ml_part") = py::none(),
+        py::arg("lse") = py::none());
+  m.def("attn_extend_paged", &attn_extend_paged, py::arg("qkv"), py::arg("k_pool"), py::arg("v_pool"),
         py::arg("block_table"), py::arg("lens"), py::arg("heads"), py::arg("kv_heads"), py::arg("scale"),
         py::arg("splits"), py::arg("out"), py::arg("o_part") = py::none(), py::arg("ml_part") = py::none(),
         py::arg("lse") = py::none());

@@ -74,6 +74,11 @@ int pdt_attn_decode_paged(const uint16_t* qkv, int64_t q_sb, const uint16_t* k_p
                           const int* block_table, const int* lens, float* o_part, float* ml_part, uint16_t* out,
                           float* lse, int B, int H, int Hkv, int n_pages, int max_pages, int S, int C, float scale,
                           hipStream_t s);
+// kernels/attn_paged_extend.hip: pdt_attn_extend on a paged cache; geo4 = pdt_attn_extend_geo at 64 max_pages
+int pdt_attn_extend_paged(const uint16_t* qkv, int64_t q_sb, int64_t q_st, const uint16_t* k_pool,
+                          const uint16_t* v_pool, const int* block_table, const int* lens, float* o_part,
+                          float* ml_part, uint16_t* out, float* lse, int B, int Tn, int H, int Hkv, int n_pages,
+                          int max_pages, int S, int C, int NB, int NT, float scale, hipStream_t s);
 
 // kernels/batchnorm.hip
 int64_t pdt_bn_workspace_floats(int64_t M, int C);

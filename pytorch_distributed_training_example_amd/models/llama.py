@@ -36,7 +36,8 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..config import SW
-from ..ops.attention import attention_decode, attention_decode_paged, attention_extend, attention_qkv
+from ..ops.attention import (attention_decode, attention_decode_paged, attention_extend, attention_extend_paged,
+                             attention_qkv)
 from ..ops.cross_entropy import cross_entropy
 from ..ops.fp8 import Fp8Act, add_rms_norm_fp8, fp8_input_slot, fp8_linear, fp8_ok, fp8_swiglu_mlp, rms_fp8_ok
 from ..ops.kv_cache import PAGE, KVCache, PagedKVCache
@@ -153,21 +154,24 @@ class LlamaAttention(nn.Module):
         return _linear(y, self.c_proj)
 
     def _forward_paged(self, x, rope, cache: PagedKVCache, layer: int):
-        """``_forward_cached`` on a paged cache: the paged append, then the causal flash forward on the new rows
-        (Tn > 1: a prefill of empty slots, the ones ``cache.select`` named) or the paged split-KV kernel
-        (Tn == 1, every slot). Tn > 1 onto a slot that holds something is the multi-token append, which has no
-        paged kernel yet."""
+        """``_forward_cached`` on a paged cache, on the slots ``cache.select`` named: the paged append, then the
+        causal flash forward on the new rows (Tn > 1: a prefill of empty slots), the paged split-KV kernel
+        (Tn == 1) or, under ``Llama.extend`` with Tn > 1, the paged multi-token append kernel, whatever the slots
+        hold."""
         Tn = x.shape[1]
         table, lens, slots = cache.view()
-        if Tn > 1 and any(cache.bounds[s] > 0 for s in (range(cache.slots) if slots is None else slots)):
-            raise NotImplementedError(f"{Tn} new tokens onto paged slots that may hold something: the multi-token "
-                                      "append (extend) has no paged kernel yet; a paged cache takes a prefill of "
-                                      "empty slots and one-token decode steps")
+        if Tn > 1 and not cache.extending and any(
+                cache.bounds[s] > 0 for s in (range(cache.slots) if slots is None else slots)):
+            raise ValueError(f"{Tn} new tokens onto paged slots that may hold up to {cache.bound} positions: chunked "
+                             "prefill is not what prefill does (prefill empty slots, then extend() or decode_step())")
         cache.require(Tn, rope.cos.shape[0], slots)
         qkv = _linear(x, self.c_attn)
         qkv = rope_append_paged_(qkv, rope.cos, rope.sin, self.heads, self.kv_heads, cache.k[layer], cache.v[layer],
                                  table, lens)
-        if Tn > 1:
+        if Tn > 1 and cache.extending:
+            y = attention_extend_paged(qkv, cache.k[layer], cache.v[layer], table, lens, self.heads, self.kv_heads,
+                                       cache=cache)
+        elif Tn > 1:
             y = attention_qkv(qkv, self.heads, causal=True, kv_heads=self.kv_heads)
         else:
             y = attention_decode_paged(qkv, cache.k[layer], cache.v[layer], table, lens, self.heads, self.kv_heads,
@@ -397,7 +401,46 @@ class Llama(nn.Module):
         cache.advance(1)
         return self._head(x[:, 0])
 
-    def extend(self, idx: torch.Tensor, cache: KVCache, new_lens=None, last_only: bool = False) -> torch.Tensor:
+    def _extend_paged(self, idx: torch.Tensor, cache: PagedKVCache, new_lens, last_only: bool, slots) -> torch.Tensor:
+        """``extend`` on the distinct admitted slots ``slots`` of a paged cache, whose pages
+        ``cache.reserve(Tn, slots=slots)`` has handed out; the other slots are not touched."""
+        b, Tn = idx.shape
+        if slots is None:
+            raise NotImplementedError("extend on a paged cache is a per-sequence operation: name the slots that run "
+                                      "with slots= (slots=range(cache.slots) is the all-slot form)")
+        slots = [int(s) for s in slots]
+        if (cache.n_layer, cache.kv_heads) != (self.cfg.n_layer, self.cfg.kv_heads) or len(slots) != b:
+            raise ValueError(f"paged cache for {cache.n_layer} layers x {cache.kv_heads} K/V heads does not fit this "
+                             f"model ({self.cfg.n_layer} x {self.cfg.kv_heads}), or {len(slots)} slots for {b} rows")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise RuntimeError("the KV-cache path is inference only: call it under torch.no_grad()")
+        if Tn < 1:
+            raise ValueError("extend: at least one new token per sequence")
+        if new_lens is not None:
+            new_lens = _lens_arg(new_lens, b, 0, Tn, idx.device, "new_lens")
+        cache.select(slots)  # refuses slots that are not distinct and admitted
+        cache.extending = True
+        try:
+            x = F.embedding(idx, self.transformer.wte.weight)
+            x = run_llama_blocks(self.transformer.h, x, self.transformer.ln_f, self.rope, cache)
+            if new_lens is not None:  # the selected rows of lens, gathered before the forward
+                moved = cache.view()[1] + new_lens
+        finally:
+            cache.extending = False
+            cache.select(None)
+        if new_lens is None:
+            cache.advance(Tn, slots)
+        else:
+            cache.set_lens(moved, bound=[cache.bounds[s] + Tn for s in slots], slots=slots)
+        if last_only:
+            if new_lens is None:
+                x = x[:, -1]
+            else:  # a sequence that got nothing returns its row 0: the caller keeps what it had
+                x = x.gather(1, (new_lens.long() - 1).clamp(min=0)[:, None, None].expand(b, 1, x.shape[-1]))[:, 0]
+        return self._head(x)
+
+    def extend(self, idx: torch.Tensor, cache: KVCache, new_lens=None, last_only: bool = False,
+               slots=None) -> torch.Tensor:
         """Append ``idx`` [B, Tn] at positions ``cache.lens[b] + t`` of a cache that may already hold a
         conversation (a later turn's prompt, a slice of a chunked prefill, drafted tokens to verify: the
         caller rolls back with ``cache.set_lens``). Returns the logits [B, Tn, V]; with ``last_only`` [B, V]
@@ -406,7 +449,19 @@ class Llama(nn.Module):
         tensor, or a device tensor, which is clamped rather than read); the next append overwrites the
         padding rows. Tn == 1 runs the split-KV decode kernel, Tn > 1 the multi-token append kernel, on an
         empty cache too. With ``new_lens`` None or on the device nothing here reads the device, so the call
-        can be captured like ``decode_step``."""
+        can be captured like ``decode_step``.
+
+        On a ``PagedKVCache`` ``slots`` names the B distinct admitted slots that run (their pages come from
+        ``cache.reserve(Tn, slots=slots)`` beforehand): the paged append kernel for Tn > 1, and only their
+        ``lens`` and host bounds move; the other slots get no row and keep their ``lens``. This is how a long
+        prompt joins a running batch in slices, a later turn lands on a slot's history and drafted tokens are
+        verified (roll back with ``cache.set_lens(..., slots=slots)``). Without ``slots`` a paged cache raises
+        ``NotImplementedError``: ``slots=range(cache.slots)`` is the all-slot form. The slot gather uploads an
+        index, so this form is not captured."""
+        if isinstance(cache, PagedKVCache):
+            return self._extend_paged(idx, cache, new_lens, last_only, slots)
+        if slots is not None:
+            raise ValueError("extend: slots names slots of a PagedKVCache; a KVCache's batch is fixed")
         B, Tn = idx.shape
         self._check_cache(cache, B)
         if Tn < 1:
@@ -432,21 +487,29 @@ class Llama(nn.Module):
 
     def _prefill_chunked(self, idx: torch.Tensor, cache: KVCache, prompt_lens, chunk: int) -> torch.Tensor:
         """``prefill`` in slices of ``chunk`` positions: the first through ``prefill``, the rest through
-        ``extend(..., last_only=True)``; a sequence whose prompt ended in an earlier slice keeps its logits."""
+        ``extend(..., last_only=True)``; a sequence whose prompt ended in an earlier slice keeps its logits. On a
+        paged cache (every slot admitted) each slice's pages are reserved just before it runs."""
         B, T0 = idx.shape
         if chunk < 1:
             raise ValueError(f"prefill_chunk must be positive, got {chunk}")
         if prompt_lens is not None:
             prompt_lens = _lens_arg(prompt_lens, B, 1, T0, idx.device, "prompt_lens")
+        paged = isinstance(cache, PagedKVCache)
+        kw = dict(slots=range(B)) if paged else {}
         first = min(chunk, T0)
+        if paged:
+            cache.reserve(first)
         logits = self.prefill(idx[:, :first], cache, None if prompt_lens is None else prompt_lens.clamp(max=first))
         for s in range(first, T0, chunk):
             part = idx[:, s:s + chunk]
+            if paged:
+                cache.reserve(part.shape[1])
             if prompt_lens is None:
-                logits = self.extend(part, cache, last_only=True)
+                logits = self.extend(part, cache, last_only=True, **kw)
             else:
                 n = (prompt_lens - s).clamp(0, part.shape[1])
-                logits = torch.where((n > 0)[:, None], self.extend(part, cache, new_lens=n, last_only=True), logits)
+                logits = torch.where((n > 0)[:, None], self.extend(part, cache, new_lens=n, last_only=True, **kw),
+                                     logits)
         return logits
 
     @torch.no_grad()
@@ -461,14 +524,11 @@ class Llama(nn.Module):
         no step reads a token on the host). With ``prefill_chunk`` the prompt runs in slices of that many
         positions (``prefill`` of the first, ``extend`` of the rest), which bounds the activation memory of a
         long prompt by the slice. With ``paged`` the same loop runs on a ``PagedKVCache`` sized for the batch,
-        which reserves pages before the prefill and before every step (no ``prefill_chunk`` there: a paged
-        cache has no multi-token append yet). Runs in ``eval()`` and restores the mode."""
+        which reserves pages before the prefill (with ``prefill_chunk``: before every slice) and before every
+        step. Runs in ``eval()`` and restores the mode."""
         B, T0 = idx.shape
         if max_new_tokens < 1:
             raise ValueError(f"max_new_tokens must be positive, got {max_new_tokens}")
-        if paged and prefill_chunk is not None:
-            raise NotImplementedError("generate: prefill_chunk needs the multi-token append, which has no paged "
-                                      "kernel yet")
         if T0 + max_new_tokens > self.cfg.block_size:
             raise ValueError(f"prompt of {T0} + {max_new_tokens} new tokens exceeds block_size {self.cfg.block_size} "
                              "(the RoPE table)")
@@ -480,7 +540,8 @@ class Llama(nn.Module):
                 cache = self.new_paged_cache(B, B * per_seq, per_seq)
                 for s in range(B):
                     cache.admit(s)
-                cache.reserve(T0)
+                if prefill_chunk is None:
+                    cache.reserve(T0)
             else:
                 cache = self.new_cache(B, T0 + max_new_tokens)
             if prefill_chunk is None:

@@ -388,6 +388,65 @@ def attention_extend(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
     return (out, lse) if return_lse else out
 
 
+EXTEND_PAGED_STATS = {"native_calls": 0, "geo": None}  # launches of the paged append kernel, its last (S, C, NB, NT)
+
+
+def attention_extend_paged(qkv: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor,
+                           lens: torch.Tensor, heads: int, kv_heads: int | None = None, scale: float | None = None,
+                           splits: int | None = None, cache=None, return_lse: bool = False):
+    """``attention_extend`` on a paged cache: ``qkv`` [B, Tn, (H + 2·Hkv)·64] with Q rotated, ``rope_append_paged_``
+    having written the tokens' K and V at positions ``lens[b] + t`` of the pages that ``block_table`` (int32
+    [B, max_pages]) names in ``k_pool`` / ``v_pool`` [n_pages, Hkv, 64, 64]; ``lens`` int32 [B] is the count before
+    the append and is read on the device. Query (b, t) sees keys 0 .. lens[b] + t, whatever else its pages or the
+    pool hold. Returns [B, Tn, H·64] (and the LSE [B, Tn, H] with ``return_lse``). Inference only.
+
+    bf16 GPU tensors run the paged append kernel (csrc/kernels/attn_paged_extend.hip) with the (S, C, NB, NT) of
+    ``attention_extend_geo`` for a capacity of 64·max_pages, Tn == 1 the paged decode kernel (as
+    ``attention_extend``'s callers take ``attention_decode``); ``splits`` and ``cache`` (a ``PagedKVCache``, whose
+    scratch serves B <= slots rows) as in ``attention_decode``. CPU, fp32 and ``PDT_DISABLE_NATIVE=1`` gather
+    every slot's pages into a contiguous cache and take the PyTorch reference."""
+    kv_heads = heads if kv_heads is None else kv_heads
+    if kv_heads <= 0 or heads % kv_heads != 0:
+        raise ValueError(f"attention_extend_paged: heads = {heads} is not a positive multiple of kv_heads = {kv_heads}")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (qkv, k_pool, v_pool)):
+        raise RuntimeError("attention_extend_paged: inference only (run it under torch.no_grad())")
+    if qkv.dim() != 3 or qkv.shape[1] < 1 or qkv.shape[2] % (heads + 2 * kv_heads) != 0:
+        raise ValueError(f"attention_extend_paged: qkv {tuple(qkv.shape)} is not [B, Tn >= 1, (heads + 2·kv_heads)·Dh]")
+    dh = qkv.shape[2] // (heads + 2 * kv_heads)
+    scale = scale if scale is not None else 1.0 / math.sqrt(dh)
+    if use_native(qkv) and qkv.dtype == torch.bfloat16:  # head dim 64 and the layouts: the binding's checks
+        B, Tn = qkv.shape[0], qkv.shape[1]
+        if cache is not None and B > cache.batch:
+            cache = None
+        if Tn == 1:  # fewer rows than slots use the leading rows of the cache's scratch
+            got = attention_decode_paged(qkv, k_pool, v_pool, block_table, lens, heads, kv_heads, scale, splits,
+                                         cache, return_lse)
+            return (got[0], got[1].view(B, 1, heads)) if return_lse else got
+        out = torch.empty(B, Tn, heads * dh, device=qkv.device, dtype=qkv.dtype)
+        lse = torch.empty(B, Tn, heads, device=qkv.device, dtype=torch.float32) if return_lse else None
+        o_part = ml_part = None
+        if block_table.dim() == 2 and block_table.shape[1] > 0 and dh == 64:
+            S = attention_extend_geo(B, kv_heads, PAGE * block_table.shape[1], Tn, splits, heads // kv_heads)[0]
+            if S > 1:
+                if cache is not None:
+                    o_part, ml_part = (t[:B] for t in cache.scratch(heads, S, Tn))
+                else:
+                    o_part = torch.empty(B, Tn, heads, S, 64, device=qkv.device, dtype=torch.float32)
+                    ml_part = torch.empty(B, Tn, heads, S, 2, device=qkv.device, dtype=torch.float32)
+        geo = native().attn_extend_paged(qkv, k_pool, v_pool, block_table, lens, heads, kv_heads, scale,
+                                         int(splits or 0), out, o_part, ml_part, lse)
+        EXTEND_PAGED_STATS["native_calls"] += 1
+        EXTEND_PAGED_STATS["geo"] = tuple(int(x) for x in geo)
+        return (out, lse) if return_lse else out
+    from .rope import gather_pages
+    if k_pool.dim() != 4 or k_pool.shape != v_pool.shape or block_table.dim() != 2 or block_table.shape[0] != qkv.shape[0]:
+        raise ValueError(f"attention_extend_paged: pools {tuple(k_pool.shape)}, {tuple(v_pool.shape)} are not "
+                         f"[n_pages, kv_heads, 64, Dh] or the table {tuple(block_table.shape)} is not [B, max_pages]")
+    out, lse = _extend_reference(qkv, gather_pages(k_pool, block_table), gather_pages(v_pool, block_table),
+                                 lens, heads, kv_heads, scale)
+    return (out, lse) if return_lse else out
+
+
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False,
               dropout_p: float = 0.0, scale: float | None = None) -> torch.Tensor:
     """Unpacked [B, H, T, Dh] interface (SDPA-compatible)."""

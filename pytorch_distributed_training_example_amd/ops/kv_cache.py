@@ -133,7 +133,8 @@ class PagedKVCache:
         self._bound = [0] * slots
         self._active = [False] * slots
         self._scratch: dict = {}
-        self._view = None  # (block_table rows, lens) of the slots a prefill runs on
+        self._view = None  # (block_table rows, lens) of the slots a prefill or an extend runs on
+        self.extending = False  # set by Llama.extend around its forward: Tn > 1 then runs the paged append kernel
 
     # ------------------------------------------------------------------ what the contiguous cache also answers
     @property
@@ -240,12 +241,18 @@ class PagedKVCache:
                                  f"the rotary table's {table_len} positions")
 
     # ------------------------------------------------------------------ lens
-    def advance(self, n: int = 1) -> None:
-        """``lens += n * active`` on the device; the bounds of the active slots follow."""
-        self.lens.add_(self.active, alpha=n)
-        for s in range(self.slots):
-            if self._active[s]:
-                self._bound[s] += n
+    def advance(self, n: int = 1, slots=None) -> None:
+        """``lens += n * active`` on the device; the bounds of the active slots follow. With ``slots`` (distinct
+        admitted slots) only those move."""
+        if slots is None:
+            self.lens.add_(self.active, alpha=n)
+            named = [s for s in range(self.slots) if self._active[s]]
+        else:
+            named = self._named(slots)
+            self.lens.index_add_(0, torch.as_tensor(named, device=self.device),
+                                 torch.full((len(named),), n, device=self.device, dtype=torch.int32))
+        for s in named:
+            self._bound[s] += n
 
     def set_lens(self, lens, bound=None, slots=None) -> None:
         """``lens[slots] = lens`` (default: all slots). ``KVCache.set_lens``'s contract per slot: a sequence or a
@@ -290,11 +297,14 @@ class PagedKVCache:
         """(block_table rows, lens, slots or None) of the slots the forward runs on."""
         return self._view if self._view is not None else (self.block_table, self.lens, None)
 
-    def scratch(self, heads: int, S: int):
-        """(o_part [slots, heads, S, 64], ml_part [slots, heads, S, 2]) fp32: allocated on the first request."""
-        key = (heads, S)
+    def scratch(self, heads: int, S: int, tokens: int = 1):
+        """(o_part [slots, heads, S, 64], ml_part [slots, heads, S, 2]) fp32: allocated on the first request. With
+        ``tokens`` > 1 (a multi-token append) the shapes are [slots, tokens, heads, S, 64] and [slots, tokens, heads,
+        S, 2], as ``KVCache.scratch``'s; a call on fewer rows than ``slots`` uses the leading rows."""
+        key = (heads, S) if tokens == 1 else (heads, S, tokens)
         if key not in self._scratch:
+            lead = (self.slots,) if tokens == 1 else (self.slots, tokens)
             self._scratch[key] = (
-                torch.empty(self.slots, heads, S, HEAD_DIM, device=self.device, dtype=torch.float32),
-                torch.empty(self.slots, heads, S, 2, device=self.device, dtype=torch.float32))
+                torch.empty(*lead, heads, S, HEAD_DIM, device=self.device, dtype=torch.float32),
+                torch.empty(*lead, heads, S, 2, device=self.device, dtype=torch.float32))
         return self._scratch[key]

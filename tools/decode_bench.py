@@ -47,6 +47,11 @@ alternating, device events, median of the rounds): attention_decode_paged with a
 with a seeded shuffled one against attention_decode on the same keys, and whether the three give the same
 bits; then llama_medium's captured decode step on a KVCache and on a PagedKVCache.
 
+--paged --extend: the paged append kernel. The --extend table's shapes and recipe: attention_extend (the reference
+of every time) and attention_extend_paged with a sequential and a seeded shuffled block table take turns in one
+process, captured and replayed, over rotating caches, and whether the three give the same bits; then llama_medium
+with 8 paged slots, a 512-token prompt joining in slices of 64 against the same prompt as one paged prefill.
+
     python tools/decode_bench.py [--rounds 7] [--iters 50] [--gen-rounds 3] [--no-generate] [--extend] [--paged] [--out FILE]
 """
 from __future__ import annotations
@@ -265,6 +270,114 @@ def bench_paged_step(rounds, emit, prompt=128, steps=32):
              f"{statistics.median(v):.3f} ms ({min(v):.3f}-{max(v):.3f})")
     emit("llama_medium: last replayed logits equal on the two caches: "
          f"{bool(torch.equal(runs['contiguous'][2], runs['paged'][2]))}")
+
+
+def bench_paged_extend(rounds, iters, emit):
+    """--paged --extend: attention_extend_paged under a sequential and a seeded shuffled block table against
+    attention_extend (the contiguous kernel, the reference of every time) at bench_extend's shapes, the same keys
+    in all three, each captured and replayed over rotating caches, taking turns; and whether the bits agree."""
+    from pytorch_distributed_training_example_amd.ops.attention import (attention_extend, attention_extend_geo,
+                                                                         attention_extend_paged)
+    from pytorch_distributed_training_example_amd.ops.kv_cache import KVCache
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    scale = 1.0 / math.sqrt(DH)
+    MP = CAP // 64
+    perm = torch.randperm(B * MP, generator=torch.Generator().manual_seed(0)).to(dev)
+    tables = {"paged seq ": torch.arange(B * MP, device=dev, dtype=torch.int32).view(B, MP),
+              "paged shuf": perm.to(torch.int32).view(B, MP).contiguous()}
+    for hkv in KV_HEADS:
+        cache_bytes = 2 * B * hkv * CAP * DH * 2
+        ncopy = max(1, min(64, ROTATE_BYTES // cache_bytes))
+        cache = KVCache(ncopy, B, hkv, CAP, dev)
+        pools = {k: ([], []) for k in tables}
+        for l in range(ncopy):
+            for c, which in ((cache.k[l], 0), (cache.v[l], 1)):
+                c.copy_(torch.randn(B, hkv, CAP, DH, device=dev, generator=g))
+                seq = c.view(B, hkv, MP, 64, DH).permute(0, 2, 1, 3, 4).reshape(B * MP, hkv, 64, DH).contiguous()
+                shuf = torch.empty_like(seq)
+                shuf[perm] = seq  # logical page i lives in pool page perm[i]
+                pools["paged seq "][which].append(seq)
+                pools["paged shuf"][which].append(shuf)
+        emit(f"## Hkv = {hkv} (G = {H // hkv}): one cache {cache_bytes / 2**20:.0f} MiB, rotating over {ncopy} "
+             f"({ncopy * cache_bytes / 2**20:.0f} MiB)")
+        for tn in (4, 8, 64):
+            qkv = torch.randn(B, tn, (H + 2 * hkv) * DH, device=dev, generator=g).bfloat16()
+            geo = attention_extend_geo(B, hkv, CAP, tn, None, H // hkv)
+            for lens in (128, CAP - 1 - tn):
+                cache.set_lens([lens] * B)
+                must = 2 * B * hkv * (lens + tn) * DH * 2 + 2 * B * tn * H * DH * 2
+                cands = {"contiguous": lambda i: attention_extend(qkv, cache.k[i % ncopy], cache.v[i % ncopy], cache.lens,
+                                                                  H, hkv, scale, cache=cache)}
+                for name, table in tables.items():
+                    cands[name] = lambda i, kp=pools[name][0], vp=pools[name][1], t=table: attention_extend_paged(
+                        qkv, kp[i % ncopy], vp[i % ncopy], t, cache.lens, H, hkv, scale, cache=cache)
+                ref = attention_extend(qkv, cache.k[0], cache.v[0], cache.lens, H, hkv, scale, cache=cache, return_lse=True)
+                same = []
+                for name, table in tables.items():
+                    o, lse = attention_extend_paged(qkv, pools[name][0][0], pools[name][1][0], table, cache.lens, H, hkv,
+                                                    scale, cache=cache, return_lse=True)
+                    same.append(f"{name.strip()}: O {bool(torch.equal(o, ref[0]))}, LSE {bool(torch.equal(lse, ref[1]))}")
+                graphs = {k: _graphed(fn, iters) for k, fn in cands.items()}
+                t = {k: [] for k in cands}
+                for _ in range(rounds):
+                    for k in cands:
+                        t[k].append(_time_ms(lambda i, gr=graphs[k]: gr.replay(), 1) / iters)
+                base = statistics.median(t["contiguous"])
+                for k, v in t.items():
+                    m = statistics.median(v)
+                    emit(f"Tn {tn:3d} lens {lens:5d}  {k:<10} {m * 1e3:7.1f} us ({min(v) * 1e3:.1f}-{max(v) * 1e3:.1f})  "
+                         f"{m / base:5.2f}x contiguous ({(m - base) * 1e3:+.2f} us)  must move {must / 1e6:6.2f} MB  "
+                         f"{must / m / 1e9:5.2f} TB/s")
+                emit(f"Tn {tn:3d} lens {lens:5d}  geo (S, C, NB, NT) = {geo} for all three; bits equal to the contiguous "
+                     "kernel's: " + "; ".join(same))
+                del graphs
+        del cache, pools
+
+
+def bench_paged_join(rounds, emit, prompt=512, chunk=64):
+    """--paged --extend: llama_medium, 8 slots of a PagedKVCache: a 512-token prompt per slot as one paged prefill
+    against the same prompt joining in slices of 64 through extend(..., slots=range(8)), eager, taking turns."""
+    from pytorch_distributed_training_example_amd.models import get_model
+    from pytorch_distributed_training_example_amd.models.precision import to_bf16_mixed
+    torch.manual_seed(0)
+    model = to_bf16_mixed(get_model("llama_medium").cuda()).eval()
+    idx = torch.randint(0, model.cfg.vocab_size, (B, prompt), generator=torch.Generator().manual_seed(1)).cuda()
+
+    cache = model.new_paged_cache(B, B * (prompt // 64 + 1))
+
+    def fresh():  # every slot given back and admitted again: both candidates pay it
+        for s in range(B):
+            cache.free(s)
+            cache.admit(s)
+        return cache
+
+    @torch.no_grad()
+    def whole():
+        fresh().reserve(prompt)
+        return model.prefill(idx, cache)
+
+    @torch.no_grad()
+    def sliced():
+        return model._prefill_chunked(idx, fresh(), None, chunk)
+
+    cands = {"one prefill": whole, f"slices of {chunk}": sliced}
+    last = {k: fn() for k, fn in cands.items()}
+    out = {k: [] for k in cands}
+    for _ in range(rounds):
+        for k, fn in cands.items():
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            fn()
+            e.record()
+            torch.cuda.synchronize()
+            out[k].append(s.elapsed_time(e))
+    for k, v in out.items():
+        emit(f"llama_medium kv_heads=16, {B} paged slots, {prompt}-token prompt, {k:<13}: {statistics.median(v):8.2f} ms "
+             f"({min(v):.2f}-{max(v):.2f})")
+    a, b = (v.float() for v in last.values())
+    emit(f"llama_medium: last-position logits, slices against one prefill: max |difference| = {(a - b).abs().max().item():.3g} "
+         f"of max |logit| = {b.abs().max().item():.3g}; argmax equal in {int((a.argmax(-1) == b.argmax(-1)).sum())} of {B}")
 
 
 def bench_extend(rounds, iters, emit):
@@ -712,7 +825,12 @@ def main(argv=None):
 
     emit(f"# {torch.cuda.get_device_name(0)}; B={B} H={H} Dh={DH} capacity={CAP} bf16; median of {a.rounds} alternating "
          f"rounds (min-max), {a.iters} calls per window, device events")
-    if a.paged:
+    if a.paged and a.extend:
+        if not a.no_kernel:
+            bench_paged_extend(a.rounds, a.iters, emit)
+        if not a.no_generate:
+            bench_paged_join(a.gen_rounds, emit)
+    elif a.paged:
         if not a.no_kernel:
             bench_paged(a.rounds, a.iters, emit)
         if not a.no_generate:
