@@ -95,9 +95,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--sample-weights", choices=["bf16", "fp8"], default="bf16",
                    help="llama_* only, with --sample-tokens: fp8 quantises the Linear weights row-wise to e4m3 before "
                         "sampling (Llama.quantize_decode_weights: decode steps then stream one byte per weight)")
-    p.add_argument("--sample-cache", choices=["contiguous", "paged"], default="contiguous",
+    p.add_argument("--sample-cache", choices=["contiguous", "paged", "paged-fp8"], default="contiguous",
                    help="llama_* only, with --sample-tokens: paged generates on a PagedKVCache (pages of 64 positions "
-                        "found through a block table) instead of one contiguous slab per sequence")
+                        "found through a block table) instead of one contiguous slab per sequence; paged-fp8 on one "
+                        "that stores e4m3 rows with a scale each")
     p.add_argument("--sample-prompt", default="1", metavar="IDS", help="comma-separated prompt token ids (default: 1)")
     p.add_argument("--sample-temperature", type=float, default=0.0, metavar="T",
                    help="0 (default): greedy; otherwise sample from softmax(logits / T), seeded from --seed")
@@ -370,9 +371,10 @@ def run(rank: int, world: int, args) -> dict:
         prompt = torch.tensor([parse_prompt(args.sample_prompt)], device=device)
         if getattr(args, "sample_weights", "bf16") == "fp8":
             model.quantize_decode_weights()
+        sample_cache = getattr(args, "sample_cache", "contiguous")
         toks = model.generate(prompt, args.sample_tokens, temperature=args.sample_temperature,
-                              top_k=args.sample_top_k, generator=gen,
-                              paged=getattr(args, "sample_cache", "contiguous") == "paged")
+                              top_k=args.sample_top_k, generator=gen, paged=sample_cache != "contiguous",
+                              kv_dtype="fp8" if sample_cache == "paged-fp8" else None)
         result["sample"] = toks[0].tolist()
         print(f"Sample: {result['sample']}", flush=True)
     metrics.close()

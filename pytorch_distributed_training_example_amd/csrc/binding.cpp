@@ -2000,7 +2000,8 @@ struct PagedDims {
   int B, Tn, H, Hkv, n_pages, max_pages;
 };
 PagedDims paged_dims(const Op& op, const Tensor& qkv, const Tensor& k_pool, const Tensor& v_pool,
-                     const Tensor& block_table, const Tensor& lens, int64_t heads, int64_t kv_heads) {
+                     const Tensor& block_table, const Tensor& lens, int64_t heads, int64_t kv_heads,
+                     const Tensor* k_scale = nullptr, const Tensor* v_scale = nullptr) {
   TORCH_CHECK(qkv.scalar_type() == at::kBFloat16, op.name, ": qkv must be bf16, got ", qkv.scalar_type());
   TORCH_CHECK(qkv.dim() == 3 && qkv.is_contiguous() && aligned16(qkv), op.name,
               ": qkv must be a contiguous, 16-byte aligned [B, Tn, (heads + 2 * kv_heads) * 64] tensor");
@@ -2008,9 +2009,16 @@ PagedDims paged_dims(const Op& op, const Tensor& qkv, const Tensor& k_pool, cons
               " is not a positive multiple of kv_heads = ", kv_heads);
   TORCH_CHECK(qkv.size(2) == (heads + 2 * kv_heads) * 64, op.name, ": head dim must be 64: last dim ", qkv.size(2),
               " is not (heads + 2 * kv_heads) * 64 with heads = ", heads, ", kv_heads = ", kv_heads);
+  const bool fp8 = k_scale != nullptr;  // the e4m3 cache (attn_paged_fp8.hip): byte pools and a scale per stored row
   for (const Tensor* c : {&k_pool, &v_pool}) {
-    TORCH_CHECK(c->defined() && c->device() == op.dev && c->scalar_type() == at::kBFloat16, op.name,
-                ": the pools must be bf16 tensors on ", op.dev);
+    if (fp8) {
+      TORCH_CHECK(c->defined() && c->device() == op.dev && c->scalar_type() == at::kFloat8_e4m3fn, op.name,
+                  ": the pools of an fp8 cache must be float8_e4m3fn tensors on ", op.dev, " (a bf16 cache takes the op "
+                  "without scales)");
+    } else {
+      TORCH_CHECK(c->defined() && c->device() == op.dev && c->scalar_type() == at::kBFloat16, op.name,
+                  ": the pools must be bf16 tensors on ", op.dev);
+    }
     TORCH_CHECK(c->dim() == 4 && c->size(0) > 0 && c->size(1) == kv_heads && c->size(2) == 64 && c->size(3) == 64,
                 op.name, ": the pools must be [n_pages, kv_heads, 64, 64] (pages of 64 keys, head dim 64) with kv_heads = ",
                 kv_heads, ", got ", c->sizes());
@@ -2018,6 +2026,15 @@ PagedDims paged_dims(const Op& op, const Tensor& qkv, const Tensor& k_pool, cons
   }
   TORCH_CHECK(k_pool.sizes() == v_pool.sizes(), op.name, ": k_pool and v_pool must have equal sizes");
   TORCH_CHECK(k_pool.size(0) <= 0x7fffffffLL, op.name, ": too many pages");
+  if (fp8)
+    for (const Tensor* c : {k_scale, v_scale}) {
+      TORCH_CHECK(c->defined() && c->device() == op.dev && c->scalar_type() == at::kFloat, op.name,
+                  ": the scale pools must be fp32 tensors on ", op.dev);
+      TORCH_CHECK(c->dim() == 3 && c->size(0) == k_pool.size(0) && c->size(1) == kv_heads && c->size(2) == 64, op.name,
+                  ": the scale pools must be [n_pages, kv_heads, 64], one scale per row of the pools ", k_pool.sizes(),
+                  ", got ", c->sizes());
+      TORCH_CHECK(c->is_contiguous() && aligned16(*c), op.name, ": the scale pools must be contiguous and 16-byte aligned");
+    }
   TORCH_CHECK(block_table.defined() && block_table.device() == op.dev && block_table.scalar_type() == at::kInt &&
                   block_table.is_contiguous() && block_table.dim() == 2 && block_table.size(0) == qkv.size(0) &&
                   block_table.size(1) > 0 && block_table.size(1) <= (1 << 23),
@@ -2079,6 +2096,66 @@ std::vector<int64_t> attn_decode_paged(Tensor qkv, Tensor k_pool, Tensor v_pool,
                                  block_table.data_ptr<int>(), lens.data_ptr<int>(), op_ptr, ml_ptr, bf16_out(out), lp,
                                  d.B, d.H, d.Hkv, d.n_pages, d.max_pages, (int)S, (int)geo[1], (float)scale, stream());
   TORCH_CHECK(rc == 0, "pdt_attn_decode_paged failed: ", rc);
+  if (S > 1) {
+    rc = pdt_attn_decode_combine(op_ptr, ml_ptr, bf16_out(out), lp, d.B, d.H, (int)S, stream());
+    TORCH_CHECK(rc == 0, "pdt_attn_decode_combine failed: ", rc);
+  }
+  return geo;
+}
+
+// ----------------------------------------------------------------------------- e4m3 paged KV cache (attn_paged_fp8.hip)
+// rope_kv_append_paged with a quantising store: pools float8_e4m3fn [n_pages, kv_heads, 64, 64], scale pools fp32
+// [n_pages, kv_heads, 64]; a stored row is quantize_rows_e4m3's of the row the bf16 cache would hold.
+void rope_kv_append_paged_fp8(Tensor qkv, Tensor cos, Tensor sin, int64_t heads, int64_t kv_heads, Tensor k_pool,
+                              Tensor v_pool, Tensor k_scale, Tensor v_scale, Tensor block_table, Tensor lens) {
+  const Op op("rope_kv_append_paged_fp8", qkv);
+  const PagedDims d = paged_dims(op, qkv, k_pool, v_pool, block_table, lens, heads, kv_heads, &k_scale, &v_scale);
+  TORCH_CHECK(cos.dim() == 2 && cos.size(1) == 32 && sin.sizes() == cos.sizes(),
+              "rope_kv_append_paged_fp8: cos and sin must be [T_max, 32] tables");
+  const int64_t Tmax = cos.size(0);
+  const float* cp = f32_ptr(op, "cos", cos, Tmax * 32);
+  const float* sp = f32_ptr(op, "sin", sin, Tmax * 32);
+  TORCH_CHECK(Tmax > 0 && Tmax <= 0x7fffffffLL && aligned16(cos) && aligned16(sin),
+              "rope_kv_append_paged_fp8: cos / sin must be 16-byte aligned");
+  int rc = pdt_rope_kv_append_paged_fp8(bf16_out(qkv), cp, sp, byte_ptr(k_pool), byte_ptr(v_pool),
+                                        k_scale.data_ptr<float>(), v_scale.data_ptr<float>(),
+                                        block_table.data_ptr<int>(), lens.data_ptr<int>(), d.B, d.Tn, d.H, d.Hkv,
+                                        d.n_pages, d.max_pages, (int)Tmax, stream());
+  TORCH_CHECK(rc == 0, "pdt_rope_kv_append_paged_fp8 failed: ", rc);
+}
+
+// attn_decode_paged on an e4m3 cache: attention on float(pool) * scale[row]. Returns (S, C) as attn_decode_paged.
+std::vector<int64_t> attn_decode_paged_fp8(Tensor qkv, Tensor k_pool, Tensor v_pool, Tensor k_scale, Tensor v_scale,
+                                           Tensor block_table, Tensor lens, int64_t heads, int64_t kv_heads,
+                                           double scale, int64_t splits, Tensor out, c10::optional<Tensor> o_part,
+                                           c10::optional<Tensor> ml_part, c10::optional<Tensor> lse) {
+  const Op op("attn_decode_paged_fp8", qkv);
+  const PagedDims d = paged_dims(op, qkv, k_pool, v_pool, block_table, lens, heads, kv_heads, &k_scale, &v_scale);
+  TORCH_CHECK(d.Tn == 1, "attn_decode_paged_fp8: one new token per sequence, got Tn = ", d.Tn);
+  TORCH_CHECK(scale > 0 && splits >= 0, "attn_decode_paged_fp8: scale must be positive and splits >= 0");
+  TORCH_CHECK(out.defined() && out.device() == op.dev && out.scalar_type() == at::kBFloat16 && out.is_contiguous() &&
+                  out.numel() == (int64_t)d.B * d.H * 64 && aligned16(out),
+              "attn_decode_paged_fp8: out must be a contiguous bf16 [B, 1, heads * 64] tensor on ", op.dev);
+  const std::vector<int64_t> geo = attn_decode_geo(d.B, d.Hkv, (int64_t)d.max_pages * 64, splits, d.H / d.Hkv);
+  const int64_t S = geo[0], rows = (int64_t)d.B * d.H;
+  float* lp = opt_f32_ptr(op, "lse", lse, rows);
+  float *op_ptr = nullptr, *ml_ptr = nullptr;
+  if (S > 1) {
+    TORCH_CHECK(has(o_part) && has(ml_part), "attn_decode_paged_fp8: S = ", S, " splits need the o_part / ml_part scratch");
+    for (const Tensor* t : {&*o_part, &*ml_part})
+      TORCH_CHECK(t->device() == op.dev && t->scalar_type() == at::kFloat && t->is_contiguous() && aligned16(*t),
+                  "attn_decode_paged_fp8: the scratch must be contiguous, 16-byte aligned fp32 on ", op.dev);
+    TORCH_CHECK(o_part->numel() >= rows * S * 64 && ml_part->numel() >= rows * S * 2,
+                "attn_decode_paged_fp8: scratch too small for S = ", S, ": o_part ", o_part->numel(), " < ",
+                rows * S * 64, " or ml_part ", ml_part->numel(), " < ", rows * S * 2);
+    op_ptr = o_part->data_ptr<float>();
+    ml_ptr = ml_part->data_ptr<float>();
+  }
+  int rc = pdt_attn_decode_paged_fp8(bf16_ptr(qkv), qkv.stride(0), byte_ptr(k_pool), byte_ptr(v_pool),
+                                     k_scale.data_ptr<float>(), v_scale.data_ptr<float>(), block_table.data_ptr<int>(),
+                                     lens.data_ptr<int>(), op_ptr, ml_ptr, bf16_out(out), lp, d.B, d.H, d.Hkv, d.n_pages,
+                                     d.max_pages, (int)S, (int)geo[1], (float)scale, stream());
+  TORCH_CHECK(rc == 0, "pdt_attn_decode_paged_fp8 failed: ", rc);
   if (S > 1) {
     rc = pdt_attn_decode_combine(op_ptr, ml_ptr, bf16_out(out), lp, d.B, d.H, (int)S, stream());
     TORCH_CHECK(rc == 0, "pdt_attn_decode_combine failed: ", rc);
@@ -3164,6 +3241,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("block_table"), py::arg("lens"), py::arg("heads"), py::arg("kv_heads"), py::arg("scale"),
         py::arg("splits"), py::arg("out"), py::arg("o_part") = py::none(), py::arg("ml_part") = py::none(),
         py::arg("lse") = py::none());
+  m.def("rope_kv_append_paged_fp8", &rope_kv_append_paged_fp8, py::arg("qkv"), py::arg("cos"), py::arg("sin"),
+        py::arg("heads"), py::arg("kv_heads"), py::arg("k_pool"), py::arg("v_pool"), py::arg("k_scale"),
+        py::arg("v_scale"), py::arg("block_table"), py::arg("lens"));
+  m.def("attn_decode_paged_fp8", &attn_decode_paged_fp8, py::arg("qkv"), py::arg("k_pool"), py::arg("v_pool"),
+        py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"), py::arg("lens"), py::arg("heads"),
+        py::arg("kv_heads"), py::arg("scale"), py::arg("splits"), py::arg("out"), py::arg("o_part") = py::none(),
+        py::arg("ml_part") = py::none(), py::arg("lse") = py::none());
   m.def("attn_extend_paged", &attn_extend_paged, py::arg("qkv"), py::arg("k_pool"), py::arg("v_pool"),
         py::arg("block_table"), py::arg("lens"), py::arg("heads"), py::arg("kv_heads"), py::arg("scale"),
         py::arg("splits"), py::arg("out"), py::arg("o_part") = py::none(), py::arg("ml_part") = py::none(),

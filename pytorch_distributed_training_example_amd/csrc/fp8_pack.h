@@ -28,6 +28,11 @@ __device__ __forceinline__ uint32_t pack4_fp8(float a, float b, float c, float d
   return (uint32_t)w;
 }
 
+// The row-wise rule of quantize_rows_e4m3 (kernels/gemm_skinny_w8.hip, kernels/attn_paged_fp8.hip), fp32: the
+// stored scale and the factor the row is multiplied by before pack4_fp8, from the row's amax = max |x|.
+__device__ __forceinline__ float e4m3_row_scale(float amax) { return amax > 0.f ? amax * (1.0f / kE4M3Max) : 1.0f; }
+__device__ __forceinline__ float e4m3_row_inv(float amax) { return amax > 0.f ? kE4M3Max / amax : 0.f; }
+
 // Byte j of each of 4 words -> one word (byte i from word i): a 4 x 4 byte transpose column.
 __device__ __forceinline__ uint32_t byte_col(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, int j) {
   const int sh = 8 * j;

@@ -305,8 +305,8 @@ PDT_NO_PACKED_F32 __global__ __launch_bounds__(256) void quant_rows_e4m3_kernel(
     const int other = __builtin_amdgcn_ds_bpermute((lane ^ (1 << b)) << 2, __builtin_bit_cast(int, amax));
     amax = __builtin_fmaxf(amax, __builtin_bit_cast(float, other));
   }
-  const float inv = amax > 0.f ? kE4M3Max / amax : 0.f;
-  if (lane == 0) scale[n] = amax > 0.f ? amax * (1.0f / kE4M3Max) : 1.0f;
+  const float inv = e4m3_row_inv(amax);
+  if (lane == 0) scale[n] = e4m3_row_scale(amax);
   uint8_t* out = wq + (int64_t)n * K;
   for (int k = 8 * lane; k < K; k += 512) {
     float v[8];

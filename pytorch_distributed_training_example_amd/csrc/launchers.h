@@ -74,6 +74,15 @@ int pdt_attn_decode_paged(const uint16_t* qkv, int64_t q_sb, const uint16_t* k_p
                           const int* block_table, const int* lens, float* o_part, float* ml_part, uint16_t* out,
                           float* lse, int B, int H, int Hkv, int n_pages, int max_pages, int S, int C, float scale,
                           hipStream_t s);
+// kernels/attn_paged_fp8.hip: the two above on an e4m3 cache. k_pool, v_pool [n_pages, Hkv, 64, 64] e4m3fn bytes,
+// k_scale, v_scale [n_pages, Hkv, 64] fp32: one scale per stored row (quantize_rows_e4m3's rule on the bf16 row).
+int pdt_rope_kv_append_paged_fp8(uint16_t* qkv, const float* cos, const float* sin, uint8_t* k_pool, uint8_t* v_pool,
+                                 float* k_scale, float* v_scale, const int* block_table, const int* lens, int B, int Tn,
+                                 int H, int Hkv, int n_pages, int max_pages, int Tmax, hipStream_t s);
+int pdt_attn_decode_paged_fp8(const uint16_t* qkv, int64_t q_sb, const uint8_t* k_pool, const uint8_t* v_pool,
+                              const float* k_scale, const float* v_scale, const int* block_table, const int* lens,
+                              float* o_part, float* ml_part, uint16_t* out, float* lse, int B, int H, int Hkv,
+                              int n_pages, int max_pages, int S, int C, float scale, hipStream_t s);
 // kernels/attn_paged_extend.hip: pdt_attn_extend on a paged cache; geo4 = pdt_attn_extend_geo at 64 max_pages
 int pdt_attn_extend_paged(const uint16_t* qkv, int64_t q_sb, int64_t q_st, const uint16_t* k_pool,
                           const uint16_t* v_pool, const int* block_table, const int* lens, float* o_part,

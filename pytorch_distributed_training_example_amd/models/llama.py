@@ -36,14 +36,14 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..config import SW
-from ..ops.attention import (attention_decode, attention_decode_paged, attention_extend, attention_extend_paged,
-                             attention_qkv)
+from ..ops.attention import (attention_decode, attention_decode_paged, attention_decode_paged_fp8, attention_extend,
+                             attention_extend_paged, attention_qkv)
 from ..ops.cross_entropy import cross_entropy
 from ..ops.fp8 import Fp8Act, add_rms_norm_fp8, fp8_input_slot, fp8_linear, fp8_ok, fp8_swiglu_mlp, rms_fp8_ok
 from ..ops.kv_cache import PAGE, KVCache, PagedKVCache
 from ..ops.linear import SKINNY_MAX_ROWS, linear, linear_skinny, linear_skinny_w8, quantize_rows_e4m3
 from ..ops.rmsnorm import RMSNorm, add_rms_norm
-from ..ops.rope import RotaryTable, rope_append_, rope_append_paged_, rope_qkv_
+from ..ops.rope import RotaryTable, rope_append_, rope_append_paged_, rope_append_paged_fp8_, rope_qkv_
 from ..ops.swiglu import swiglu
 from .transformer import init_weights
 
@@ -164,6 +164,8 @@ class LlamaAttention(nn.Module):
                 cache.bounds[s] > 0 for s in (range(cache.slots) if slots is None else slots)):
             raise ValueError(f"{Tn} new tokens onto paged slots that may hold up to {cache.bound} positions: chunked "
                              "prefill is not what prefill does (prefill empty slots, then extend() or decode_step())")
+        if cache.fp8:
+            return self._forward_paged_fp8(x, rope, cache, layer, table, lens, slots)
         cache.require(Tn, rope.cos.shape[0], slots)
         qkv = _linear(x, self.c_attn)
         qkv = rope_append_paged_(qkv, rope.cos, rope.sin, self.heads, self.kv_heads, cache.k[layer], cache.v[layer],
@@ -176,6 +178,26 @@ class LlamaAttention(nn.Module):
         else:
             y = attention_decode_paged(qkv, cache.k[layer], cache.v[layer], table, lens, self.heads, self.kv_heads,
                                        cache=cache)
+        return _linear(y, self.c_proj)
+
+    def _forward_paged_fp8(self, x, rope, cache: PagedKVCache, layer: int, table, lens, slots):
+        """``_forward_paged`` on an e4m3 cache: the quantising append, then the causal flash forward on the bf16
+        ``qkv`` (Tn > 1: a prefill of empty slots, which never reads the cache) or the e4m3 decode kernel
+        (Tn == 1). The multi-token append on such a cache is refused before any launch."""
+        Tn = x.shape[1]
+        if Tn > 1 and cache.extending:
+            raise NotImplementedError(f"extend of {Tn} tokens on an fp8 paged cache is out of scope: the e4m3 form of "
+                                      "the multi-token append kernel is not built (prefill empty slots whole, then "
+                                      "decode_step, or use a bf16 paged cache)")
+        cache.require(Tn, rope.cos.shape[0], slots)
+        qkv = _linear(x, self.c_attn)
+        qkv = rope_append_paged_fp8_(qkv, rope.cos, rope.sin, self.heads, self.kv_heads, cache.k[layer], cache.v[layer],
+                                     cache.k_scale[layer], cache.v_scale[layer], table, lens)
+        if Tn > 1:
+            y = attention_qkv(qkv, self.heads, causal=True, kv_heads=self.kv_heads)
+        else:
+            y = attention_decode_paged_fp8(qkv, cache.k[layer], cache.v[layer], cache.k_scale[layer],
+                                           cache.v_scale[layer], table, lens, self.heads, self.kv_heads, cache=cache)
         return _linear(y, self.c_proj)
 
 
@@ -308,12 +330,18 @@ class Llama(nn.Module):
         w = self.lm_head.weight
         return KVCache(self.cfg.n_layer, batch, self.cfg.kv_heads, capacity or self.cfg.block_size, w.device, w.dtype)
 
-    def new_paged_cache(self, slots: int, n_pages: int, max_pages_per_seq: int | None = None) -> PagedKVCache:
+    def new_paged_cache(self, slots: int, n_pages: int, max_pages_per_seq: int | None = None,
+                        kv_dtype: str | None = None) -> PagedKVCache:
         """A paged KV cache of ``slots`` sequence slots on a pool of ``n_pages`` pages of 64 positions per layer;
-        a slot may hold up to ``max_pages_per_seq`` pages (default: what ``block_size`` positions need)."""
+        a slot may hold up to ``max_pages_per_seq`` pages (default: what ``block_size`` positions need). ``kv_dtype``
+        None keeps the model's dtype; "fp8" stores e4m3 rows with one fp32 scale each (half the pool bytes per
+        token and a bit: 66 against 128 per K or V row)."""
+        if kv_dtype not in (None, "fp8"):
+            raise ValueError(f'new_paged_cache: kv_dtype is None or "fp8", got {kv_dtype!r}')
         w = self.lm_head.weight
         cache = PagedKVCache(self.cfg.n_layer, slots, self.cfg.kv_heads, n_pages,
-                             max_pages_per_seq or -(-self.cfg.block_size // PAGE), w.device, w.dtype)
+                             max_pages_per_seq or -(-self.cfg.block_size // PAGE), w.device,
+                             torch.float8_e4m3fn if kv_dtype == "fp8" else w.dtype)
         cache.table_len = self.cfg.block_size
         return cache
 
@@ -515,7 +543,8 @@ class Llama(nn.Module):
     @torch.no_grad()
     def generate(self, idx: torch.Tensor, max_new_tokens: int, temperature: float = 0.0, top_k: int | None = None,
                  eos_token: int | None = None, generator: torch.Generator | None = None, prompt_lens=None,
-                 return_logits: bool = False, prefill_chunk: int | None = None, paged: bool = False):
+                 return_logits: bool = False, prefill_chunk: int | None = None, paged: bool = False,
+                 kv_dtype: str | None = None):
         """Sample ``max_new_tokens`` tokens after the prompts ``idx`` [B, T0] (right-padded when
         ``prompt_lens`` is given); returns them as [B, max_new_tokens] on the device, with ``return_logits``
         also the logits [B, max_new_tokens, V] each was drawn from. Greedy at ``temperature`` 0, otherwise
@@ -525,8 +554,15 @@ class Llama(nn.Module):
         positions (``prefill`` of the first, ``extend`` of the rest), which bounds the activation memory of a
         long prompt by the slice. With ``paged`` the same loop runs on a ``PagedKVCache`` sized for the batch,
         which reserves pages before the prefill (with ``prefill_chunk``: before every slice) and before every
-        step. Runs in ``eval()`` and restores the mode."""
+        step; ``kv_dtype="fp8"`` makes that cache an e4m3 one (``new_paged_cache``), which takes the prompt whole:
+        with ``prefill_chunk`` it is refused. Runs in ``eval()`` and restores the mode."""
         B, T0 = idx.shape
+        if kv_dtype is not None and not paged:
+            raise NotImplementedError(f"generate: kv_dtype = {kv_dtype!r} needs paged=True; an fp8 contiguous KVCache is "
+                                      "out of scope")
+        if kv_dtype is not None and prefill_chunk is not None:
+            raise NotImplementedError("generate: prefill_chunk on an fp8 paged cache is out of scope (it needs the e4m3 "
+                                      "form of the multi-token append kernel)")
         if max_new_tokens < 1:
             raise ValueError(f"max_new_tokens must be positive, got {max_new_tokens}")
         if T0 + max_new_tokens > self.cfg.block_size:
@@ -537,7 +573,7 @@ class Llama(nn.Module):
         try:
             if paged:
                 per_seq = -(-(T0 + max_new_tokens) // PAGE)
-                cache = self.new_paged_cache(B, B * per_seq, per_seq)
+                cache = self.new_paged_cache(B, B * per_seq, per_seq, kv_dtype=kv_dtype)
                 for s in range(B):
                     cache.admit(s)
                 if prefill_chunk is None:

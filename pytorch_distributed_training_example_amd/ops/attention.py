@@ -316,6 +316,68 @@ def attention_decode_paged(qkv: torch.Tensor, k_pool: torch.Tensor, v_pool: torc
     return (out, lse) if return_lse else out
 
 
+PAGED_FP8_STATS = {"native_calls": 0, "geo": None}  # launches of the e4m3 paged decode kernel, its last (S, C)
+
+
+def dequantize_pages(pool: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """An e4m3 pool [n_pages, Hkv, 64, 64] and its scale pool [n_pages, Hkv, 64] as fp32 rows ``float(q) * scale``.
+    Rows nobody wrote may hold NaN bytes or scales; the references only read them behind a mask."""
+    return pool.float() * scale.float()[..., None]
+
+
+def attention_decode_paged_fp8(qkv: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_scale: torch.Tensor,
+                               v_scale: torch.Tensor, block_table: torch.Tensor, lens: torch.Tensor, heads: int,
+                               kv_heads: int | None = None, scale: float | None = None, splits: int | None = None,
+                               cache=None, return_lse: bool = False):
+    """``attention_decode_paged`` on an e4m3 cache, a sibling of it, not an argument of it, so that a bf16 call
+    cannot pick up scales by accident: ``k_pool`` / ``v_pool`` [n_pages, Hkv, 64, 64] float8_e4m3fn and ``k_scale`` /
+    ``v_scale`` [n_pages, Hkv, 64] fp32, one scale per stored row (``rope_append_paged_fp8_`` writes both). The
+    result is attention on the dequantised rows ``float(k) * k_scale[row]``, ``float(v) * v_scale[row]`` of keys
+    0 .. lens[b]; everything else is ``attention_decode_paged``'s contract, stale rows and stale scales (NaN
+    included) and bad page ids too. Returns [B, 1, H·64] (and the LSE [B, H] with ``return_lse``). Inference only.
+
+    bf16 ``qkv`` on the GPU runs csrc/kernels/attn_paged_fp8.hip; CPU, fp32 and ``PDT_DISABLE_NATIVE=1`` gather the
+    pages and scales, dequantise in fp32 and take the PyTorch reference."""
+    kv_heads = heads if kv_heads is None else kv_heads
+    if kv_heads <= 0 or heads % kv_heads != 0:
+        raise ValueError(f"attention_decode_paged_fp8: heads = {heads} is not a positive multiple of kv_heads = {kv_heads}")
+    if torch.is_grad_enabled() and qkv.requires_grad:
+        raise RuntimeError("attention_decode_paged_fp8: inference only (run it under torch.no_grad())")
+    if qkv.dim() != 3 or qkv.shape[1] != 1 or qkv.shape[2] % (heads + 2 * kv_heads) != 0:
+        raise ValueError(f"attention_decode_paged_fp8: qkv {tuple(qkv.shape)} is not [B, 1, (heads + 2·kv_heads)·Dh]")
+    dh = qkv.shape[2] // (heads + 2 * kv_heads)
+    scale = scale if scale is not None else 1.0 / math.sqrt(dh)
+    if use_native(qkv) and qkv.dtype == torch.bfloat16:  # dtypes, head dim 64 and the layouts: the binding's checks
+        B = qkv.shape[0]
+        out = torch.empty(B, 1, heads * dh, device=qkv.device, dtype=qkv.dtype)
+        lse = torch.empty(B, heads, device=qkv.device, dtype=torch.float32) if return_lse else None
+        o_part = ml_part = None
+        if block_table.dim() == 2 and block_table.shape[1] > 0 and dh == 64:
+            S, _ = attention_decode_geo(B, kv_heads, PAGE * block_table.shape[1], splits, heads // kv_heads)
+            if S > 1:
+                if cache is not None and B <= cache.batch:
+                    o_part, ml_part = cache.scratch(heads, S)
+                else:
+                    o_part = torch.empty(B, heads, S, 64, device=qkv.device, dtype=torch.float32)
+                    ml_part = torch.empty(B, heads, S, 2, device=qkv.device, dtype=torch.float32)
+        geo = native().attn_decode_paged_fp8(qkv, k_pool, v_pool, k_scale, v_scale, block_table, lens, heads, kv_heads,
+                                             scale, int(splits or 0), out, o_part, ml_part, lse)
+        PAGED_FP8_STATS["native_calls"] += 1
+        PAGED_FP8_STATS["geo"] = (int(geo[0]), int(geo[1]))
+        return (out, lse) if return_lse else out
+    from .rope import gather_pages
+    if k_pool.dtype != torch.float8_e4m3fn or k_pool.dim() != 4 or k_pool.shape != v_pool.shape \
+            or k_scale.shape != k_pool.shape[:3] or v_scale.shape != k_pool.shape[:3] or block_table.dim() != 2 \
+            or block_table.shape[0] != qkv.shape[0]:
+        raise ValueError(f"attention_decode_paged_fp8: pools {tuple(k_pool.shape)}, {tuple(v_pool.shape)} are not e4m3 "
+                         f"[n_pages, kv_heads, 64, Dh] with scale pools {tuple(k_scale.shape)}, {tuple(v_scale.shape)} "
+                         f"[n_pages, kv_heads, 64], or the table {tuple(block_table.shape)} is not [B, max_pages]")
+    out, lse = _decode_reference(qkv, gather_pages(dequantize_pages(k_pool, k_scale), block_table),
+                                 gather_pages(dequantize_pages(v_pool, v_scale), block_table), lens, heads, kv_heads,
+                                 scale)
+    return (out, lse) if return_lse else out
+
+
 EXTEND_STATS = {"native_calls": 0, "geo": None}  # launches of the append kernel and its last (S, C, NB, NT)
 
 

@@ -27,6 +27,9 @@ class KVCache:
         if min(n_layer, batch, kv_heads, capacity) <= 0:
             raise ValueError(f"KVCache: n_layer, batch, kv_heads and capacity must be positive, got "
                              f"{(n_layer, batch, kv_heads, capacity)}")
+        if dtype == torch.float8_e4m3fn:
+            raise NotImplementedError("KVCache: an fp8 contiguous cache is out of scope; the e4m3 cache is the paged one "
+                                      "(PagedKVCache(..., dtype=torch.float8_e4m3fn))")
         self.n_layer, self.batch, self.kv_heads, self.capacity = n_layer, batch, kv_heads, capacity
         self.device, self.dtype = torch.device(device), dtype
         shape = (batch, kv_heads, capacity, HEAD_DIM)
@@ -110,7 +113,13 @@ class PagedKVCache:
     entry changed (in steady decoding once per 64 steps and slot); it raises before it changes or launches
     anything when the pool, ``max_pages_per_seq`` or the rotary table (``table_len``) cannot cover the step.
     Nothing on the step path reads the device, so a captured decode step replays with ``reserve`` called
-    between the replays. Freed pages are not cleared: the kernels never read a row at or past ``lens``."""
+    between the replays. Freed pages are not cleared: the kernels never read a row at or past ``lens``.
+
+    With ``dtype=torch.float8_e4m3fn`` (csrc/kernels/attn_paged_fp8.hip) the pools hold one byte per element, a key
+    row is one 64-byte line, and ``k_scale[l]`` / ``v_scale[l]`` (fp32 [n_pages, Hkv, 64]) hold one scale per stored
+    (position, K/V head) row: the row is ``quantize_rows_e4m3``'s of the row the bf16 cache would store, and the
+    attention runs on ``float(k) * k_scale[row]``, ``float(v) * v_scale[row]``. Table, ``lens``, ``active``, the
+    allocator and the scratch mean what they mean above; freed pages and their scales are not cleared either."""
 
     def __init__(self, n_layer: int, slots: int, kv_heads: int, n_pages: int, max_pages_per_seq: int, device,
                  dtype=torch.bfloat16):
@@ -123,6 +132,10 @@ class PagedKVCache:
         shape = (n_pages, kv_heads, PAGE, HEAD_DIM)
         self.k = [torch.zeros(shape, device=self.device, dtype=dtype) for _ in range(n_layer)]
         self.v = [torch.zeros(shape, device=self.device, dtype=dtype) for _ in range(n_layer)]
+        self.k_scale = self.v_scale = None
+        if self.fp8:
+            self.k_scale = [torch.zeros(shape[:3], device=self.device, dtype=torch.float32) for _ in range(n_layer)]
+            self.v_scale = [torch.zeros(shape[:3], device=self.device, dtype=torch.float32) for _ in range(n_layer)]
         self.block_table = torch.full((slots, max_pages_per_seq), -1, device=self.device, dtype=torch.int32)
         self.lens = torch.zeros(slots, device=self.device, dtype=torch.int32)
         self.active = torch.zeros(slots, device=self.device, dtype=torch.int32)
@@ -137,6 +150,11 @@ class PagedKVCache:
         self.extending = False  # set by Llama.extend around its forward: Tn > 1 then runs the paged append kernel
 
     # ------------------------------------------------------------------ what the contiguous cache also answers
+    @property
+    def fp8(self) -> bool:
+        """An e4m3 cache: byte pools with ``k_scale`` / ``v_scale`` beside them."""
+        return self.dtype == torch.float8_e4m3fn
+
     @property
     def batch(self) -> int:
         return self.slots

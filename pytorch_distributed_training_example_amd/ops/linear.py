@@ -290,6 +290,12 @@ def quantize_rows_e4m3(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         if wc.data_ptr() % 16 == 0:
             wq, scale = native().quantize_rows_e4m3(wc)
             return wq, scale
+    return quantize_rows_e4m3_reference(w)
+
+
+def quantize_rows_e4m3_reference(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``quantize_rows_e4m3``'s formula in torch on ``w`` [N, K] (any float dtype, taken to fp32), without its checks
+    and without a host read: what the reference paths of the e4m3 KV cache apply to the rows they store."""
     wf = w.float()
     amax = wf.abs().amax(1)
     zero = amax == 0

@@ -227,3 +227,58 @@ def rope_append_paged_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, 
     for pool, c in ((k_pool, kc), (v_pool, vc)):
         pool[tbl[ok]] = c.view(B, kv_heads, mp, PAGE, dh).permute(0, 2, 1, 3, 4)[ok]
     return qkv
+
+
+# ----------------------------------------------------------------------------- the same on an e4m3 paged cache
+APPEND_PAGED_FP8_STATS = {"native_calls": 0}  # launches of the quantising paged append kernel
+
+
+def rope_append_paged_fp8_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, heads: int, kv_heads: int | None,
+                           k_pool: torch.Tensor, v_pool: torch.Tensor, k_scale: torch.Tensor, v_scale: torch.Tensor,
+                           block_table: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+    """``rope_append_paged_`` with a quantising store (csrc/kernels/attn_paged_fp8.hip): ``k_pool`` / ``v_pool``
+    [n_pages, kv_heads, 64, 64] float8_e4m3fn and ``k_scale`` / ``v_scale`` [n_pages, kv_heads, 64] fp32. ``qkv`` is
+    rotated in place exactly as ``rope_append_paged_`` rotates it; the row that call would store (K: the rotated
+    row after its rounding to qkv's dtype) goes to the pools as ``quantize_rows_e4m3`` of it, bytes and scale. Rows
+    out of range behave as there. Returns ``qkv``; ``lens`` is not advanced. Inference only.
+
+    bf16 GPU tensors run the kernel; CPU, fp32 and ``PDT_DISABLE_NATIVE=1`` pass the bf16 reference's rows through
+    the torch form of ``quantize_rows_e4m3``."""
+    kv_heads = heads if kv_heads is None else kv_heads
+    if kv_heads <= 0 or heads % kv_heads != 0:
+        raise ValueError(f"rope_append_paged_fp8_: heads = {heads} is not a positive multiple of kv_heads = {kv_heads}")
+    if torch.is_grad_enabled() and qkv.requires_grad:
+        raise RuntimeError("rope_append_paged_fp8_: inference only (run it under torch.no_grad())")
+    if qkv.dim() != 3 or qkv.shape[-1] % (heads + 2 * kv_heads) != 0 or not qkv.is_contiguous():
+        raise ValueError(f"rope_append_paged_fp8_: qkv {tuple(qkv.shape)} is not a contiguous [B, Tn, (heads + "
+                         f"2·kv_heads)·Dh] with heads = {heads}, kv_heads = {kv_heads}")
+    if use_native(qkv) and qkv.dtype == torch.bfloat16:  # dtypes, layouts, table, lens: the binding's checks
+        native().rope_kv_append_paged_fp8(qkv, cos, sin, heads, kv_heads, k_pool, v_pool, k_scale, v_scale,
+                                          block_table, lens)
+        APPEND_PAGED_FP8_STATS["native_calls"] += 1
+        return qkv
+    from .linear import quantize_rows_e4m3_reference
+    dh = qkv.shape[-1] // (heads + 2 * kv_heads)
+    if k_pool.dtype != torch.float8_e4m3fn or k_pool.shape != v_pool.shape or k_pool.dim() != 4 \
+            or tuple(k_pool.shape[1:]) != (kv_heads, PAGE, dh) or k_scale.shape != k_pool.shape[:3] \
+            or v_scale.shape != k_pool.shape[:3] or block_table.dim() != 2 or block_table.shape[0] != qkv.shape[0]:
+        raise ValueError(f"rope_append_paged_fp8_: pools {tuple(k_pool.shape)}, {tuple(v_pool.shape)} are not e4m3 "
+                         f"[n_pages, {kv_heads}, {PAGE}, {dh}] with scale pools [n_pages, {kv_heads}, {PAGE}], or the "
+                         f"table {tuple(block_table.shape)} is not [{qkv.shape[0]}, max_pages]")
+    # the contiguous reference into an empty cache of qkv's dtype, then the written rows quantised into their pages
+    B, Tn = qkv.shape[0], qkv.shape[1]
+    cap = block_table.shape[1] * PAGE
+    kc = torch.zeros(B, kv_heads, cap, dh, dtype=qkv.dtype, device=qkv.device)
+    vc = torch.zeros_like(kc)
+    _append_reference_(qkv, cos, sin, heads, kv_heads, kc, vc, lens)
+    pos = torch.arange(cap, device=qkv.device)[None, :].expand(B, cap)
+    t = pos - lens.long()[:, None]
+    page = block_table.long().gather(1, pos >> 6)
+    take = (t >= 0) & (t < Tn) & (pos < min(cap, cos.shape[0])) & (page >= 0) & (page < k_pool.shape[0])
+    bi, ji = take.nonzero(as_tuple=True)
+    pg, row = page[bi, ji], ji & (PAGE - 1)
+    for pool, scale, c in ((k_pool, k_scale, kc), (v_pool, v_scale, vc)):
+        q, s = quantize_rows_e4m3_reference(c[bi, :, ji].reshape(-1, dh))
+        pool.view(torch.uint8)[pg, :, row] = q.view(torch.uint8).view(-1, kv_heads, dh)
+        scale[pg, :, row] = s.view(-1, kv_heads)
+    return qkv
