@@ -92,9 +92,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--sample-tokens", type=int, default=0, metavar="N",
                    help="llama_* only: after the last epoch rank 0 generates N tokens on the KV cache and prints "
                         "'Sample: [ids]' (with --resume and a finished checkpoint: sample it without training)")
-    p.add_argument("--sample-weights", choices=["bf16", "fp8"], default="bf16",
+    p.add_argument("--sample-weights", choices=["bf16", "fp8", "int4"], default="bf16",
                    help="llama_* only, with --sample-tokens: fp8 quantises the Linear weights row-wise to e4m3 before "
-                        "sampling (Llama.quantize_decode_weights: decode steps then stream one byte per weight)")
+                        "sampling (Llama.quantize_decode_weights: decode steps then stream one byte per weight); int4 "
+                        "quantises them to 4 bits with one scale per 128 inputs (half a byte per weight)")
     p.add_argument("--sample-cache", choices=["contiguous", "paged", "paged-fp8"], default="contiguous",
                    help="llama_* only, with --sample-tokens: paged generates on a PagedKVCache (pages of 64 positions "
                         "found through a block table) instead of one contiguous slab per sequence; paged-fp8 on one "
@@ -369,8 +370,8 @@ def run(rank: int, world: int, args) -> dict:
     if getattr(args, "sample_tokens", 0) and rank == 0:
         gen = torch.Generator(device=device).manual_seed(args.seed)
         prompt = torch.tensor([parse_prompt(args.sample_prompt)], device=device)
-        if getattr(args, "sample_weights", "bf16") == "fp8":
-            model.quantize_decode_weights()
+        if getattr(args, "sample_weights", "bf16") != "bf16":
+            model.quantize_decode_weights(args.sample_weights)
         sample_cache = getattr(args, "sample_cache", "contiguous")
         toks = model.generate(prompt, args.sample_tokens, temperature=args.sample_temperature,
                               top_k=args.sample_top_k, generator=gen, paged=sample_cache != "contiguous",

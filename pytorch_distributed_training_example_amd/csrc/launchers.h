@@ -313,6 +313,13 @@ int pdt_gemm_skinny_w8_geo(int M, int N, int K, int mode, int splits, int* geo3)
 int pdt_gemm_skinny_w8(const uint16_t* x, const uint8_t* wq, const float* scale, uint16_t* y, float* ws, int M, int N,
                        int K, int mode, int S, int FT, int NT, hipStream_t s);
 
+// kernels/gemm_skinny_w4.hip: the same on int4 weights (packed nibbles, wq [N, K / 2]) with one fp32 scale per
+// (128 consecutive k, output feature), scale [K / 128, N] (W4A16), and the group-wise quantiser that packs them
+int pdt_quant_groups_int4(const uint16_t* w, uint8_t* wq, float* scale, int N, int K, hipStream_t s);
+int pdt_gemm_skinny_w4_geo(int M, int N, int K, int mode, int splits, int* geo3);
+int pdt_gemm_skinny_w4(const uint16_t* x, const uint8_t* wq, const float* scale, uint16_t* y, float* ws, int M, int N,
+                       int K, int mode, int S, int FT, int NT, hipStream_t s);
+
 // kernels/layernorm.hip
 int64_t pdt_ln_workspace_floats(int64_t N, int D);
 int pdt_ln_fwd(const void* x, const void* res, int dtype, const float* w, const float* b, void* y, void* sum_out,

@@ -25,6 +25,9 @@ Weight-only 8-bit decoding: ``Llama.quantize_decode_weights()`` quantises every 
 row-wise to e4m3 (ops/linear.py ``quantize_rows_e4m3``); calls on at most 64 rows in ``eval()`` under
 ``no_grad`` then run the W8A16 skinny GEMM (``linear_skinny_w8``), whatever ``PDT_DECODE_GEMM`` says. More rows
 (a long prefill) and training keep the bf16 weights, which stay in place; ``drop_decode_weights()`` undoes it.
+``quantize_decode_weights("int4")`` stores symmetric int4 with one fp32 scale per 128 inputs instead
+(``quantize_groups_int4``, a quarter of the bf16 bytes plus the scales) and the same calls run the W4A16 skinny
+GEMM (``linear_skinny_w4``); one call replaces the other's copies.
 """
 from __future__ import annotations
 
@@ -41,7 +44,8 @@ from ..ops.attention import (attention_decode, attention_decode_paged, attention
 from ..ops.cross_entropy import cross_entropy
 from ..ops.fp8 import Fp8Act, add_rms_norm_fp8, fp8_input_slot, fp8_linear, fp8_ok, fp8_swiglu_mlp, rms_fp8_ok
 from ..ops.kv_cache import PAGE, KVCache, PagedKVCache
-from ..ops.linear import SKINNY_MAX_ROWS, linear, linear_skinny, linear_skinny_w8, quantize_rows_e4m3
+from ..ops.linear import (SKINNY_MAX_ROWS, linear, linear_skinny, linear_skinny_w4, linear_skinny_w8,
+                          quantize_groups_int4, quantize_rows_e4m3)
 from ..ops.rmsnorm import RMSNorm, add_rms_norm
 from ..ops.rope import RotaryTable, rope_append_, rope_append_paged_, rope_append_paged_fp8_, rope_qkv_
 from ..ops.swiglu import swiglu
@@ -79,30 +83,41 @@ def _skinny(x, training: bool) -> bool:
             and 0 < x.numel() // x.shape[-1] <= SKINNY_MAX_ROWS)
 
 
-def _w8(x, mod: nn.Linear):
-    """``mod``'s (wq, scale) when ``quantize_decode_weights`` left them there and this call is decode-time
-    (``eval()``, no autograd, at most 64 rows); else None. Weights updated in place since then are refused."""
-    q = getattr(mod, "_w8", None)
+def _w8(x, mod: nn.Linear, attr: str = "_w8"):
+    """``mod``'s (wq, scale) when ``quantize_decode_weights`` left them there (``attr``: ``_w8`` e4m3, ``_w4`` int4)
+    and this call is decode-time (``eval()``, no autograd, at most 64 rows); else None. Weights updated in place
+    since then are refused."""
+    q = getattr(mod, attr, None)
     if (q is None or mod.training or torch.is_grad_enabled() or not isinstance(x, torch.Tensor)
             or not 0 < x.numel() // x.shape[-1] <= SKINNY_MAX_ROWS):
         return None
     if q[2] != mod.weight._version:
         raise RuntimeError("a Linear's weight changed in place after quantize_decode_weights(): its e4m3 copy is "
-                           "stale; call quantize_decode_weights() again (or drop_decode_weights())")
+                           "stale; call quantize_decode_weights() again (or drop_decode_weights())"
+                           if attr == "_w8" else
+                           "a Linear's weight changed in place after quantize_decode_weights(\"int4\"): its int4 copy "
+                           "is stale; call quantize_decode_weights(\"int4\") again (or drop_decode_weights())")
     return q[0], q[1]
+
+
+def _w4(x, mod: nn.Linear):
+    return _w8(x, mod, "_w4")
 
 
 def _linear(x, mod: nn.Linear) -> torch.Tensor:
     """``mod``'s bias-free GEMM: fp8 when ``enable_fp8`` tagged it and the shape is served (ops/fp8.py; ``x``
     may then be an ``Fp8Act``, already e4m3 from ``add_rms_norm_fp8``), else bf16 (ops/linear.py); decode-time
-    rows on the W8A16 skinny GEMM after ``quantize_decode_weights()``, else under ``PDT_DECODE_GEMM=1`` on the
-    bf16 skinny GEMM."""
+    rows on the W8A16 (W4A16) skinny GEMM after ``quantize_decode_weights()`` (``("int4")``), else under
+    ``PDT_DECODE_GEMM=1`` on the bf16 skinny GEMM."""
     t = _fp8_tag(mod)
     if t is not None and (isinstance(x, Fp8Act) or fp8_ok(x, mod.weight)):
         return fp8_linear(x, mod.weight, None, t[0], t[1])
     q = _w8(x, mod)
     if q is not None:
         return linear_skinny_w8(x, q[0], q[1])
+    q = _w4(x, mod)
+    if q is not None:
+        return linear_skinny_w4(x, q[0], q[1])
     if _skinny(x, mod.training):
         return linear_skinny(x, mod.weight)
     return linear(x, mod.weight)
@@ -215,6 +230,9 @@ class LlamaMLP(nn.Module):
         q = _w8(x, self.c_fc)
         if q is not None:  # as below, on the e4m3 weights
             return _linear(linear_skinny_w8(x, q[0], q[1], swiglu=True), self.c_proj)
+        q = _w4(x, self.c_fc)
+        if q is not None:  # and on the int4 weights
+            return _linear(linear_skinny_w4(x, q[0], q[1], swiglu=True), self.c_proj)
         if _skinny(x, self.c_fc.training):  # c_fc with SwiGLU in the GEMM's epilogue: no [rows, 2F] round trip
             return _linear(linear_skinny(x, self.c_fc.weight, swiglu=True), self.c_proj)
         return _linear(swiglu(_linear(x, self.c_fc)), self.c_proj)
@@ -285,6 +303,9 @@ class Llama(nn.Module):
         q = _w8(x, self.lm_head)
         if q is not None:
             return linear_skinny_w8(x, q[0], q[1])
+        q = _w4(x, self.lm_head)
+        if q is not None:
+            return linear_skinny_w4(x, q[0], q[1])
         if _skinny(x, self.training):
             return linear_skinny(x, self.lm_head.weight)
         return linear(x, self.lm_head.weight)
@@ -307,20 +328,28 @@ class Llama(nn.Module):
         yield self.lm_head
 
     @torch.no_grad()
-    def quantize_decode_weights(self) -> "Llama":
+    def quantize_decode_weights(self, dtype: str = "fp8") -> "Llama":
         """Quantise every block Linear and the LM head row-wise to e4m3 for decode-time calls (at most 64 rows,
         ``eval()``, no autograd): each module gets ``_w8 = (wq, scale, weight._version)`` as a plain attribute,
         not a parameter or buffer, so ``state_dict()`` is unchanged and the bf16 weights stay for everything
-        else. Call it again after the weights change."""
+        else. ``dtype="int4"``: group-wise int4 instead (one fp32 scale per 128 inputs), kept as ``_w4`` in the
+        same form. Either call removes what the other left. Call it again after the weights change."""
+        if dtype not in ("fp8", "int4"):
+            raise ValueError(f'quantize_decode_weights: dtype is "fp8" or "int4", got {dtype!r}')
+        self.drop_decode_weights()
         for mod in self._decode_linears():
-            wq, scale = quantize_rows_e4m3(mod.weight.detach().to(torch.bfloat16))
-            mod._w8 = (wq, scale, mod.weight._version)
+            w = mod.weight.detach().to(torch.bfloat16)
+            if dtype == "fp8":
+                mod._w8 = (*quantize_rows_e4m3(w), mod.weight._version)
+            else:
+                mod._w4 = (*quantize_groups_int4(w), mod.weight._version)
         return self
 
     def drop_decode_weights(self) -> "Llama":
         for mod in self._decode_linears():
-            if hasattr(mod, "_w8"):
-                del mod._w8
+            for attr in ("_w8", "_w4"):
+                if hasattr(mod, attr):
+                    delattr(mod, attr)
         return self
 
     # ------------------------------------------------------------------ generation on a KV cache

@@ -20,7 +20,10 @@ Inference on at most 64 rows (a decode step, a short extend) has a kernel of its
 with SwiGLU applied to ``c_fc``'s packed gate/up output in the same launch. The Llama decoder uses it under
 ``PDT_DECODE_GEMM=1`` (default 0). ``quantize_rows_e4m3`` + ``linear_skinny_w8`` are the same Linears on weights
 stored as e4m3 bytes with one fp32 scale per output feature (csrc/kernels/gemm_skinny_w8.hip): half the bytes to
-stream; ``Llama.quantize_decode_weights()`` opts a model in.
+stream; ``Llama.quantize_decode_weights()`` opts a model in. ``quantize_groups_int4`` + ``linear_skinny_w4`` store
+symmetric int4 with one fp32 scale per 128 inputs in a layout packed for the kernel
+(csrc/kernels/gemm_skinny_w4.hip; ``pack_int4`` defines it): a quarter of the bytes plus the scales;
+``Llama.quantize_decode_weights("int4")``.
 """
 from __future__ import annotations
 
@@ -233,8 +236,9 @@ def linear_gelu(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
 
 
 # ---------------------------------------------------------------------------- decode-time Linears (M <= 64)
-# launches of the bf16 skinny GEMM, the last (S, FT, NT) either kernel ran with, launches of the e4m3-weight one
-SKINNY_STATS = {"native_calls": 0, "geo": None, "w8_calls": 0}
+# launches of the bf16 skinny GEMM, the last (S, FT, NT) any of the kernels ran with, launches of the e4m3-weight
+# one and of the int4-weight one
+SKINNY_STATS = {"native_calls": 0, "geo": None, "w8_calls": 0, "w4_calls": 0}
 SKINNY_MAX_ROWS = 64
 
 
@@ -338,6 +342,114 @@ def linear_skinny_w8(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor, swi
                                                                                     wq.shape[1], mode, sp))
             return y.view(*x.shape[:-1], y.shape[-1])
     y = F.linear(x, (wq.float() * scale[:, None]).to(x.dtype))
+    if swiglu:
+        from .swiglu import swiglu as _swiglu
+        y = _swiglu(y)
+    return y
+
+
+# ---------------------------------------------------------------------------- the same on group-wise int4 (W4A16)
+INT4_GROUP = 128   # k per scale
+INT4_LINE = 256    # k per 128-byte line of a packed row: the kernel's K step
+INT4_MAX = 7.0
+# Byte b of a packed word holds value j = _NIB_LO[b] in its low nibble and j = _NIB_HI[b] in its high one: the word
+# has j = 2 t in nibble t and j = 2 t + 1 in nibble t + 4.
+_NIB_LO, _NIB_HI = (0, 4, 1, 5), (2, 6, 3, 7)
+
+
+def pack_int4(q: torch.Tensor) -> torch.Tensor:
+    """``q`` int8 [N, K] with values in [-8, 7], K % 256 == 0 -> uint8 [N, K / 2], the layout gemm_skinny_w4.hip
+    reads (this function and ``unpack_int4`` are its definition). A row's 128-byte line ``s`` holds k in
+    [256 s, 256 s + 256); its bytes [32 g, 32 g + 32), g = 0..3, are eight little-endian 32-bit words, and word i
+    holds the eight values k = 256 s + 32 i + 8 g + j as two's-complement nibbles, j = 2 t in nibble t and
+    j = 2 t + 1 in nibble t + 4."""
+    if q.dim() != 2 or q.dtype != torch.int8 or q.shape[1] % INT4_LINE != 0:
+        raise ValueError(f"pack_int4: an int8 [N, K] with K % {INT4_LINE} == 0, got {q.dtype} {tuple(q.shape)}")
+    N, K = q.shape
+    u = (q & 15).to(torch.uint8).view(N, K // INT4_LINE, 8, 4, 8)          # [n, s, i, g, j]
+    b = u[..., list(_NIB_LO)] | (u[..., list(_NIB_HI)] << 4)               # [n, s, i, g, byte of the word]
+    return b.permute(0, 1, 3, 2, 4).reshape(N, K // 2)                     # [n, s, g, i, byte]
+
+
+def unpack_int4(wq: torch.Tensor) -> torch.Tensor:
+    """``pack_int4``'s inverse: uint8 [N, K / 2] -> int8 [N, K] in [-8, 7]."""
+    if wq.dim() != 2 or wq.dtype != torch.uint8 or wq.shape[1] % (INT4_LINE // 2) != 0:
+        raise ValueError(f"unpack_int4: a uint8 [N, K / 2] with K % {INT4_LINE} == 0, got {wq.dtype} {tuple(wq.shape)}")
+    N, K = wq.shape[0], 2 * wq.shape[1]
+    b = wq.reshape(N, K // INT4_LINE, 4, 8, 4).permute(0, 1, 3, 2, 4)        # [n, s, i, g, byte]
+    u = torch.empty(N, K // INT4_LINE, 8, 4, 8, dtype=torch.uint8, device=wq.device)
+    u[..., list(_NIB_LO)] = b & 15
+    u[..., list(_NIB_HI)] = b >> 4
+    q = u.to(torch.int8)
+    return torch.where(q > 7, q - 16, q).reshape(N, K)
+
+
+def quantize_groups_int4(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``w`` [N, K] bf16, K % 256 == 0 -> (``wq`` [N, K / 2] uint8 in ``pack_int4``'s layout, ``scale`` [K / 128, N]
+    fp32, group-major), symmetric int4 with one scale per 128 consecutive k of a row, in fp32: amax over the group,
+    scale = amax * (1 / 7) (1 for a zero group), q = clamp(rint(w * (7 / amax)), -7, 7), ties to even. The kernel on
+    the GPU, the same formula in torch elsewhere (CPU, ``PDT_DISABLE_NATIVE=1``): equal bytes and scales. A NaN or
+    Inf in ``w`` is refused."""
+    if w.dim() != 2 or w.dtype != torch.bfloat16 or w.shape[1] % INT4_LINE != 0 or w.numel() == 0:
+        raise ValueError(f"quantize_groups_int4: a bf16 [N, K] weight with K % {INT4_LINE} == 0, got {w.dtype} "
+                         f"{tuple(w.shape)}")
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("quantize_groups_int4: the weight holds NaN or Inf")
+    if use_native(w):
+        wc = w.contiguous()
+        if wc.data_ptr() % 16 == 0:
+            wq, scale = native().quantize_groups_int4(wc)
+            return wq, scale
+    N, K = w.shape
+    wf = w.float().view(N, K // INT4_GROUP, INT4_GROUP)
+    amax = wf.abs().amax(2)
+    zero = amax == 0
+    scale = torch.where(zero, torch.ones_like(amax), amax * torch.tensor(1.0 / INT4_MAX, dtype=torch.float32))
+    # (a division of tensors, as in quantize_rows_e4m3_reference: ``7 / amax`` would round twice)
+    inv = torch.where(zero, torch.zeros_like(amax), torch.full_like(amax, INT4_MAX) / amax)
+    q = (wf * inv[:, :, None]).round().clamp(-INT4_MAX, INT4_MAX).to(torch.int8).view(N, K)
+    return pack_int4(q), scale.t().contiguous()
+
+
+def dequantize_groups_int4(wq: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """fp32 [N, K]: ``unpack_int4(wq)[n, k] * scale[k // 128, n]``, one exact-or-rounded fp32 product per element."""
+    q = unpack_int4(wq).float()
+    return q * scale.t().repeat_interleave(INT4_GROUP, 1)
+
+
+def skinny_w4_ok(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor, swiglu: bool = False) -> bool:
+    """Inside gemm_skinny_w4.hip's contract: GPU, bf16 rows (1..64), packed int4 weights [N, K / 2] uint8 with fp32
+    scales [K / 128, N], out features % 16 (% 32 with ``swiglu``), in features % 256 and below 2^24, contiguous
+    16-byte aligned weights and scales, the weight below 2^31 bytes."""
+    if not (x.is_cuda and wq.is_cuda and scale.is_cuda and x.dtype == torch.bfloat16 and wq.dtype == torch.uint8
+            and scale.dtype == torch.float32 and wq.dim() == 2 and x.dim() >= 1 and x.shape[-1] == 2 * wq.shape[1]):
+        return False
+    N, K = wq.shape[0], 2 * wq.shape[1]
+    rows = x.numel() // K if K else 0
+    return (1 <= rows <= SKINNY_MAX_ROWS and N % (32 if swiglu else 16) == 0 and N > 0 and K % INT4_LINE == 0
+            and 0 < K < 2 ** 24 and scale.shape == (K // INT4_GROUP, N) and wq.is_contiguous()
+            and wq.data_ptr() % 16 == 0 and scale.is_contiguous() and scale.data_ptr() % 16 == 0
+            and N * (K // 2) < 2 ** 31)
+
+
+def linear_skinny_w4(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor, swiglu: bool = False,
+                     splits: Optional[int] = None) -> torch.Tensor:
+    """``x @ dequantize_groups_int4(wq, scale).T`` (``swiglu``: SwiGLU of it, ``wq`` the packed [gate; up] rows) for
+    inference on at most 64 rows, on the W4A16 weight-streaming kernel: exact int4 operands in the matrix cores, one
+    fp32 fma by the group's scale per 128 k. GPU bf16 rows inside the contract with no gradient to record; anything
+    else (CPU, fp32, ``PDT_DISABLE_NATIVE=1``, a shape outside the contract, autograd on ``x``) is ``F.linear`` on
+    the dequantised weight (then ``ops.swiglu.swiglu``). ``splits``: grid split-K override (None: the kernel's rule)."""
+    needs_grad = torch.is_grad_enabled() and x.requires_grad
+    if use_native(x) and not needs_grad and skinny_w4_ok(x, wq, scale, swiglu):
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        if x2.data_ptr() % 16 == 0:
+            mode, sp = (1 if swiglu else 0), int(splits or 0)
+            y = native().gemm_skinny_w4(x2, wq, scale, mode, sp)
+            SKINNY_STATS["w4_calls"] += 1
+            SKINNY_STATS["geo"] = tuple(int(v) for v in native().gemm_skinny_w4_geo(x2.shape[0], wq.shape[0],
+                                                                                    2 * wq.shape[1], mode, sp))
+            return y.view(*x.shape[:-1], y.shape[-1])
+    y = F.linear(x, dequantize_groups_int4(wq, scale).to(x.dtype))
     if swiglu:
         from .swiglu import swiglu as _swiglu
         y = _swiglu(y)

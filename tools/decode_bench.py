@@ -42,6 +42,11 @@ replayed, weights rotating through 512 MiB of distinct copies, alternating, devi
 each line's rate is over the bytes that candidate must move. Then the generation A/B under PDT_DECODE_GEMM=1:
 the captured step and 128 tokens after a 128-token prompt, bf16 weights against quantize_decode_weights().
 
+--gemm-w4: the decode-time Linears on group-wise int4 weights. The --gemm-w8 shapes and recipe with two candidates,
+the W4A16 skinny GEMM and the W8A16 one (the reference of every time), each rotating through its own 512 MiB of
+distinct copies; the bytes a candidate must move include its scales. Then the captured step and 128 tokens after a
+128-token prompt on quantize_decode_weights() against quantize_decode_weights("int4").
+
 --paged: the paged decode kernel. The kernel table's shapes and recipe (captured and replayed, rotating caches,
 alternating, device events, median of the rounds): attention_decode_paged with a sequential block table and
 with a seeded shuffled one against attention_decode on the same keys, and whether the three give the same
@@ -859,6 +864,125 @@ def bench_gemm_w8_generate(rounds, emit, prompt=128, new=128):
          "of positions (a random-weight model: the quantisation moves near-ties, after which the rest differs)")
 
 
+def bench_gemm_w4(rounds, iters, emit):
+    """As bench_gemm_w8 with the int4-weight kernel against the e4m3-weight one, the reference of every time; each
+    rotates through its own >= 512 MiB of distinct weight copies (more copies than the bf16 size would need), and a
+    window makes at least as many calls as there are copies. The bytes a candidate must move include its scales."""
+    from pytorch_distributed_training_example_amd.ops._native import native
+    C, dev = native(), "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    for name, N, K, fused in GEMM_SHAPES:
+        ncopy, ncopy8, ncopy4 = (-(-ROTATE_BYTES // (N * K * 2)), -(-ROTATE_BYTES // (N * K)),
+                                 -(-ROTATE_BYTES // (N * K // 2)))
+        calls = max(iters, ncopy4)
+        w = (torch.randn(ncopy, N, K, device=dev, generator=g) / math.sqrt(K)).bfloat16()
+        q8 = [C.quantize_rows_e4m3(w[i % ncopy]) for i in range(ncopy8)]
+        w8q, s8 = torch.stack([a for a, _ in q8]), torch.stack([b for _, b in q8])
+        q4 = [C.quantize_groups_int4(w[i % ncopy]) for i in range(ncopy4)]
+        w4q, s4 = torch.stack([a for a, _ in q4]), torch.stack([b for _, b in q4])
+        del q8, q4
+        emit(f"## {name}: N = {N}, K = {K}: {N * K / 2**21:.2f} MiB int4 + {N * K / 32 / 2**20:.2f} MiB scales x {ncopy4} "
+             f"copies, {N * K / 2**20:.1f} MiB e4m3 x {ncopy8} copies, {calls} calls per window")
+        for M in GEMM_ROWS:
+            x = torch.randn(M, K, device=dev, generator=g).bfloat16()
+            mode = 1 if fused else 0
+            geo = {"w4": tuple(C.gemm_skinny_w4_geo(M, N, K, mode, 0)), "w8": tuple(C.gemm_skinny_w8_geo(M, N, K, mode, 0))}
+            io = M * K * 2 + M * (N // 2 if fused else N) * 2
+            must = {"w4": N * K // 2 + (K // 128) * N * 4 + io, "w8": N * K + N * 4 + io}
+
+            def w4(i):
+                return C.gemm_skinny_w4(x, w4q[i % ncopy4], s4[i % ncopy4], mode, 0)
+
+            def w8(i):
+                return C.gemm_skinny_w8(x, w8q[i % ncopy8], s8[i % ncopy8], mode, 0)
+
+            err = (w4(0).float() - w8(0).float()).abs().max().item()
+            t = _alternate({"w4": w4, "w8": w8}, rounds, calls)
+            med = {k: statistics.median(v[1]) for k, v in t.items()}
+            for k, (_, tg) in t.items():
+                emit(f"M {M:2d}  {k:<3} (S, FT, NT) = {geo[k]}  replayed {med[k] * 1e3:6.1f} us "
+                     f"({min(tg) * 1e3:.1f}-{max(tg) * 1e3:.1f})  {must[k] / 2**20:6.2f} MiB  {must[k] / med[k] / 1e9:5.2f} TB/s  "
+                     f"{med['w8'] / med[k]:5.2f}x w8")
+            emit(f"M {M:2d}  max |w4 - w8| = {err:.3g} (the two quantisations)")
+        del w, w8q, s8, w4q, s4
+
+
+def bench_gemm_w4_generate(rounds, emit, prompt=128, new=128):
+    """The captured llama_medium decode step and the 128-after-128-token generation on it: quantize_decode_weights()
+    (e4m3, the reference) against quantize_decode_weights("int4"), one process, alternating."""
+    from pytorch_distributed_training_example_amd.models import get_model
+    from pytorch_distributed_training_example_amd.models.precision import to_bf16_mixed
+    torch.manual_seed(0)
+    model = to_bf16_mixed(get_model("llama_medium").cuda()).eval()
+    idx = torch.randint(0, model.cfg.vocab_size, (B, prompt), generator=torch.Generator().manual_seed(1)).cuda()
+    mods = list(model._decode_linears())
+    saved = {"e4m3": ("_w8", [m._w8 for m in model.quantize_decode_weights()._decode_linears()]),
+             "int4": ("_w4", [m._w4 for m in model.quantize_decode_weights("int4")._decode_linears()])}
+    states = {}
+
+    def select(name):
+        model.drop_decode_weights()
+        for m, q in zip(mods, saved[name][1]):
+            setattr(m, saved[name][0], q)
+
+    with torch.no_grad():
+        for name in saved:
+            select(name)
+            cache = model.new_cache(B, prompt + new)
+            model.prefill(idx, cache)
+            tok = torch.zeros(B, dtype=torch.long, device="cuda")
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                model.decode_step(tok, cache)
+            torch.cuda.current_stream().wait_stream(side)
+            cache.reset()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                logits = model.decode_step(tok, cache)
+            states[name] = (cache, tok, graph, logits)
+
+        def gen(name):
+            select(name)
+            cache, tok, graph, logits = states[name]
+            cache.reset()
+            toks = [model.prefill(idx, cache).argmax(-1)]
+            cache.set_lens(cache.lens, bound=prompt + new)
+            for _ in range(new - 1):
+                tok.copy_(toks[-1])
+                graph.replay()
+                toks.append(logits.argmax(-1))
+            return torch.stack(toks, 1)
+
+        toks = {name: gen(name) for name in states}
+        torch.cuda.synchronize()
+        ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
+        t_gen, t_step = {n: [] for n in states}, {n: [] for n in states}
+        for _ in range(rounds):
+            for name in states:
+                s, e = ev(), ev()
+                s.record()
+                gen(name)
+                e.record()
+                torch.cuda.synchronize()
+                t_gen[name].append(s.elapsed_time(e))
+                states[name][0].set_lens([prompt] * B)
+                s, e = ev(), ev()
+                s.record()
+                for _ in range(32):
+                    states[name][2].replay()
+                e.record()
+                torch.cuda.synchronize()
+                t_step[name].append(s.elapsed_time(e) / 32)
+    for name in states:
+        mg, ms = statistics.median(t_gen[name]), statistics.median(t_step[name])
+        emit(f"llama_medium, {name} weights: {prompt}+{new} tokens x {B} on the captured step {mg:8.1f} ms "
+             f"({min(t_gen[name]):.1f}-{max(t_gen[name]):.1f}), {B * new / mg * 1e3:7.0f} new tok/s; replayed step at "
+             f"position {prompt}..{prompt + 31}: {ms:.3f} ms ({min(t_step[name]):.3f}-{max(t_step[name]):.3f})")
+    emit(f"llama_medium: tokens with int4 weights == e4m3 weights: {float((toks['int4'] == toks['e4m3']).float().mean()):.3f} "
+         "of positions (a random-weight model: the quantisation moves near-ties, after which the rest differs)")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--rounds", type=int, default=7)
@@ -872,6 +996,9 @@ def main(argv=None):
     ap.add_argument("--gemm-w8", action="store_true", help="the decode-time Linears on e4m3 weights: the W8A16 skinny "
                     "GEMM against the bf16 one and the library, then the generation with and without "
                     "quantize_decode_weights() under PDT_DECODE_GEMM=1")
+    ap.add_argument("--gemm-w4", action="store_true", help="the decode-time Linears on group-wise int4 weights: the W4A16 "
+                    "skinny GEMM against the W8A16 one, then the generation on quantize_decode_weights() and on "
+                    "quantize_decode_weights(\"int4\")")
     ap.add_argument("--paged-fp8", action="store_true", help="the e4m3 paged decode kernel against the bf16 paged "
                     "kernel (both captured, rotating caches, taking turns), then the captured llama_medium step on both caches")
     ap.add_argument("--paged", action="store_true", help="the paged decode kernel under a sequential and a shuffled "
@@ -903,6 +1030,11 @@ def main(argv=None):
             bench_paged(a.rounds, a.iters, emit)
         if not a.no_generate:
             bench_paged_step(a.gen_rounds, emit)
+    elif a.gemm_w4:
+        if not a.no_kernel:
+            bench_gemm_w4(a.rounds, a.iters, emit)
+        if not a.no_generate:
+            bench_gemm_w4_generate(a.gen_rounds, emit)
     elif a.gemm_w8:
         if not a.no_kernel:
             bench_gemm_w8(a.rounds, a.iters, emit)
@@ -917,7 +1049,8 @@ def main(argv=None):
         bench_extend(a.rounds, a.iters, emit)
     elif not a.no_kernel:
         bench_kernel(a.rounds, a.iters, emit)
-    if not a.no_generate and not a.extend and not a.gemm and not a.gemm_w8 and not a.paged and not a.paged_fp8:
+    if not a.no_generate and not a.extend and not a.gemm and not a.gemm_w8 and not a.gemm_w4 and not a.paged \
+            and not a.paged_fp8:
         bench_generate(a.gen_rounds, emit)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
