@@ -104,6 +104,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--sample-temperature", type=float, default=0.0, metavar="T",
                    help="0 (default): greedy; otherwise sample from softmax(logits / T), seeded from --seed")
     p.add_argument("--sample-top-k", type=int, default=None, metavar="K", help="sample among the K likeliest tokens")
+    p.add_argument("--sample-top-p", type=float, default=None, metavar="P",
+                   help="nucleus sampling: keep the likeliest tokens whose probabilities add up to P, 0 < P <= 1 "
+                        "(after --sample-top-k); needs --sample-sampler fused")
+    p.add_argument("--sample-sampler", choices=["torch", "fused"], default="torch",
+                   help="torch (default): argmax / torch.multinomial on a torch.Generator; fused: one HIP launch per "
+                        "token (ops/sampling.py), drawing from a Philox counter seeded from --seed")
     p.add_argument("--profile", default=None, metavar="DIR",
                    help="torch.profiler trace of a few steps of epoch 1 into DIR (rank 0), roctx ranges on")
     return p
@@ -165,6 +171,11 @@ def sample_args_error(args) -> Optional[str]:
         return f"--sample-prompt: token ids must be in [0, {cfg.vocab_size}) for {args.model}"
     if args.sample_temperature < 0 or (args.sample_top_k is not None and args.sample_top_k < 1):
         return "--sample-temperature must be >= 0 and --sample-top-k >= 1"
+    top_p = getattr(args, "sample_top_p", None)
+    if top_p is not None and getattr(args, "sample_sampler", "torch") != "fused":
+        return "--sample-top-p: nucleus sampling belongs to the fused sampler; add --sample-sampler fused"
+    if top_p is not None and not 0.0 < top_p <= 1.0:
+        return f"--sample-top-p {top_p}: P must be in (0, 1]"
     return None
 
 
@@ -375,7 +386,9 @@ def run(rank: int, world: int, args) -> dict:
         sample_cache = getattr(args, "sample_cache", "contiguous")
         toks = model.generate(prompt, args.sample_tokens, temperature=args.sample_temperature,
                               top_k=args.sample_top_k, generator=gen, paged=sample_cache != "contiguous",
-                              kv_dtype="fp8" if sample_cache == "paged-fp8" else None)
+                              kv_dtype="fp8" if sample_cache == "paged-fp8" else None,
+                              top_p=getattr(args, "sample_top_p", None),
+                              sampler=getattr(args, "sample_sampler", "torch"))
         result["sample"] = toks[0].tolist()
         print(f"Sample: {result['sample']}", flush=True)
     metrics.close()

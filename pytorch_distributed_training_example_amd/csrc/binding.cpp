@@ -2442,6 +2442,45 @@ Tensor dropout_mask(Tensor ticket, int64_t dstream, std::vector<int64_t> shape, 
   return out;
 }
 
+// ----------------------------------------------------------------------------- token sampling (sampling.hip)
+// One token per row of logits [B, V] from per-row temperature / top_k / top_p device tensors; the uniform is
+// u [B], or the Philox word of (ticket, stream, row). probs [B, V] fp32, when given, receives the filtered,
+// renormalised distribution each token was drawn from.
+Tensor sample_logits(Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, c10::optional<Tensor> u,
+                     c10::optional<Tensor> ticket, int64_t pstream, c10::optional<Tensor> probs) {
+  const Op op("sample_logits", logits);
+  TORCH_CHECK(logits.scalar_type() == at::kFloat || logits.scalar_type() == at::kBFloat16,
+              "sample_logits: logits must be fp32 or bf16, got ", logits.scalar_type());
+  TORCH_CHECK(logits.dim() == 2, "sample_logits: logits must be [B, V], got ", logits.dim(), " dimensions");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V >= 1 && V <= 131072, "sample_logits: V = ", V, " outside 1..131072");
+  TORCH_CHECK(B >= 1 && B <= 65535, "sample_logits: B = ", B, " outside 1..65535");
+  TORCH_CHECK(logits.is_contiguous(), "sample_logits: logits rows must be contiguous (stride V, 1)");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
+              "sample_logits: logits must start at a 16-byte boundary (misaligned)");
+  const float* tp = f32_ptr(op, "temperature", temperature, B);
+  check_flat(op, "top_k", top_k, at::kInt, B);
+  const float* pp = f32_ptr(op, "top_p", top_p, B);
+  TORCH_CHECK(has(u) != has(ticket), "sample_logits: exactly one of u and ticket must be given");
+  const float* up = has(u) ? f32_ptr(op, "u", *u, B) : nullptr;
+  const int64_t* kp = nullptr;
+  if (has(ticket)) {
+    check_flat(op, "ticket", *ticket, at::kLong, 2);
+    kp = ticket->data_ptr<int64_t>();
+  }
+  float* prp = nullptr;
+  if (has(probs)) {
+    TORCH_CHECK(probs->dim() == 2 && probs->size(0) == B && probs->size(1) == V,
+                "sample_logits: probs must be [B, V] like the logits");
+    prp = f32_ptr(op, "probs", *probs, B * V);
+  }
+  auto tokens = at::empty({B}, logits.options().dtype(at::kLong));
+  const int rc = pdt_sample_logits(logits.data_ptr(), dcode(logits), (int)B, (int)V, tp, top_k.data_ptr<int>(), pp, up,
+                                   kp, (int)pstream, tokens.data_ptr<int64_t>(), prp, stream());
+  TORCH_CHECK(rc == 0, "sample_logits: pdt_sample_logits failed: ", rc);
+  return tokens;
+}
+
 // s = x + dropout(res), y = LN(s): {y, mean, rstd, s}
 std::vector<Tensor> ln_fwd_drop(Tensor x, Tensor w, Tensor b, double eps, Tensor res, Tensor ticket, int64_t dstream,
                                 int64_t thr) {
@@ -3268,6 +3307,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dropout_begin", &dropout_begin);
   m.def("dropout_fwd", &dropout_fwd);
   m.def("dropout_mask", &dropout_mask);
+  m.def("sample_logits", &sample_logits, py::arg("logits"), py::arg("temperature"), py::arg("top_k"), py::arg("top_p"),
+        py::arg("u") = py::none(), py::arg("ticket") = py::none(), py::arg("stream") = 0,
+        py::arg("probs") = py::none());
   m.def("ln_fwd_drop", &ln_fwd_drop);
   m.def("ln_bwd_drop", &ln_bwd_drop);
   m.def("colsum", &colsum);

@@ -406,6 +406,13 @@ int pdt_rope_qkv(uint16_t* qkv, const float* cos, const float* sin, int B, int T
 int pdt_rope_qkv_gqa(uint16_t* qkv, const float* cos, const float* sin, int B, int T, int H, int Hkv, int conj,
                      hipStream_t s);
 
+// kernels/sampling.hip: one token per row of logits [B, V] (dtype 0 fp32, 1 bf16; base 16-byte aligned, rows
+// contiguous) from per-row temperature / top_k / top_p on the device. The uniform of row b is u[b], or with
+// u == nullptr the Philox word of (ticket, philox_stream, b). probs [B, V] fp32 or nullptr.
+int pdt_sample_logits(const void* logits, int dtype, int B, int V, const float* temperature, const int* top_k,
+                      const float* top_p, const float* u, const int64_t* ticket, int philox_stream, int64_t* tokens,
+                      float* probs, hipStream_t s);
+
 // kernels/slice_sum.hip
 int pdt_slice_sum_bf16(const uint16_t* x, uint16_t* out, int S, int64_t n, hipStream_t s);
 

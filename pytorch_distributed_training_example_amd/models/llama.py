@@ -48,6 +48,8 @@ from ..ops.linear import (SKINNY_MAX_ROWS, linear, linear_skinny, linear_skinny_
                           quantize_groups_int4, quantize_rows_e4m3)
 from ..ops.rmsnorm import RMSNorm, add_rms_norm
 from ..ops.rope import RotaryTable, rope_append_, rope_append_paged_, rope_append_paged_fp8_, rope_qkv_
+from ..ops.sampling import SamplerState
+from ..ops.sampling import sample as sample_fused
 from ..ops.swiglu import swiglu
 from .transformer import init_weights
 
@@ -573,7 +575,7 @@ class Llama(nn.Module):
     def generate(self, idx: torch.Tensor, max_new_tokens: int, temperature: float = 0.0, top_k: int | None = None,
                  eos_token: int | None = None, generator: torch.Generator | None = None, prompt_lens=None,
                  return_logits: bool = False, prefill_chunk: int | None = None, paged: bool = False,
-                 kv_dtype: str | None = None):
+                 kv_dtype: str | None = None, top_p=None, sampler: str = "torch"):
         """Sample ``max_new_tokens`` tokens after the prompts ``idx`` [B, T0] (right-padded when
         ``prompt_lens`` is given); returns them as [B, max_new_tokens] on the device, with ``return_logits``
         also the logits [B, max_new_tokens, V] each was drawn from. Greedy at ``temperature`` 0, otherwise
@@ -584,8 +586,24 @@ class Llama(nn.Module):
         long prompt by the slice. With ``paged`` the same loop runs on a ``PagedKVCache`` sized for the batch,
         which reserves pages before the prefill (with ``prefill_chunk``: before every slice) and before every
         step; ``kv_dtype="fp8"`` makes that cache an e4m3 one (``new_paged_cache``), which takes the prompt whole:
-        with ``prefill_chunk`` it is refused. Runs in ``eval()`` and restores the mode."""
+        with ``prefill_chunk`` it is refused. ``sampler="fused"`` draws every token with one launch of the
+        HIP sampler instead (``ops/sampling.py``: adds nucleus sampling ``top_p``, accepts ``temperature`` /
+        ``top_k`` / ``top_p`` as per-sequence [B] tensors, and draws from a Philox counter seeded from
+        ``generator.initial_seed()``, 0 without one, so a run is a function of the seed); ``top_p`` with the
+        ``"torch"`` sampler is refused. Runs in ``eval()`` and restores the mode."""
         B, T0 = idx.shape
+        if sampler not in ("torch", "fused"):
+            raise ValueError(f"generate: sampler must be 'torch' or 'fused', got {sampler!r}")
+        if sampler == "torch" and top_p is not None:
+            raise ValueError("generate: top_p needs sampler='fused' (the torch sampler has no nucleus filter)")
+        if sampler == "fused":
+            state = SamplerState(generator.initial_seed() if generator is not None else 0)
+
+            def draw(logits):
+                return sample_fused(logits.contiguous(), temperature, top_k, top_p, state=state)
+        else:
+            def draw(logits):
+                return _sample(logits, temperature, top_k, generator)
         if kv_dtype is not None and not paged:
             raise NotImplementedError(f"generate: kv_dtype = {kv_dtype!r} needs paged=True; an fp8 contiguous KVCache is "
                                       "out of scope")
@@ -616,7 +634,7 @@ class Llama(nn.Module):
             toks, all_logits = [], []
             done = torch.zeros(B, dtype=torch.bool, device=idx.device)
             for i in range(max_new_tokens):
-                tok = _sample(logits, temperature, top_k, generator)
+                tok = draw(logits)
                 if eos_token is not None:
                     tok = torch.where(done, torch.full_like(tok, eos_token), tok)
                     done = done | (tok == eos_token)

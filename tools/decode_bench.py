@@ -61,6 +61,12 @@ of every time) and attention_extend_paged with a sequential and a seeded shuffle
 process, captured and replayed, over rotating caches, and whether the three give the same bits; then llama_medium
 with 8 paged slots, a 512-token prompt joining in slices of 64 against the same prompt as one paged prefill.
 
+--sampler: the fused top-k / top-p sampler (ops/sampling.py). bf16 logits [B, 32000], B in {1, 8, 64}, rotating through
+16 distinct buffers; greedy, T = 0.8, T = 0.8 with k = 50, and that with p = 0.9. The fused call against the aten chain
+of models/llama.py:_sample (which has no top-p), taking turns, device events, median of the rounds; the fused call
+eager and captured, the chain eager only (its aten kernels record memset nodes, which do not replay safely here). Then llama_medium's 128-after-128-token generation on the
+captured step with either sampler between the replays.
+
     python tools/decode_bench.py [--rounds 7] [--iters 50] [--gen-rounds 3] [--no-generate] [--extend] [--paged] [--paged-fp8] [--out FILE]
 """
 from __future__ import annotations
@@ -983,8 +989,105 @@ def bench_gemm_w4_generate(rounds, emit, prompt=128, new=128):
          "of positions (a random-weight model: the quantisation moves near-ties, after which the rest differs)")
 
 
+SAMPLER_SETTINGS = (("greedy", 0.0, None, None), ("T=0.8", 0.8, None, None), ("T=0.8 k=50", 0.8, 50, None),
+                    ("T=0.8 k=50 p=0.9", 0.8, 50, 0.9))
+
+
+def bench_sampler(rounds, iters, emit, V=32000, ncopy=16):
+    """--sampler: ops.sampling.sample (one HIP launch plus the ticket launch) against the aten chain of
+    models/llama.py:_sample on bf16 logits [B, 32000] rotating through distinct buffers, taking turns. The fused call
+    is timed eager and captured. The chain is timed eager only: its multi-block reductions and topk clear their
+    counters with memset nodes, and a replay of a graph that holds them faulted the device when this was first run."""
+    from pytorch_distributed_training_example_amd.models.llama import _sample
+    from pytorch_distributed_training_example_amd.ops.sampling import SamplerState, sample
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    for rows in (1, 8, 64):
+        bufs = [(3 * torch.randn(rows, V, device=dev, generator=g)).bfloat16() for _ in range(ncopy)]
+        for name, T, k, p in SAMPLER_SETTINGS:
+            st, gen = SamplerState(0), torch.Generator(device=dev).manual_seed(0)
+            cands = {"fused": lambda i: sample(bufs[i % ncopy], T, k, p, state=st)}
+            if p is None:  # the chain has no nucleus filter
+                cands["chain"] = lambda i: _sample(bufs[i % ncopy], T, k, gen)
+            for fn in cands.values():
+                for i in range(3):
+                    fn(i)
+            torch.cuda.synchronize()
+            graphs = {"fused": _graphed(cands["fused"], iters)}
+            t = {c: ([], []) for c in cands}
+            for _ in range(rounds):
+                for c, fn in cands.items():
+                    t[c][0].append(_time_ms(fn, iters))
+                    if c in graphs:
+                        t[c][1].append(_time_ms(lambda i, gr=graphs[c]: gr.replay(), 1) / iters)
+            for c, (te, tg) in t.items():
+                rep = f"replayed {statistics.median(tg) * 1e3:6.1f} us ({min(tg) * 1e3:.1f}-{max(tg) * 1e3:.1f})" if tg else "replayed n/a"
+                emit(f"B {rows:2d}  {name:<17} {c:<5} eager {statistics.median(te) * 1e3:6.1f} us "
+                     f"({min(te) * 1e3:.1f}-{max(te) * 1e3:.1f})  {rep}")
+            del graphs
+
+
+def bench_sampler_generate(rounds, emit, prompt=128, new=128):
+    """--sampler: llama_medium, 8 sequences, 128 tokens after a 128-token prompt on the captured decode step, the
+    token between two replays drawn by the aten chain and by the fused sampler (eager launches), taking turns."""
+    from pytorch_distributed_training_example_amd.models import get_model
+    from pytorch_distributed_training_example_amd.models.llama import _sample
+    from pytorch_distributed_training_example_amd.models.precision import to_bf16_mixed
+    from pytorch_distributed_training_example_amd.ops.sampling import SamplerState, sample
+    torch.manual_seed(0)
+    model = to_bf16_mixed(get_model("llama_medium").cuda()).eval()
+    idx = torch.randint(0, model.cfg.vocab_size, (B, prompt), generator=torch.Generator().manual_seed(1)).cuda()
+    gen, st = torch.Generator(device="cuda").manual_seed(0), SamplerState(0)
+    draws = {"chain  T=0.8 k=50": lambda l: _sample(l, 0.8, 50, gen),
+             "fused  T=0.8 k=50": lambda l: sample(l, 0.8, 50, None, state=st),
+             "fused  T=0.8 k=50 p=0.9": lambda l: sample(l, 0.8, 50, 0.9, state=st),
+             "argmax (greedy, as the other tables)": lambda l: l.argmax(-1)}
+    with torch.no_grad():
+        cache = model.new_cache(B, prompt + new)
+        model.prefill(idx, cache)
+        tok = torch.zeros(B, dtype=torch.long, device="cuda")
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            model.decode_step(tok, cache)
+        torch.cuda.current_stream().wait_stream(side)
+        cache.reset()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            logits = model.decode_step(tok, cache)
+
+        def gen_tokens(draw):
+            cache.reset()
+            toks = [draw(model.prefill(idx, cache))]
+            cache.set_lens(cache.lens, bound=prompt + new)
+            for _ in range(new - 1):
+                tok.copy_(toks[-1])
+                graph.replay()
+                toks.append(draw(logits))
+            return torch.stack(toks, 1)
+
+        for d in draws.values():
+            gen_tokens(d)
+        torch.cuda.synchronize()
+        out = {k: [] for k in draws}
+        for _ in range(rounds):
+            for k, d in draws.items():
+                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record()
+                gen_tokens(d)
+                e.record()
+                torch.cuda.synchronize()
+                out[k].append(s.elapsed_time(e))
+    for k, v in out.items():
+        m = statistics.median(v)
+        emit(f"llama_medium: {prompt}+{new} tokens x {B} on the captured step, draw = {k:<37} {m:8.1f} ms "
+             f"({min(v):.1f}-{max(v):.1f})  {B * new / m * 1e3:7.0f} new tok/s")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--sampler", action="store_true", help="the fused top-k / top-p sampler against the aten chain of "
+                    "_sample on [B, 32000] bf16 logits, then the llama_medium generation with either between the replays")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=50, help="kernel calls per timed window")
     ap.add_argument("--gen-rounds", type=int, default=3)
@@ -1015,7 +1118,13 @@ def main(argv=None):
 
     emit(f"# {torch.cuda.get_device_name(0)}; B={B} H={H} Dh={DH} capacity={CAP} bf16; median of {a.rounds} alternating "
          f"rounds (min-max), {a.iters} calls per window, device events")
-    if a.paged and a.extend:
+    if a.sampler:
+        if not a.no_kernel:
+            with torch.no_grad():
+                bench_sampler(a.rounds, a.iters, emit)
+        if not a.no_generate:
+            bench_sampler_generate(a.gen_rounds, emit)
+    elif a.paged and a.extend:
         if not a.no_kernel:
             bench_paged_extend(a.rounds, a.iters, emit)
         if not a.no_generate:
@@ -1050,7 +1159,7 @@ def main(argv=None):
     elif not a.no_kernel:
         bench_kernel(a.rounds, a.iters, emit)
     if not a.no_generate and not a.extend and not a.gemm and not a.gemm_w8 and not a.gemm_w4 and not a.paged \
-            and not a.paged_fp8:
+            and not a.paged_fp8 and not a.sampler:
         bench_generate(a.gen_rounds, emit)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
