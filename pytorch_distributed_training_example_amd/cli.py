@@ -92,10 +92,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--sample-tokens", type=int, default=0, metavar="N",
                    help="llama_* only: after the last epoch rank 0 generates N tokens on the KV cache and prints "
                         "'Sample: [ids]' (with --resume and a finished checkpoint: sample it without training)")
-    p.add_argument("--sample-weights", choices=["bf16", "fp8", "int4"], default="bf16",
+    p.add_argument("--sample-weights", choices=["bf16", "fp8", "int4", "int4-all"], default="bf16",
                    help="llama_* only, with --sample-tokens: fp8 quantises the Linear weights row-wise to e4m3 before "
                         "sampling (Llama.quantize_decode_weights: decode steps then stream one byte per weight); int4 "
-                        "quantises them to 4 bits with one scale per 128 inputs (half a byte per weight)")
+                        "quantises them to 4 bits with one scale per 128 inputs (half a byte per weight); int4-all "
+                        "also runs calls on more than 64 rows (the prompt) on the int4 weights (all_rows=True)")
     p.add_argument("--sample-cache", choices=["contiguous", "paged", "paged-fp8"], default="contiguous",
                    help="llama_* only, with --sample-tokens: paged generates on a PagedKVCache (pages of 64 positions "
                         "found through a block table) instead of one contiguous slab per sequence; paged-fp8 on one "
@@ -381,7 +382,9 @@ def run(rank: int, world: int, args) -> dict:
     if getattr(args, "sample_tokens", 0) and rank == 0:
         gen = torch.Generator(device=device).manual_seed(args.seed)
         prompt = torch.tensor([parse_prompt(args.sample_prompt)], device=device)
-        if getattr(args, "sample_weights", "bf16") != "bf16":
+        if getattr(args, "sample_weights", "bf16") == "int4-all":
+            model.quantize_decode_weights("int4", all_rows=True)
+        elif getattr(args, "sample_weights", "bf16") != "bf16":
             model.quantize_decode_weights(args.sample_weights)
         sample_cache = getattr(args, "sample_cache", "contiguous")
         toks = model.generate(prompt, args.sample_tokens, temperature=args.sample_temperature,

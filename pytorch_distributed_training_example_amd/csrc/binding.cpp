@@ -2393,6 +2393,46 @@ Tensor gemm_skinny_w4(Tensor x, Tensor wq, Tensor scale, int64_t mode, int64_t s
   return y;
 }
 
+// ----------------------------------------------------------------------------- W4A16 GEMM, any M (gemm_w4.hip)
+// (S, BM, BN) of gemm_w4 for x [M, K], wq [N, K / 2]: S grid splits of K, a BM x BN tile per workgroup. splits 0:
+// the default rule. Refuses shapes outside the contract.
+std::vector<int64_t> gemm_w4_geo(int64_t M, int64_t N, int64_t K, int64_t splits) {
+  TORCH_CHECK(M >= 1 && M <= 64 * 65535, "gemm_w4: 1 <= M <= ", 64 * 65535, " rows, got ", M);
+  TORCH_CHECK(N >= 16 && N % 16 == 0 && N <= 0x7fffffffLL, "gemm_w4: N % 16 == 0, got ", N);
+  TORCH_CHECK(K >= 256 && K % 256 == 0 && K < (1 << 24), "gemm_w4: K % 256 == 0 and K < 2^24, got ", K);
+  TORCH_CHECK(splits >= 0 && splits <= 65535, "gemm_w4: splits in [0, 65535], got ", splits);
+  TORCH_CHECK(N * (K / 2) < 0x80000000LL, "gemm_w4: wq of ", N, " x ", K / 2, " is past 2^31 bytes");
+  int g[3];
+  const int rc = pdt_gemm_w4_geo((int)M, (int)N, (int)K, (int)splits, g);
+  TORCH_CHECK(rc == 0, "gemm_w4: pdt_gemm_w4_geo failed: ", rc);
+  return {g[0], g[1], g[2]};
+}
+
+// y [M, N] = bf16(sum_g scale[g, n] * (x [M, group g] q [N, group g]^T)) for any M: x bf16, wq uint8 [N, K / 2] packed
+// int4, scale fp32 [K / 128, N]. y_out: write into this tensor instead of a new one.
+Tensor gemm_w4(Tensor x, Tensor wq, Tensor scale, int64_t splits, c10::optional<Tensor> y_out) {
+  const Op op("gemm_w4", x);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && wq.scalar_type() == at::kByte,
+              "gemm_w4: x must be bf16 and wq uint8 (packed int4)");
+  TORCH_CHECK(wq.device() == op.dev, "gemm_w4: wq must be on ", op.dev);
+  TORCH_CHECK(x.dim() == 2 && wq.dim() == 2 && x.size(1) == 2 * wq.size(1), "gemm_w4: x [M, K] and wq [N, K / 2]");
+  TORCH_CHECK(x.is_contiguous() && wq.is_contiguous() && aligned16(x) && aligned16(wq),
+              "gemm_w4: x and wq must be contiguous and 16-byte aligned");
+  const int64_t M = x.size(0), K = x.size(1), N = wq.size(0);
+  const std::vector<int64_t> geo = gemm_w4_geo(M, N, K, splits);
+  TORCH_CHECK(scale.dim() == 2 && scale.size(0) == K / 128 && scale.size(1) == N && aligned16(scale),
+              "gemm_w4: scale must be a 16-byte aligned fp32 [K / 128, N] = [", K / 128, ", ", N, "]");
+  const float* sc = f32_ptr(op, "scale", scale, (K / 128) * N);
+  const int64_t S = geo[0];
+  auto y = out_or_new(op, "y_out", y_out, {M, N}, x.options());
+  Tensor ws;
+  if (S > 1) ws = at::empty({S * M * N}, x.options().dtype(at::kFloat));
+  const int rc = pdt_gemm_w4(bf16_ptr(x), byte_ptr(wq), sc, bf16_out(y), ptr_or_null<float>(ws), (int)M, (int)N, (int)K,
+                             (int)S, (int)geo[1], stream());
+  TORCH_CHECK(rc == 0, "gemm_w4: pdt_gemm_w4 failed: ", rc);
+  return y;
+}
+
 // ----------------------------------------------------------------------------- dropout (philox.h)
 const int64_t* ticket_ptr(const Tensor& ticket, const Tensor& like) {
   TORCH_CHECK(ticket.is_cuda() && ticket.scalar_type() == at::kLong && ticket.numel() == 2 && ticket.is_contiguous() &&
@@ -3368,6 +3408,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("splits") = 0);
   m.def("gemm_skinny_w4", &gemm_skinny_w4, py::arg("x"), py::arg("wq"), py::arg("scale"), py::arg("mode") = 0,
         py::arg("splits") = 0, py::arg("y_out") = py::none());
+  m.def("gemm_w4_geo", &gemm_w4_geo, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("splits") = 0);
+  m.def("gemm_w4", &gemm_w4, py::arg("x"), py::arg("wq"), py::arg("scale"), py::arg("splits") = 0,
+        py::arg("y_out") = py::none());
   m.def("swiglu_bwd", &swiglu_bwd, py::arg("dy"), py::arg("gu"), py::arg("dgu_out") = py::none());
   py::class_<P2PComm>(m, "P2PComm")
       .def(py::init<int, int, int64_t, int, int>(), py::arg("rank"), py::arg("world"), py::arg("capacity_bytes"),

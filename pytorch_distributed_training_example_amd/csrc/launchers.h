@@ -320,6 +320,12 @@ int pdt_gemm_skinny_w4_geo(int M, int N, int K, int mode, int splits, int* geo3)
 int pdt_gemm_skinny_w4(const uint16_t* x, const uint8_t* wq, const float* scale, uint16_t* y, float* ws, int M, int N,
                        int K, int mode, int S, int FT, int NT, hipStream_t s);
 
+// kernels/gemm_w4.hip: the same operands for any M: a tiled W4A16 GEMM, weights stationary in registers, X through
+// LDS. geo3 = (S, BM, BN)
+int pdt_gemm_w4_geo(int M, int N, int K, int splits, int* geo3);
+int pdt_gemm_w4(const uint16_t* x, const uint8_t* wq, const float* scale, uint16_t* y, float* ws, int M, int N, int K,
+                int S, int BM, hipStream_t s);
+
 // kernels/layernorm.hip
 int64_t pdt_ln_workspace_floats(int64_t N, int D);
 int pdt_ln_fwd(const void* x, const void* res, int dtype, const float* w, const float* b, void* y, void* sum_out,

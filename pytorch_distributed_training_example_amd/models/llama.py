@@ -27,7 +27,9 @@ row-wise to e4m3 (ops/linear.py ``quantize_rows_e4m3``); calls on at most 64 row
 (a long prefill) and training keep the bf16 weights, which stay in place; ``drop_decode_weights()`` undoes it.
 ``quantize_decode_weights("int4")`` stores symmetric int4 with one fp32 scale per 128 inputs instead
 (``quantize_groups_int4``, a quarter of the bf16 bytes plus the scales) and the same calls run the W4A16 skinny
-GEMM (``linear_skinny_w4``); one call replaces the other's copies.
+GEMM (``linear_skinny_w4``); one call replaces the other's copies. ``quantize_decode_weights("int4",
+all_rows=True)`` sends calls on more than 64 rows (a long prefill, an extend, a verify) to the int4 copies too, on
+the tiled W4A16 GEMM (``linear_w4``): the whole of generation then computes from one set of weights.
 """
 from __future__ import annotations
 
@@ -44,7 +46,7 @@ from ..ops.attention import (attention_decode, attention_decode_paged, attention
 from ..ops.cross_entropy import cross_entropy
 from ..ops.fp8 import Fp8Act, add_rms_norm_fp8, fp8_input_slot, fp8_linear, fp8_ok, fp8_swiglu_mlp, rms_fp8_ok
 from ..ops.kv_cache import PAGE, KVCache, PagedKVCache
-from ..ops.linear import (SKINNY_MAX_ROWS, linear, linear_skinny, linear_skinny_w4, linear_skinny_w8,
+from ..ops.linear import (SKINNY_MAX_ROWS, linear, linear_skinny, linear_skinny_w8, linear_w4,
                           quantize_groups_int4, quantize_rows_e4m3)
 from ..ops.rmsnorm import RMSNorm, add_rms_norm
 from ..ops.rope import RotaryTable, rope_append_, rope_append_paged_, rope_append_paged_fp8_, rope_qkv_
@@ -87,11 +89,13 @@ def _skinny(x, training: bool) -> bool:
 
 def _w8(x, mod: nn.Linear, attr: str = "_w8"):
     """``mod``'s (wq, scale) when ``quantize_decode_weights`` left them there (``attr``: ``_w8`` e4m3, ``_w4`` int4)
-    and this call is decode-time (``eval()``, no autograd, at most 64 rows); else None. Weights updated in place
-    since then are refused."""
+    and this call is decode-time (``eval()``, no autograd, at most 64 rows, or any row count when the int4 copy
+    was made with ``all_rows=True``); else None. Weights updated in place since then are refused."""
     q = getattr(mod, attr, None)
-    if (q is None or mod.training or torch.is_grad_enabled() or not isinstance(x, torch.Tensor)
-            or not 0 < x.numel() // x.shape[-1] <= SKINNY_MAX_ROWS):
+    if q is None or mod.training or torch.is_grad_enabled() or not isinstance(x, torch.Tensor):
+        return None
+    rows = x.numel() // x.shape[-1]
+    if rows < 1 or (rows > SKINNY_MAX_ROWS and not (len(q) > 3 and q[3])):  # q[3]: ``all_rows`` (int4 only)
         return None
     if q[2] != mod.weight._version:
         raise RuntimeError("a Linear's weight changed in place after quantize_decode_weights(): its e4m3 copy is "
@@ -119,7 +123,7 @@ def _linear(x, mod: nn.Linear) -> torch.Tensor:
         return linear_skinny_w8(x, q[0], q[1])
     q = _w4(x, mod)
     if q is not None:
-        return linear_skinny_w4(x, q[0], q[1])
+        return linear_w4(x, q[0], q[1])
     if _skinny(x, mod.training):
         return linear_skinny(x, mod.weight)
     return linear(x, mod.weight)
@@ -234,7 +238,7 @@ class LlamaMLP(nn.Module):
             return _linear(linear_skinny_w8(x, q[0], q[1], swiglu=True), self.c_proj)
         q = _w4(x, self.c_fc)
         if q is not None:  # and on the int4 weights
-            return _linear(linear_skinny_w4(x, q[0], q[1], swiglu=True), self.c_proj)
+            return _linear(linear_w4(x, q[0], q[1], swiglu=True), self.c_proj)
         if _skinny(x, self.c_fc.training):  # c_fc with SwiGLU in the GEMM's epilogue: no [rows, 2F] round trip
             return _linear(linear_skinny(x, self.c_fc.weight, swiglu=True), self.c_proj)
         return _linear(swiglu(_linear(x, self.c_fc)), self.c_proj)
@@ -307,7 +311,7 @@ class Llama(nn.Module):
             return linear_skinny_w8(x, q[0], q[1])
         q = _w4(x, self.lm_head)
         if q is not None:
-            return linear_skinny_w4(x, q[0], q[1])
+            return linear_w4(x, q[0], q[1])
         if _skinny(x, self.training):
             return linear_skinny(x, self.lm_head.weight)
         return linear(x, self.lm_head.weight)
@@ -330,21 +334,27 @@ class Llama(nn.Module):
         yield self.lm_head
 
     @torch.no_grad()
-    def quantize_decode_weights(self, dtype: str = "fp8") -> "Llama":
+    def quantize_decode_weights(self, dtype: str = "fp8", all_rows: bool = False) -> "Llama":
         """Quantise every block Linear and the LM head row-wise to e4m3 for decode-time calls (at most 64 rows,
         ``eval()``, no autograd): each module gets ``_w8 = (wq, scale, weight._version)`` as a plain attribute,
         not a parameter or buffer, so ``state_dict()`` is unchanged and the bf16 weights stay for everything
         else. ``dtype="int4"``: group-wise int4 instead (one fp32 scale per 128 inputs), kept as ``_w4`` in the
-        same form. Either call removes what the other left. Call it again after the weights change."""
+        same form. Either call removes what the other left. Call it again after the weights change.
+        ``all_rows=True`` (int4 only) appends the flag to the ``_w4`` tuple: calls on more than 64 rows then run
+        on the int4 copies too (``linear_w4``), so the prompt's K/V rows and the decode steps come from the same
+        weights; the default leaves such calls on the bf16 weights."""
         if dtype not in ("fp8", "int4"):
             raise ValueError(f'quantize_decode_weights: dtype is "fp8" or "int4", got {dtype!r}')
+        if all_rows and dtype == "fp8":
+            raise NotImplementedError('quantize_decode_weights("fp8", all_rows=True): the W8A16 GEMM for more than 64 '
+                                      'rows is not built (only the W8A16 skinny kernel reads e4m3 weights); use "int4"')
         self.drop_decode_weights()
         for mod in self._decode_linears():
             w = mod.weight.detach().to(torch.bfloat16)
             if dtype == "fp8":
                 mod._w8 = (*quantize_rows_e4m3(w), mod.weight._version)
             else:
-                mod._w4 = (*quantize_groups_int4(w), mod.weight._version)
+                mod._w4 = (*quantize_groups_int4(w), mod.weight._version, bool(all_rows))
         return self
 
     def drop_decode_weights(self) -> "Llama":

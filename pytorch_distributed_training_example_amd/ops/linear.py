@@ -23,7 +23,9 @@ stored as e4m3 bytes with one fp32 scale per output feature (csrc/kernels/gemm_s
 stream; ``Llama.quantize_decode_weights()`` opts a model in. ``quantize_groups_int4`` + ``linear_skinny_w4`` store
 symmetric int4 with one fp32 scale per 128 inputs in a layout packed for the kernel
 (csrc/kernels/gemm_skinny_w4.hip; ``pack_int4`` defines it): a quarter of the bytes plus the scales;
-``Llama.quantize_decode_weights("int4")``.
+``Llama.quantize_decode_weights("int4")``. ``linear_w4`` serves the same int4 operands at any row count: above 64
+rows a tiled, compute-bound kernel of its own (csrc/kernels/gemm_w4.hip);
+``Llama.quantize_decode_weights("int4", all_rows=True)``.
 """
 from __future__ import annotations
 
@@ -237,8 +239,8 @@ def linear_gelu(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
 
 # ---------------------------------------------------------------------------- decode-time Linears (M <= 64)
 # launches of the bf16 skinny GEMM, the last (S, FT, NT) any of the kernels ran with, launches of the e4m3-weight
-# one and of the int4-weight one
-SKINNY_STATS = {"native_calls": 0, "geo": None, "w8_calls": 0, "w4_calls": 0}
+# one and of the int4-weight one, launches of the any-row int4 GEMM (gemm_w4.hip)
+SKINNY_STATS = {"native_calls": 0, "geo": None, "w8_calls": 0, "w4_calls": 0, "w4_tall_calls": 0}
 SKINNY_MAX_ROWS = 64
 
 
@@ -450,6 +452,49 @@ def linear_skinny_w4(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor, swi
                                                                                     2 * wq.shape[1], mode, sp))
             return y.view(*x.shape[:-1], y.shape[-1])
     y = F.linear(x, dequantize_groups_int4(wq, scale).to(x.dtype))
+    if swiglu:
+        from .swiglu import swiglu as _swiglu
+        y = _swiglu(y)
+    return y
+
+
+# ---------------------------------------------------------------------------- W4A16 at any row count
+def w4_ok(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor) -> bool:
+    """Inside gemm_w4.hip's contract: ``skinny_w4_ok``'s operands (GPU, bf16 rows, packed int4 weights [N, K / 2]
+    uint8 with fp32 scales [K / 128, N], out features % 16, in features % 256 and below 2^24, contiguous 16-byte
+    aligned weights and scales, the weight below 2^31 bytes) at any row count >= 1."""
+    if not (x.is_cuda and wq.is_cuda and scale.is_cuda and x.dtype == torch.bfloat16 and wq.dtype == torch.uint8
+            and scale.dtype == torch.float32 and wq.dim() == 2 and x.dim() >= 1 and x.shape[-1] == 2 * wq.shape[1]):
+        return False
+    N, K = wq.shape[0], 2 * wq.shape[1]
+    rows = x.numel() // K if K else 0
+    return (1 <= rows <= 64 * 65535 and N % 16 == 0 and N > 0 and K % INT4_LINE == 0 and 0 < K < 2 ** 24
+            and scale.shape == (K // INT4_GROUP, N) and wq.is_contiguous() and wq.data_ptr() % 16 == 0
+            and scale.is_contiguous() and scale.data_ptr() % 16 == 0 and N * (K // 2) < 2 ** 31)
+
+
+def linear_w4(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor, swiglu: bool = False,
+              splits: Optional[int] = None) -> torch.Tensor:
+    """``linear_skinny_w4`` without its row limit. At most 64 rows: exactly ``linear_skinny_w4``. More rows on the
+    GPU inside ``w4_ok`` with no gradient to record: the tiled W4A16 GEMM (csrc/kernels/gemm_w4.hip: the same
+    arithmetic, weights dequantised once per workgroup and held in registers, rows through LDS), then
+    ``ops.swiglu.swiglu`` for ``swiglu``. Anything else (CPU, fp32, ``PDT_DISABLE_NATIVE=1``, autograd on ``x``) is
+    ``F.linear`` on the dequantised weight. ``splits``: grid split-K override (None: the kernel's rule)."""
+    K = x.shape[-1]
+    if K == 0 or x.numel() // K <= SKINNY_MAX_ROWS:
+        return linear_skinny_w4(x, wq, scale, swiglu, splits)
+    needs_grad = torch.is_grad_enabled() and x.requires_grad
+    y = None
+    if use_native(x) and not needs_grad and w4_ok(x, wq, scale):
+        x2 = x.reshape(-1, K).contiguous()
+        if x2.data_ptr() % 16 == 0:
+            sp = int(splits or 0)
+            y = native().gemm_w4(x2, wq, scale, sp)
+            SKINNY_STATS["w4_tall_calls"] += 1
+            SKINNY_STATS["geo"] = tuple(int(v) for v in native().gemm_w4_geo(x2.shape[0], wq.shape[0], K, sp))
+            y = y.view(*x.shape[:-1], y.shape[-1])
+    if y is None:
+        y = F.linear(x, dequantize_groups_int4(wq, scale).to(x.dtype))
     if swiglu:
         from .swiglu import swiglu as _swiglu
         y = _swiglu(y)

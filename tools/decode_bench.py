@@ -47,6 +47,11 @@ the W4A16 skinny GEMM and the W8A16 one (the reference of every time), each rota
 distinct copies; the bytes a candidate must move include its scales. Then the captured step and 128 tokens after a
 128-token prompt on quantize_decode_weights() against quantize_decode_weights("int4").
 
+--gemm-w4-tall: the any-row W4A16 GEMM (csrc/kernels/gemm_w4.hip). llama_medium's five weight shapes at M in
+{128, 512, 2048}: the kernel, F.linear on the bf16 weight (what such rows run without all_rows) and dequantise +
+F.linear take turns in one process, the --gemm-w4 recipe. Then llama_medium with 8 paged slots: a 512-token prefill
+and the captured decode step on quantize_decode_weights("int4") with and without all_rows=True.
+
 --paged: the paged decode kernel. The kernel table's shapes and recipe (captured and replayed, rotating caches,
 alternating, device events, median of the rounds): attention_decode_paged with a sequential block table and
 with a seeded shuffled one against attention_decode on the same keys, and whether the three give the same
@@ -989,6 +994,132 @@ def bench_gemm_w4_generate(rounds, emit, prompt=128, new=128):
          "of positions (a random-weight model: the quantisation moves near-ties, after which the rest differs)")
 
 
+W4_TALL_ROWS = (128, 512, 2048)
+
+
+def bench_gemm_w4_tall(rounds, iters, emit):
+    """--gemm-w4-tall: llama_medium's five weight shapes at M in {128, 512, 2048}: the any-row W4A16 GEMM against
+    F.linear on the bf16 weight (what these rows run without all_rows) and against dequantise + F.linear
+    (linear_skinny_w4's fallback). The --gemm-w4 recipe: captured and replayed (the fallback eagerly), the weights
+    rotating through >= 512 MiB of bf16 copies and their int4 forms, taking turns, device events, median of the
+    rounds."""
+    from pytorch_distributed_training_example_amd.ops._native import native
+    from pytorch_distributed_training_example_amd.ops.linear import dequantize_groups_int4
+    C, dev = native(), "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    for name, N, K, fused in GEMM_SHAPES:
+        if fused:
+            continue  # SwiGLU above 64 rows is the SwiGLU kernel on this kernel's output
+        ncopy = -(-ROTATE_BYTES // (N * K * 2))
+        calls = max(iters, ncopy)
+        w = (torch.randn(ncopy, N, K, device=dev, generator=g) / math.sqrt(K)).bfloat16()
+        q4 = [C.quantize_groups_int4(w[i]) for i in range(ncopy)]
+        w4q, s4 = torch.stack([a for a, _ in q4]), torch.stack([b for _, b in q4])
+        del q4
+        emit(f"## {name}: N = {N}, K = {K}: {N * K / 2**21:.2f} MiB int4 + {N * K / 32 / 2**20:.2f} MiB scales, "
+             f"{N * K / 2**19:.1f} MiB bf16, x {ncopy} copies, {calls} calls per window")
+        for M in W4_TALL_ROWS:
+            x = torch.randn(M, K, device=dev, generator=g).bfloat16()
+            geo = tuple(C.gemm_w4_geo(M, N, K, 0))
+
+            def w4(i):
+                return C.gemm_w4(x, w4q[i % ncopy], s4[i % ncopy], 0)
+
+            def lib(i):
+                return F.linear(x, w[i % ncopy])
+
+            def deq(i):
+                return F.linear(x, dequantize_groups_int4(w4q[i % ncopy], s4[i % ncopy]).to(torch.bfloat16))
+
+            err = (w4(0).float() - deq(0).float()).abs().max().item()
+            # (the torch dequantisation uploads an index, so it cannot be captured: that candidate is timed eagerly,
+            # ten calls of several kernels each, where the launch cost is small beside them)
+            graphs = {"w4": _graphed(w4, calls), "bf16 F.linear": _graphed(lib, calls)}
+            t = {"w4": ([], []), "bf16 F.linear": ([], []), "dequantise + F.linear": ([], [])}
+            for _ in range(rounds):
+                for k in t:
+                    if k in graphs:
+                        t[k][1].append(_time_ms(lambda i, g=graphs[k]: g.replay(), 1) / calls)
+                    else:
+                        t[k][1].append(_time_ms(deq, 10))
+            med = {k: statistics.median(v[1]) for k, v in t.items()}
+            for k, (_, tg) in t.items():
+                emit(f"M {M:4d}  {k:<21} {'(S, BM, BN) = ' + str(geo) if k == 'w4' else '':<30} replayed {med[k] * 1e3:8.1f} us "
+                     f"({min(tg) * 1e3:.1f}-{max(tg) * 1e3:.1f})  {2 * M * N * K / med[k] / 1e9:7.1f} TFLOP/s  "
+                     f"{med['bf16 F.linear'] / med[k]:5.2f}x bf16 F.linear")
+            emit(f"M {M:4d}  max |w4 - dequantise + F.linear| = {err:.3g} (one bf16 rounding of the weight)")
+        del w, w4q, s4
+
+
+def bench_gemm_w4_tall_model(rounds, emit, prompt=512):
+    """llama_medium, 8 paged slots: a 512-token prefill and the captured decode step on
+    quantize_decode_weights("int4") with and without all_rows=True, one process, taking turns."""
+    from pytorch_distributed_training_example_amd.models import get_model
+    from pytorch_distributed_training_example_amd.models.precision import to_bf16_mixed
+    torch.manual_seed(0)
+    model = to_bf16_mixed(get_model("llama_medium").cuda()).eval()
+    idx = torch.randint(0, model.cfg.vocab_size, (B, prompt), generator=torch.Generator().manual_seed(1)).cuda()
+    mods = list(model._decode_linears())
+    model.quantize_decode_weights("int4")
+    saved = {"int4": [m._w4 for m in mods], "int4 all_rows": [(*m._w4[:3], True) for m in mods]}
+    steps = 32
+    pages = -(-(prompt + steps + 4) // 64)
+    cache = model.new_paged_cache(B, B * pages, pages)
+    tok = torch.zeros(B, dtype=torch.long, device="cuda")
+
+    def select(name):
+        for m, q in zip(mods, saved[name]):
+            m._w4 = q
+
+    def prefill(name):
+        select(name)
+        for s in range(B):
+            cache.free(s)
+            cache.admit(s)
+        cache.reserve(prompt + steps + 4)  # the steps' pages too: a replay runs no host code
+        return model.prefill(idx, cache)
+
+    with torch.no_grad():
+        last, graphs = {}, {}
+        for name in saved:
+            last[name] = prefill(name)
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                model.decode_step(tok, cache)
+            torch.cuda.current_stream().wait_stream(side)
+            cache.set_lens([prompt] * B)
+            graphs[name] = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graphs[name]):
+                model.decode_step(tok, cache)
+        ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
+        t_pre, t_step = {n: [] for n in saved}, {n: [] for n in saved}
+        for _ in range(rounds):
+            for name in saved:
+                s, e = ev(), ev()
+                s.record()
+                prefill(name)
+                e.record()
+                torch.cuda.synchronize()
+                t_pre[name].append(s.elapsed_time(e))
+                s, e = ev(), ev()
+                s.record()
+                for _ in range(steps):
+                    graphs[name].replay()
+                e.record()
+                torch.cuda.synchronize()
+                t_step[name].append(s.elapsed_time(e) / steps)
+    for name in saved:
+        mp, ms = statistics.median(t_pre[name]), statistics.median(t_step[name])
+        emit(f"llama_medium, {B} paged slots, {name:<13}: {prompt}-token prefill {mp:8.2f} ms ({min(t_pre[name]):.2f}-"
+             f"{max(t_pre[name]):.2f}), {B * prompt / mp:6.0f} prompt tok/ms; replayed decode step at position {prompt}.."
+             f"{prompt + steps - 1}: {ms:.3f} ms ({min(t_step[name]):.3f}-{max(t_step[name]):.3f})")
+    a, b = last["int4 all_rows"].float(), last["int4"].float()
+    emit(f"llama_medium: last-position logits, all_rows against the bf16-weight prefill: max |difference| = "
+         f"{(a - b).abs().max().item():.3g} of max |logit| = {b.abs().max().item():.3g} (the quantisation of the prompt's "
+         f"Linears); argmax equal in {int((a.argmax(-1) == b.argmax(-1)).sum())} of {B}")
+
+
 SAMPLER_SETTINGS = (("greedy", 0.0, None, None), ("T=0.8", 0.8, None, None), ("T=0.8 k=50", 0.8, 50, None),
                     ("T=0.8 k=50 p=0.9", 0.8, 50, 0.9))
 
@@ -1102,6 +1233,9 @@ def main(argv=None):
     ap.add_argument("--gemm-w4", action="store_true", help="the decode-time Linears on group-wise int4 weights: the W4A16 "
                     "skinny GEMM against the W8A16 one, then the generation on quantize_decode_weights() and on "
                     "quantize_decode_weights(\"int4\")")
+    ap.add_argument("--gemm-w4-tall", action="store_true", help="the any-row W4A16 GEMM at M in {128, 512, 2048} against "
+                    "F.linear on the bf16 weight and dequantise + F.linear, then llama_medium's 512-token paged prefill "
+                    "and captured decode step with and without all_rows=True")
     ap.add_argument("--paged-fp8", action="store_true", help="the e4m3 paged decode kernel against the bf16 paged "
                     "kernel (both captured, rotating caches, taking turns), then the captured llama_medium step on both caches")
     ap.add_argument("--paged", action="store_true", help="the paged decode kernel under a sequential and a shuffled "
@@ -1139,6 +1273,12 @@ def main(argv=None):
             bench_paged(a.rounds, a.iters, emit)
         if not a.no_generate:
             bench_paged_step(a.gen_rounds, emit)
+    elif a.gemm_w4_tall:
+        if not a.no_kernel:
+            with torch.no_grad():
+                bench_gemm_w4_tall(a.rounds, a.iters, emit)
+        if not a.no_generate:
+            bench_gemm_w4_tall_model(a.rounds, emit)
     elif a.gemm_w4:
         if not a.no_kernel:
             bench_gemm_w4(a.rounds, a.iters, emit)
@@ -1158,7 +1298,8 @@ def main(argv=None):
         bench_extend(a.rounds, a.iters, emit)
     elif not a.no_kernel:
         bench_kernel(a.rounds, a.iters, emit)
-    if not a.no_generate and not a.extend and not a.gemm and not a.gemm_w8 and not a.gemm_w4 and not a.paged \
+    if not a.no_generate and not a.extend and not a.gemm and not a.gemm_w8 and not a.gemm_w4 and not a.gemm_w4_tall \
+            and not a.paged \
             and not a.paged_fp8 and not a.sampler:
         bench_generate(a.gen_rounds, emit)
     if a.out:
